@@ -1,11 +1,11 @@
 """bench.py — headline benchmark of the per-frame optimisation hot loop on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Metric (BASELINE.json): optimiser iters/sec (+ rays/sec) on the female-3-casual-like 512x512 configuration
-(configs[1]: N=3 frames per step, 2 garments, 2048 rays/frame, coarse pyramid (225,321,129)), plus the
+(configs[1]: N=3 frames per step, 2 garments, 2048 rays/frame, coarse pyramid (225,321,129)), plus, with --full, the
 256^3 marching-cubes extraction time of configs[2] as extra fields.  A "step" is one pass of
 train.py:317-351 on one batch of synthetic frames (recmv/loop.py).  One process per GPU; frames are sharded
 over ranks (weak scaling: every rank works on its own N frames) with one RCCL all-reduce of the shared
@@ -18,7 +18,16 @@ shorter than the re-mesh period the phase of the re-mesh counter is set so that 
 K steps (re-meshing MORE often than the reference's cadence: `value` is then conservative; `remesh` carries the
 per-step split and the rate at the reference's cadence).
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR then also writes what the last timed step
+hands its caller (the loss it returns and the state it updates: the tensors the optimisation moves, the explicit garment meshes) as
+DIR/<name>.npy (dump_outputs).  Everything else the benchmark measures or checks runs only with --full (each part can still be
+turned off there with its --no-* option): the objects listed for --full below, the serial-order pass, and with N > 1 the timed all-reduce and the
+replica check.
+
+Extra object on every line:
+  remesh       — per-step GPU times from events recorded at the step boundaries of the timed region.
+
+Extra objects on the line with --full:
   roofline     — the dominant kernel (gemm_nt, the fused MFMA layer): algorithmic FLOPs of every launch in the
                  timed region / their HIP-event durations (events recorded on the stream each kernel is launched on)
                  against the dense f32 MFMA peak (157.3 TFLOP/s); `traffic` = HBM bytes per launch from the newest committed
@@ -27,7 +36,6 @@ Extra objects on the line:
   config2      — BASELINE configs[2] as its own measured leg: 257^3 pyramid, Seg3dLossless + MC every step.
   hbm_kernels  — the HBM-bound kernels at the loop's shapes, each timed with HIP events around a captured hipGraph of
                  identical launches (kernel time + the ~1.5 us dependent-launch gap; no Python between launches).
-  remesh       — per-step GPU times from events recorded at the step boundaries of the timed region.
   cpu_baseline — ONE iteration of the SAME scene in the SAME state (the GPU loop's parameters, per-frame tensors and
                  explicit meshes after the timed region, handed to a child process) on host cores through
                  oracle/cpu_port.py (torch-CPU sgemm + C/OpenMP oracle kernels); rank 0, N=1 only.
@@ -641,6 +649,36 @@ def whole_step_matrix_rate(roofline, steps, ms_per_step):
             "note": "all MFMA launches of the timed region on rank 0 (every variant, both GEMM kernels) over the whole step time"}
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6      # --dump-outputs: array data of all files together (under 64 MB with the .npy headers)
+DUMP_KEEP_WHOLE = 4096               # arrays of at most this many elements (the loss, per-net biases, ...) are never sampled
+
+
+def dump_outputs(loop, loss, rays, out_dir):
+    """--dump-outputs: what the last timed step hands its caller — the loss and ray count `HotLoop.step` returns and the state it
+    updates in place (the tensors the optimisation moves, as `_scene_tensors` names them, and the explicit garment meshes) — one
+    DIR/<name>.npy per array, float64 kept, every other dtype as float32.  Should the arrays outgrow DUMP_LIMIT_BYTES, each one of
+    more than DUMP_KEEP_WHOLE elements is cut to the same fraction of its elements, drawn by a fixed seed (flattened, in index
+    order); the small ones stay whole."""
+    import numpy as np
+    arrays = {"loss": loss, "rays": torch.tensor(float(rays), dtype=torch.float64)}
+    arrays.update(_scene_tensors(loop))
+    arrays.update(("mesh.garment_vs.%d" % g, v) for g, v in enumerate(loop.garment_vs))
+    arrays = {k: v.detach().cpu() for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == torch.float64 else v.float() for k, v in arrays.items()}
+    nbytes = lambda vs: sum(v.numel() * v.element_size() for v in vs)
+    small = nbytes(v for v in arrays.values() if v.numel() <= DUMP_KEEP_WHOLE)
+    frac = min(1.0, (DUMP_LIMIT_BYTES - small) / max(1, nbytes(v for v in arrays.values() if v.numel() > DUMP_KEEP_WHOLE)))
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    gen = torch.Generator().manual_seed(0)
+    for k, v in arrays.items():
+        if frac < 1.0 and v.numel() > DUMP_KEEP_WHOLE:
+            v = v.reshape(-1)
+            v = v[torch.randperm(v.numel(), generator=gen)[:int(v.numel() * frac)].sort().values]
+        np.save(out / (k + ".npy"), v.numpy())
+    log("outputs of the last timed step: %d arrays in %s%s" % (len(arrays), out, "" if frac == 1.0 else " (sampled)"))
+
+
 def frames_at(loop, it):
     """Frames this rank takes in optimiser iteration `it`: batch_size, except at an epoch's last position (the reference's DataLoader
     keeps the short last batch, HotLoop.iters_per_epoch) — an iteration on one frame instead of three is ~25 % cheaper."""
@@ -732,12 +770,22 @@ def main(argv=None, device_type="cuda", hotloop_kw=None, conf_overrides=None):
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--state", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--conf", default=str(REPO / "configs" / "synthetic" / "people_snapshot_like.conf"))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline and serial-order pass, MC extraction, "
+                         "hbm_kernels, cpu_baseline, the extra workload legs, with N > 1 the all-reduce timing and replica check")
     args = ap.parse_args(argv)
     if args.cpu_baseline_child:
         _cpu_baseline_child(args.conf, args.state)
         return
+    if not args.full:
+        args.no_mc = args.no_hbm_kernels = args.no_cpu_baseline = args.no_config2 = True
+        args.no_alt_mode = args.no_kernel_events = True
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             launch_ranks(args.gpus, argv, device_type)          # does not return
@@ -837,7 +885,7 @@ def main(argv=None, device_type="cuda", hotloop_kw=None, conf_overrides=None):
             remesh_steps.append(k)
         frames_hist.append(frames_at(loop, it))
         a0 = n_alloc()
-        _, r = loop.step(it, allreduce)
+        loss, r = loop.step(it, allreduce)
         dev_allocs.append(n_alloc() - a0)
         if marks:
             marks[k + 1].record()
@@ -853,6 +901,8 @@ def main(argv=None, device_type="cuda", hotloop_kw=None, conf_overrides=None):
     gs = prof.end() if prof else {}
     small_launches = prof.small if prof else None
     busy_timed = prof.busy if prof else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(loop, loss, r, args.dump_outputs)
     gs_serial = None
     if prof and not args.no_alt_mode:
         # the MFMA kernels once more with the iteration in the reference's serial order (RECMV_SERIAL=1: one stream, no
@@ -883,6 +933,7 @@ def main(argv=None, device_type="cuda", hotloop_kw=None, conf_overrides=None):
         slots[rank] = mine
         tdist.all_reduce(slots, op=tdist.ReduceOp.SUM)
         per_rank_ms = [round(float(v) / args.steps * 1e3, 3) for v in slots]
+    if world > 1 and args.full:
         # the step's collective alone: the flattened all-reduce of the shared gradients (~25 MB), 10 repetitions
         allreduce(loop.shared_parameters())
         sync()

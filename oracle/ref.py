@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 import subprocess
 from pathlib import Path
 
@@ -34,7 +35,7 @@ def available() -> bool:
 def build(force: bool = False) -> bool:
     """Build oracle/_ref from the reference tree when it is mounted (development container); keep prebuilt files
     otherwise (GPU box).  Returns `available()`."""
-    if REFERENCE.exists():
+    if os.path.isdir(REFERENCE):       # (False, not an error, where the tree is there but this user may not read it)
         cmd = ["make", "-C", str(_HERE), "ref"] + (["-B"] if force else [])
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:

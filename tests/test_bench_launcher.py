@@ -10,6 +10,8 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
+
 REPO = Path(__file__).resolve().parent.parent
 SMALL = ["--steps", "2", "--warmup", "1", "--settle-iters", "0", "--scene", "none", "--no-mc", "--no-hbm-kernels", "--no-cpu-baseline", "--no-config2",
          "--no-alt-mode", "--no-kernel-events", "--no-curves"]
@@ -46,8 +48,9 @@ def _line(args, **env):
 
 def test_gpus_2_launches_two_ranks_with_identical_replicas():
     """The entry with `--gpus 2` and no torchrun environment: two ranks over gloo, one line with n_gpus 2, a step time per rank,
-    the shared-gradient exchange timed, replicas bit-identical after the run; twice the frames of the one-rank job per step."""
-    two = _line(["--gpus", "2"])
+    the shared-gradient exchange timed and replicas bit-identical after the run (both with --full); twice the frames of the
+    one-rank job per step."""
+    two = _line(["--gpus", "2", "--full"])
     assert two["n_gpus"] == 2 and two["scaling"] == "weak" and two["steps"] == 2
     cfg = two["config"]
     assert len(cfg["per_rank_ms_per_step"]) == 2 and all(v > 0 for v in cfg["per_rank_ms_per_step"])
@@ -57,6 +60,61 @@ def test_gpus_2_launches_two_ranks_with_identical_replicas():
     assert abs(two["value"] - 2 * 1e3 / two["ms_per_step"]) < 1e-2 * two["value"]       # whole-job rate: N iterations per step time
     one = _line(["--gpus", "1"])
     assert one["n_gpus"] == 1 and one["config"]["per_rank_ms_per_step"] is None and one["config"]["replicas_bit_identical"] is None
+
+
+def test_plain_run_times_the_steps_only_and_dumps_its_last_step(tmp_path):
+    """A plain run (no --full, none of the --no-* options) leaves out everything beyond the headline, and --dump-outputs writes what
+    its last timed step computed: float32 / float64 arrays under 64 MB, the ray count of the LAST step (the line's average differs),
+    and the same arrays bit for bit when the same command runs again."""
+    plain = ["--steps", "3", "--warmup", "1", "--settle-iters", "0", "--scene", "none", "--no-curves"]
+    runs = []
+    for k in range(2):
+        r = subprocess.run([sys.executable, str(REPO / "tests" / "bench_cpu_entry.py"), "--gpus", "1",
+                            "--dump-outputs", str(tmp_path / str(k))] + plain, env=_env(), capture_output=True, text=True,
+                           timeout=1500)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-500:]
+        runs.append(json.loads(lines[0]))
+    line = runs[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["config"]["replicas_bit_identical"] is None
+    for key in ("roofline", "cpu_baseline", "hbm_kernels", "config2", "high_convergence", "full_load", "mc_extract_ms_257",
+                "busy_fraction_timed_region"):
+        assert key not in line, key
+    assert line["matrix_tflop_per_step"] is None
+    out = [{p.stem: np.load(p) for p in (tmp_path / str(k)).glob("*.npy")} for k in range(2)]
+    assert {"loss", "rays", "mesh.garment_vs.0", "model.sdf.lin0.weight_v", "dataset.poses"} <= set(out[0]), sorted(out[0])
+    assert all(a.dtype in (np.float32, np.float64) for a in out[0].values())
+    assert sum(a.nbytes for a in out[0].values()) <= 64 * 10 ** 6
+    assert np.isfinite(out[0]["loss"]).all() and out[0]["loss"].shape == ()
+    assert out[0]["rays"] == line["config"]["rays_per_iter"]              # the last step's count, not the line's average
+    assert out[0]["mesh.garment_vs.0"].ndim == 2 and out[0]["mesh.garment_vs.0"].shape[1] == 3
+    assert set(out[0]) == set(out[1]) and all(np.array_equal(out[0][k], out[1][k]) for k in out[0])
+
+
+def test_dump_outputs_samples_large_arrays_and_keeps_small_ones(tmp_path, monkeypatch):
+    """bench.dump_outputs over its size limit: arrays above DUMP_KEEP_WHOLE elements are cut to one seeded sample (the same
+    on every call), the returned scalars and small tensors are written whole."""
+    import types
+    import torch
+    sys.path.insert(0, str(REPO))
+    import bench
+    gen = torch.Generator().manual_seed(3)
+    ds = types.SimpleNamespace(**{k: torch.randn(4, 3, generator=gen) for k in bench._SCENE_DATASET})
+    loop = types.SimpleNamespace(_BUFFERS=(), dataset=ds, garment_vs=[torch.randn(50000, 3, generator=gen)])
+    state = {"sdf.lin0.weight_v": torch.randn(512, 512, generator=gen), "sdf.lin0.bias": torch.randn(512, generator=gen)}
+    loop.state_dict = lambda: state
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 400_000)
+    for k in range(2):
+        bench.dump_outputs(loop, torch.tensor(1.5), 84, tmp_path / str(k))
+    out = [{p.stem: np.load(p) for p in (tmp_path / str(k)).glob("*.npy")} for k in range(2)]
+    assert out[0]["loss"] == np.float32(1.5) and out[0]["rays"] == 84.0 and out[0]["rays"].dtype == np.float64
+    np.testing.assert_array_equal(out[0]["model.sdf.lin0.bias"], state["sdf.lin0.bias"].numpy())
+    np.testing.assert_array_equal(out[0]["dataset.poses"], ds.poses.numpy())
+    w = out[0]["model.sdf.lin0.weight_v"]
+    assert w.ndim == 1 and 0 < w.size < 512 * 512 and np.isin(w, state["sdf.lin0.weight_v"].numpy()).all()
+    assert sum(a.nbytes for a in out[0].values()) <= 400_000
+    assert all(np.array_equal(out[0][k], out[1][k]) for k in out[0])
 
 
 def test_frames_at_counts_the_short_last_batch_of_an_epoch():

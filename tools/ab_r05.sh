@@ -5,7 +5,7 @@ R=${1:-3}; O=${2:-gpurun_out/ab_r05}; mkdir -p $O
 Q="--steps 20 --warmup 5 --no-cpu-baseline --no-config2 --no-mc --no-hbm-kernels --no-alt-mode"
 for i in $(seq 1 $R); do
   (cd _ab_r05 && python bench.py $Q > ../$O/r05_$i.json 2> ../$O/r05_$i.log)
-  python bench.py $Q > $O/head_$i.json 2> $O/head_$i.log
+  python bench.py $Q --full > $O/head_$i.json 2> $O/head_$i.log      # (--full: the per-launch event brackets, as the old tree has them)
 done
 python - $O <<'PY'
 import json, glob, sys

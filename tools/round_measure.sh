@@ -5,7 +5,7 @@ R=${1:-r06}; SHA=${2:-unknown}
 REPO=$PWD
 O=$REPO/gpurun_out/$R; mkdir -p $O
 export TMPDIR=/tmp
-QUIET="--no-cpu-baseline --no-mc --no-serial-pass --no-hbm-kernels --no-config2"
+QUIET="--full --no-cpu-baseline --no-mc --no-serial-pass --no-hbm-kernels --no-config2"
 cd /tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 300 rocprofv3 --pmc $c --output-format csv -d /tmp/pmc_$c -o run -- python $REPO/bench.py --steps 3 --warmup 1 \
@@ -18,7 +18,7 @@ cd /tmp
 timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof -o run -- python $REPO/bench.py $QUIET > $O/${R}_bench_line_traced_command.json 2> /tmp/trace.err
 cd $REPO
 (echo "# rocprofv3 --kernel-trace --stats -- python bench.py $QUIET   (commit $SHA, frozen scene v1)"; python tools/prof_summary.py /tmp/prof 45) > $O/${R}_bench_kernel_trace.txt 2>&1
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${R}_bench_line_driver_command.json 2> $O/${R}_bench_driver.err
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${R}_bench_line_driver_command.json 2> $O/${R}_bench_driver.err
 tail -3 $O/${R}_bench_driver.err
 ( time timeout 900 python bench.py > $O/${R}_bench_line_default_command.json 2> $O/${R}_bench_default.err ) 2> $O/${R}_bench_default_walltime.txt
 python tools/op_census.py --top 80 2>&1 | grep -v "Warn\|amdgpu\|run_backward" > $O/${R}_op_census.txt
