@@ -432,6 +432,31 @@ int recmv_rasterize_meshes(const float* face_verts, const int64_t* mesh_first_fa
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Vertex normals + hard Phong shading of rasterised meshes (csrc/shade_meshes.hip, ABI v10).
+ *   replaces pytorch3d 0.4.0's `Meshes.verts_normals_packed` and `HardPhongShader` (phong_shading, PointLights,
+ *   Materials, hard_rgb_blend) of the inference renders (engineer/networks/OptimGarmentNetwork.py:3216-3306, shader
+ *   set by infer_fl.py), with the IoU mask error of :3241-3243 as optional integer counts.
+ * recmv_verts_normals: verts [N,V,3] f32, ONE face table faces [F,3] int64 shared by the N meshes, the vertex -> (face,
+ *   corner) adjacency adj_offsets [V+1] / adj_codes [3F] int32 (code = face * 3 + corner, each vertex's list ordered
+ *   corner 1, corner 2, corner 0 and by ascending face inside each: pytorch3d's summation order) -> normals [N,V,3]
+ *   = normalize(sum of corner cross products, eps 1e-6).  No float atomics: bitwise reproducible, independent of N.
+ * recmv_hard_phong_shade: one thread per pixel.  pix_to_face [N,H,W] int64 packed (mesh * F + face, < 0 = empty) and
+ *   bary_coords [N,H,W,3] of recmv_rasterize_meshes; colors [colors_batch,V,3] with colors_batch 1 or N (TexturesVertex);
+ *   cam_centers [N,3] (camera centre per image, device); params_host: recmv_hard_phong_params_floats() host floats =
+ *   light location[3], light ambient[3], diffuse[3], specular[3] colours, material ambient[3], diffuse[3], specular[3],
+ *   shininess, background colour[3].  images [N,H,W,4] f32 RGBA (16-byte aligned): (ambient + diffuse) * texel +
+ *   specular, background colour where empty, alpha 1.  gt_mask [N,H,W] f32 (nonzero = inside) and counts [N,2] int64
+ *   (both or neither): counts[n] = (|M n G|, |M u G|) with M = (pix_to_face >= 0), exact and order independent.
+ * ---------------------------------------------------------------------------------------------- */
+int recmv_verts_normals(const float* verts, const int64_t* faces, const int32_t* adj_offsets, const int32_t* adj_codes,
+                        int64_t N, int64_t V, int64_t F, float* normals, void* stream);
+int64_t recmv_hard_phong_params_floats(void);
+int recmv_hard_phong_shade(const int64_t* pix_to_face, const float* bary_coords, const float* verts, const float* normals,
+                           const float* colors, int64_t colors_batch, const int64_t* faces, const float* cam_centers,
+                           int64_t N, int64_t V, int64_t F, int64_t H, int64_t W, const float* params_host, float* images,
+                           const float* gt_mask, int64_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Point-cloud rasteriser + alpha compositor, forward and backward (csrc/rasterize_points.hip).
  *   replaces `self.pcRender(Pointclouds(...))` of the mask loss (engineer/networks/OptimGarmentNetwork.py:937;
  *   PointsRendererWithFrags(_Split) model/CameraMine.py:306-415; settings engineer/networks/OptimNetwork.py:87-100:

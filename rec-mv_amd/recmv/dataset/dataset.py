@@ -43,6 +43,23 @@ def read_image_bgr(path):
     return np.ascontiguousarray(rgb[:, :, ::-1])
 
 
+
+def write_image_bgr(path, img):
+    """`cv2.imwrite(path, img)` for a uint8 [H,W,3] image in B,G,R order (or [H,W] grey, or [H,W,4] B,G,R,A); the format
+    follows the file name's extension.  Returns True like cv2.imwrite."""
+    from PIL import Image
+    a = np.asarray(img)
+    if a.dtype != np.uint8:
+        raise ValueError("write_image_bgr: uint8 images only (got %s)" % a.dtype)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if a.ndim == 3 and a.shape[2] in (3, 4):
+        a = np.concatenate([a[:, :, 2::-1], a[:, :, 3:]], axis=2)
+    elif a.ndim != 2:
+        raise ValueError("write_image_bgr: [H,W], [H,W,3] or [H,W,4] images only (got %s)" % (a.shape,))
+    Image.fromarray(np.ascontiguousarray(a)).save(path)
+    return True
+
 def dct_space(k, n):
     """First k rows of the orthonormal DCT-II basis of length n (utils/utils.py:293-304: DCTBasis / DCTSpace)."""
     idx = torch.arange(n, dtype=torch.float64) + 0.5

@@ -231,3 +231,54 @@ class ConfigFactory:
     def parse_file(path):
         with open(path, "r") as f:
             return ConfigFactory.parse_string(f.read())
+
+
+_BARE_KEY = re.compile(r'^[A-Za-z0-9_\-]+$')
+
+
+class HOCONConverter:
+    """pyhocon's `HOCONConverter.convert(config, 'hocon')`: a ConfigTree as HOCON text that ConfigFactory.parse_string
+    reads back to an equal tree (strings quoted, objects as `key { ... }`, lists inline).  What train.py writes to
+    `<save folder>/config.conf` and infer_fl.py reads (reference train.py:103-104)."""
+
+    @staticmethod
+    def convert(config, output_format='hocon', indent=2):
+        if output_format != 'hocon':
+            raise ConfigException("HOCONConverter.convert: only the 'hocon' format is provided")
+        return HOCONConverter._object(config, 0, indent, top=True)
+
+    @staticmethod
+    def _key(k):
+        import json
+        k = str(k)
+        return k if _BARE_KEY.match(k) else json.dumps(k)
+
+    @staticmethod
+    def _value(v, level, indent):
+        import json
+        if isinstance(v, ConfigTree) or isinstance(v, dict):
+            return HOCONConverter._object(v, level, indent)
+        if isinstance(v, list):
+            return "[" + ", ".join(HOCONConverter._value(x, level, indent) for x in v) + "]"
+        if isinstance(v, bool):
+            return "true" if v else "false"
+        if v is None:
+            return "null"
+        if isinstance(v, int):
+            return str(v)
+        if isinstance(v, float):
+            return repr(v)
+        return json.dumps(str(v))
+
+    @staticmethod
+    def _object(tree, level, indent, top=False):
+        pad = " " * (indent * (level + (0 if top else 1)))
+        lines = []
+        for k, v in dict.items(tree):
+            if isinstance(v, dict):
+                lines.append("%s%s %s" % (pad, HOCONConverter._key(k), HOCONConverter._object(v, level + (0 if top else 1), indent)))
+            else:
+                lines.append("%s%s = %s" % (pad, HOCONConverter._key(k), HOCONConverter._value(v, level, indent)))
+        if top:
+            return "\n".join(lines) + "\n"
+        return "{\n" + "\n".join(lines) + ("\n" if lines else "") + " " * (indent * level) + "}"

@@ -1,0 +1,208 @@
+"""Inference of a trained run: per-frame posed garment meshes, their Phong renders and their colour renders.
+
+`OptimGarmentNetwork.infer` (engineer/networks/OptimGarmentNetwork.py:3216-3306), the function infer_fl.py's loop is built
+on, restated on the recmv kernels for every garment of a HotLoop:
+  deformer (offset MLP + skinning)   -> posed meshes of the N frames                               :3242-3246
+  MeshRasterizer + HardPhongShader   -> `imgs` (white TexturesVertex, PointLights at (0,1,0)),    :3247-3258
+                                        mask error 1 - |M n G| / |M u G| when a ground truth is given
+  canonical-pose mesh (offset only)  -> `def1imgs` through a camera behind the subject             :3262-3269
+  FindSurfacePs + camera rays + OptimizeGarmentSurfaceSinlge + SDF normal + compute_cardinal_rays
+  + netRender                        -> `colors` on a white canvas                                 :3271-3300
+The shading runs on csrc/shade_meshes.hip (recmv.shading), the rest on the kernels the loop uses.  Everything runs
+without autograd except the SDF normal and the cardinal rays, which differentiate the nets as the reference does.
+"""
+import time
+
+import numpy as np
+import torch
+
+from . import raster, shading, utils
+from .model import RectifiedPerspectiveCameras
+
+COLOR_CHUNK = 10000            # rays per root-finder / colour call (:3275)
+_DEF1_R = ((-1., 0., 0.), (0., 1., 0.), (0., 0., -1.))       # second camera of :3264
+
+
+def _to_uint8(x):
+    """torch.clamp(x * 255, 0, 255) -> numpy uint8 by truncation, as the reference converts (:3258, :3268)."""
+    return torch.clamp(x * 255., min=0., max=255.).cpu().numpy().astype(np.uint8)
+
+
+class _Clock:
+    """Wall-time split of the inference (shading / colour-branch root finding / ...), synchronised at each boundary; a
+    no-op without a dict to fill."""
+
+    def __init__(self, acc, device):
+        self.acc, self.cuda = acc, acc is not None and torch.device(device).type == 'cuda'
+        self.t = time.perf_counter() if acc is not None else None
+
+    def lap(self, name):
+        if self.acc is None:
+            return
+        if self.cuda:
+            torch.cuda.synchronize()
+        now = time.perf_counter()
+        self.acc[name] = self.acc.get(name, 0.0) + (now - self.t)
+        self.t = now
+
+
+def _render(meshes, cameras, H, W, lights, gt_mask=None):
+    """maskRender(defMeshes, cameras=..., lights=...) with the HardPhongShader: (images [N,H,W,4], fragments, counts)."""
+    frags = raster.MeshRasterizer(cameras, (H, W), blur_radius=0., perspective_correct=True, cull_backfaces=False)(
+        meshes.verts_padded(), meshes.faces)
+    N = meshes.verts_padded().shape[0]
+    out = shading.hard_phong_shade(frags, meshes.verts_padded(), meshes.faces, meshes.verts_normals_padded(),
+                                   meshes.textures.verts_features_padded(), shading._camera_centers(cameras, N, frags.pix_to_face.device),
+                                   lights, shading.Materials(), shading.BlendParams(), gt_mask)
+    images, counts = out if gt_mask is not None else (out, None)
+    return images, frags, counts
+
+
+def infer_garments(loop, TmpVs_list, Tmpfs_list, H, W, ratio, frame_ids, notcolor=False, gts=None, garments=None,
+                   chunk=COLOR_CHUNK, timings=None):
+    """The per-garment body of `infer` for every garment (or the indices in `garments`): a dict of lists over garments,
+    'colors' (uint8 [N,H,W,3], None with `notcolor`), 'imgs' (uint8 [N,H,W,3] with `gts`, [N,H,W,4] without), 'def1imgs'
+    (uint8 [N,H,W,4]), 'defMeshVs' (float32 [N,V,3]) and 'maskE' (float32 [N] with `gts`, else None).
+    `gts`: {'mask': [N,H,W] float, optional 'image': [N,H,W,3] in [0,1], B,G,R}.  `timings`: a dict that receives the
+    wall time in seconds of 'deform', 'shading', 'surface_points', 'root_finding' and 'color' (synchronised)."""
+    device = TmpVs_list[0].device
+    clock = _Clock(timings, device)
+    N = frame_ids.numel()
+    focals, pps, Rs, Ts, _, _ = loop.dataset.get_camera_parameters(1, device)
+    with torch.no_grad():
+        cameras = RectifiedPerspectiveCameras(focals.detach(), pps.detach(), Rs.detach(), Ts.detach(), image_size=[(W, H)])
+        newTs = loop.dataset.trans.detach().mean(0).to(device).view(1, 3)
+        newcameras = RectifiedPerspectiveCameras(focals.detach(), pps.detach(), torch.tensor([_DEF1_R], device=device), newTs,
+                                                 image_size=[(W, H)])
+        def1_lights = shading.PointLights(location=((0., 1., float(newTs[0, 2])),))
+        d_cond_list, poses, trans, rendcond = loop.get_grad_parameters(frame_ids, device)
+        d_cond_list = [c.detach() for c in d_cond_list[1:]]           # idx 0: the body's code
+        poses, trans = poses.detach(), trans.detach()
+        rendcond = rendcond.detach() if rendcond is not None else None
+    out = {k: [] for k in ('colors', 'imgs', 'def1imgs', 'defMeshVs', 'maskE')}
+    for g_i, (TmpVs, Tmpfs, name) in enumerate(zip(TmpVs_list, Tmpfs_list, loop.garment_names)):
+        if garments is not None and g_i not in garments:
+            continue
+        TmpVs = TmpVs.detach()
+        d_cond = d_cond_list[g_i]
+        if TmpVs.shape[0] == 0 or Tmpfs.shape[0] == 0:
+            _empty_garment(out, N, H, W, notcolor, gts, device)
+            continue
+        white = shading.TexturesVertex(torch.ones_like(TmpVs)[None])
+        with torch.no_grad():
+            defTmpVs = loop.deformer(TmpVs[None, :, :].expand(N, -1, 3), [d_cond, [poses, trans]], ratio=ratio,
+                                     offset_type=name).contiguous()
+            defMeshVs = defTmpVs.cpu().numpy()
+            cano = loop.deformer.defs[0](TmpVs[None, :, :].expand(N, -1, 3), d_cond, ratio=ratio, offset_type=name)
+            clock.lap('deform')
+            meshes = shading.Meshes(defTmpVs, Tmpfs, white)
+            gt_mask = gts['mask'].to(device) if gts else None
+            imgs, frags, counts = _render(meshes, cameras, H, W, shading.PointLights(), gt_mask)
+            maskE = None
+            if gts:
+                masks = frags.pix_to_face[..., 0] >= 0
+                maskE = shading.mask_error(counts).cpu().numpy()
+                gts['maskE'] = maskE
+                imgs = imgs[..., :3]
+                if 'image' in gts:
+                    imgs[~masks] = gts['image'].to(device)[~masks][:, [2, 1, 0]]
+            imgs = _to_uint8(imgs)
+            cmeshes = shading.Meshes(cano.contiguous(), Tmpfs, white)
+            cmeshes._adjacency = meshes._adjacency                    # same face table
+            def1imgs, _, _ = _render(cmeshes, newcameras, H, W, def1_lights)
+            def1imgs = _to_uint8(def1imgs)
+            clock.lap('shading')
+            batch_inds, row_inds, col_inds, initTmpPs, _ = utils.FindSurfacePs(TmpVs, Tmpfs, frags)
+            rays = cameras.view_rays_pix(col_inds, row_inds)
+            defconds = [d_cond, [poses, trans]]
+            clock.lap('surface_points')
+        colors = None
+        if not notcolor:
+            colors = _color_branch(loop, g_i, name, cameras, rays, initTmpPs, batch_inds, defconds, rendcond, ratio, chunk,
+                                   clock)
+            canvas = torch.ones(N, H, W, 3, device=device) * 255.
+            canvas[batch_inds, row_inds, col_inds, :] = colors
+            if gts and 'image' in gts:
+                canvas[~masks] = gts['image'].to(device)[~masks][:, :3] * 255.
+            colors = canvas.cpu().numpy().astype(np.uint8)
+            clock.lap('color')
+        out['colors'].append(colors)
+        out['imgs'].append(imgs)
+        out['def1imgs'].append(def1imgs)
+        out['defMeshVs'].append(defMeshVs)
+        out['maskE'].append(maskE)
+    return out
+
+
+def _empty_garment(out, N, H, W, notcolor, gts, device):
+    """A garment whose extraction found no surface: nothing covers a pixel (images of the background, maskE = 1 - 0 / |G|)."""
+    maskE = None
+    if gts:
+        g = (gts['mask'].to(device) != 0).view(N, -1).sum(1)
+        maskE = shading.mask_error(torch.stack([torch.zeros_like(g), g], 1)).cpu().numpy()
+        gts['maskE'] = maskE
+        imgs = (gts['image'].to(device)[..., [2, 1, 0]] if 'image' in gts else torch.ones(N, H, W, 3, device=device))
+    else:
+        imgs = torch.ones(N, H, W, 4, device=device)
+    colors = None
+    if not notcolor:
+        colors = (gts['image'].to(device)[..., :3] * 255. if gts and 'image' in gts
+                  else torch.ones(N, H, W, 3, device=device) * 255.).cpu().numpy().astype(np.uint8)
+    out['colors'].append(colors)
+    out['imgs'].append(_to_uint8(imgs))
+    out['def1imgs'].append(np.full((N, H, W, 4), 255, np.uint8))
+    out['defMeshVs'].append(np.zeros((N, 0, 3), np.float32))
+    out['maskE'].append(maskE)
+
+
+def _color_branch(loop, g_i, name, cameras, rays, initTmpPs, batch_inds, defconds, rendcond, ratio, chunk, clock):
+    """:3271-3296 — per chunk of rays: root finder, SDF normal, cardinal rays, colour net; clamp((c/2 + .5) * 255).  Every
+    step is per ray (the kernels' rows are independent), so the colours do not depend on `chunk`."""
+    net = loop.garment_nets[g_i]
+    cam_pos = cameras.cam_pos().detach()
+    tcolors = []
+    for rays_, ps_, b_ in zip(torch.split(rays, chunk), torch.split(initTmpPs, chunk), torch.split(batch_inds, chunk)):
+        with torch.no_grad():
+            ps_, _check = utils.OptimizeGarmentSurfaceSinlge(cam_pos, rays_.detach(), ps_.clone(), b_, net, ratio,
+                                                             loop.deformer, defconds, dthreshold=1.e-4,
+                                                             athreshold=loop.angThred, w1=3.05, w2=1., times=30,
+                                                             offset_type=name)
+        clock.lap('root_finding')
+        with torch.enable_grad():
+            ps_ = ps_.detach().clone().requires_grad_(True)
+            sdfs = net(ps_, ratio)
+            feats = net.rendcond
+            nx = torch.autograd.grad(sdfs, ps_, torch.ones_like(sdfs), retain_graph=False, create_graph=False)[0]
+            nx = nx / nx.norm(dim=1, keepdim=True)
+            crays, defVs = utils.compute_cardinal_rays(loop.deformer, ps_, rays_, defconds, b_, ratio, 'test',
+                                                       offset_type=name)
+        with torch.no_grad():
+            c = utils.compute_netRender_color(loop.netRender, ps_.detach(), defVs.detach(), nx.detach(), crays.detach(),
+                                              feats.detach(), rendcond[b_] if rendcond is not None else None, ratio)
+            tcolors.append(c)
+        clock.lap('color')
+    if not tcolors:
+        return torch.zeros(0, 3, device=rays.device)
+    return torch.clamp((torch.cat(tcolors, dim=0) / 2. + 0.5) * 255., min=0., max=255.)
+
+
+def infer(loop, TmpVs_list, Tmpfs_list, H, W, ratio, frame_ids, notcolor=False, gts=None):
+    """OptimGarmentNetwork.infer (:3216-3306): (colors_list, imgs_list, def1imgs_list, defMeshVs_list) of numpy arrays;
+    with `notcolor` the reference returns after its first garment: (None, imgs, def1imgs, defMeshVs).  With `gts`,
+    gts['maskE'] is set to the mask error of the last garment rendered."""
+    if notcolor:
+        r = infer_garments(loop, TmpVs_list, Tmpfs_list, H, W, ratio, frame_ids, True, gts, garments=(0,))
+        return None, r['imgs'][0], r['def1imgs'][0], r['defMeshVs'][0]
+    r = infer_garments(loop, TmpVs_list, Tmpfs_list, H, W, ratio, frame_ids, False, gts)
+    return r['colors'], r['imgs'], r['def1imgs'], r['defMeshVs']
+
+
+@torch.no_grad()
+def posed_body(loop, frame_ids, ratio=None):
+    """The canonical body template posed by the skinner with each frame's pose and translation (deformer.defs[1]):
+    (vertices [N,V,3], faces [F,3]) — what infer_fl.py writes to smpl_meshs/."""
+    loop._ensure_body_template()
+    _, poses, trans, _ = loop.get_grad_parameters(frame_ids, loop.device)
+    N = frame_ids.numel()
+    vs = loop.deformer.defs[1](loop.tmpBodyVs.view(1, -1, 3).expand(N, -1, 3), [poses.detach(), trans.detach()])
+    return vs, loop.tmpBodyFs

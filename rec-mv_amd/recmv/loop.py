@@ -755,6 +755,17 @@ class HotLoop:
             torch.cuda.current_stream(self.device).wait_event(ev)
         return frags
 
+    # ------------------------------------------------------------------------------------------ inference
+    def infer(self, TmpVs_list, Tmpfs_list, H, W, ratio, frame_ids, notcolor=False, gts=None):
+        """OptimGarmentNetwork.py:3216-3306 (recmv/inference.py): posed garment meshes, Phong and colour renders."""
+        from . import inference
+        return inference.infer(self, TmpVs_list, Tmpfs_list, H, W, ratio, frame_ids, notcolor, gts)
+
+    def infer_garments(self, TmpVs_list, Tmpfs_list, H, W, ratio, frame_ids, notcolor=False, gts=None, **kwargs):
+        """`infer`'s per-garment work for every garment, also with `notcolor` (recmv/inference.py:infer_garments)."""
+        from . import inference
+        return inference.infer_garments(self, TmpVs_list, Tmpfs_list, H, W, ratio, frame_ids, notcolor, gts, **kwargs)
+
     # ------------------------------------------------------------------------------------------ feature curves
     def _ensure_body_template(self):
         """`tmpBodyVs` / `tmpBodyFs`: the SMPL template in canonical space the body z-buffer tests rasterise (6890 vertices in

@@ -18,7 +18,7 @@ from ..FastMinv import Fast3x3Minv, Fast3x3Minv_backward
 
 __all__ = ["save_model", "load_model", "set_hierarchical_config", "FastDiff3x3MinvFunction", "quat2mat", "annealing_weights", "GMRobustError", "sample_points",
            "compute_Jacobian", "batch_compute_Jacobian", "compute_deformed_normals", "compute_cardinal_rays",
-           "compute_netRender_color", "scatter_mean", "write_ply", "read_ply", "smpl_tmp_Apose"]
+           "compute_netRender_color", "scatter_mean", "write_ply", "read_ply", "write_obj", "read_obj", "smpl_tmp_Apose"]
 
 
 class FastDiff3x3MinvFunction(Function):
@@ -253,6 +253,34 @@ def read_ply(name):
         raise ValueError(name + ': non-triangle face')
     return torch.from_numpy(v.copy()), torch.from_numpy(rows['idx'].astype(np.int64))
 
+
+
+def write_obj(name, verts, faces):
+    """pytorch3d's `save_obj(f, verts, faces)` (pytorch3d/io/obj_io.py, default precision): `v %f %f %f` lines, then
+    `f %d %d %d` lines with 1-based indices — what infer_fl.py writes to meshs/ and smpl_meshs/."""
+    v = np.asarray(torch.as_tensor(verts).detach().cpu().float().numpy()).reshape(-1, 3)
+    f = np.asarray(torch.as_tensor(faces).detach().cpu().long().numpy()).reshape(-1, 3) + 1
+    with open(name, 'w') as fh:
+        if v.shape[0]:
+            fh.write("\n".join("v %f %f %f" % tuple(r) for r in v.tolist()))
+        if f.shape[0]:
+            fh.write("\n" + "\n".join("f %d %d %d" % tuple(r) for r in f.tolist()))
+        fh.write("\n")
+
+
+def read_obj(name):
+    """(vertices float32 [V,3], faces int64 [F,3], 0-based) of a triangle OBJ's `v` / `f` lines (`f a/b/c` forms allowed)."""
+    vs, fs = [], []
+    with open(name) as fh:
+        for line in fh:
+            parts = line.split()
+            if not parts:
+                continue
+            if parts[0] == 'v':
+                vs.append([float(x) for x in parts[1:4]])
+            elif parts[0] == 'f':
+                fs.append([int(x.split('/')[0]) - 1 for x in parts[1:4]])
+    return (torch.tensor(vs, dtype=torch.float32).view(-1, 3), torch.tensor(fs, dtype=torch.int64).view(-1, 3))
 
 def smpl_tmp_Apose(init_pose_type=0):
     """utils/utils.py:68-99 — the canonical pose the skinning volume is baked in: legs spread by 10 / 7 / 15 / 15 degrees, arms

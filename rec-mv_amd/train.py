@@ -254,6 +254,10 @@ def main(argv=None, large_pose=False):
                                          a_pose=bool(getattr(args, 'a_pose', False)))
         for t in capture.conds + [capture.poses, capture.trans, capture.shape] + list(capture.camera_params.values()):
             t.data = t.data.to(device)            # the reference keeps these on the host and moves batches per call
+    if rank == 0:                                 # train.py:103-104: the run's config beside its checkpoints (infer_fl.py reads it)
+        from recmv.hocon import HOCONConverter
+        with open(osp.join(save_root, 'config.conf'), 'w') as fh:
+            fh.write(HOCONConverter.convert(config, 'hocon'))
     # The start-up stage (first-run skinner bake, SDF pre-fit, feature-line registration) draws unsynchronised random numbers and
     # leaves files other ranks would read half-written: rank 0 runs it FIRST, the other ranks wait at a barrier and then find the
     # stored files (initial_skinner_*.pth, initial_sdf_*.pth, fl_init/init_trans_matrix.pth) like any later run does.
