@@ -613,6 +613,29 @@ int recmv_profile_large(double* out, int n_variants);
  * streams on one time axis), out2[1] = seconds from the first bracketed start to the last bracketed end. */
 int recmv_profile_busy(double* out2);
 
+/* ------------------------------------------------------------------------------------------------
+ * Non-rigid ICP of a garment template (csrc/nricp.hip; added to ABI v10, no existing signature changed).  No float
+ * atomics: bitwise reproducible.
+ * recmv_knn1: exact 1-nearest neighbour of every source point p [N,3] f32 among the targets q [M,3] f32 (pytorch3d
+ *   knn_points K=1): idx [N] int64 and squared distance dist [N] f32; ties go to the lowest target index.  N = 0 is a
+ *   no-op, M = 0 an argument error.  Workspace: recmv_knn1_workspace_bytes(N), 8-byte aligned.
+ * recmv_nricp_energy: one inner iteration of NRICP_Optimizer_AdamW at the affine maps A [N,3,3], b [N,3] of the rest
+ *   positions x [N,3], closest points c [N,3] with normals nc [N,3], template normals nx [N,3], interior [N] u8;
+ *   edges [E,2] int64 (unique undirected), inc_offsets [N+1] / inc_edges [2E] int32 (vertex -> incident edges),
+ *   nbr_offsets [N+1] / nbr_idx [2E] int32 (vertex -> neighbours, degree = row length).  Writes scalars [4] f32 =
+ *   (loss, vert_sum, stiff_sum, lap) on the device, the weight mask [N] u8 and the gradients dA [N,3,3], db [N,3].
+ *   Workspace: recmv_nricp_energy_workspace_bytes(N), 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t recmv_knn1_workspace_bytes(int64_t N);
+int recmv_knn1(const float* p, int64_t N, const float* q, int64_t M, int64_t* idx, float* dist, void* workspace,
+               int64_t workspace_bytes, void* stream);
+int64_t recmv_nricp_energy_workspace_bytes(int64_t N);
+int recmv_nricp_energy(const float* A, const float* b, const float* x, const float* c, const float* nc, const float* nx,
+                       const uint8_t* interior, const int64_t* edges, int64_t E, const int32_t* inc_offsets,
+                       const int32_t* inc_edges, const int32_t* nbr_offsets, const int32_t* nbr_idx, int64_t N,
+                       float gamma, float stiffness_weight, float laplacian_weight, float threshold, float* scalars,
+                       uint8_t* mask, float* dA, float* db, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

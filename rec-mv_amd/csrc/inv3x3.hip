@@ -19,35 +19,7 @@ constexpr int kBlk = 256;
 // (oracle/recmv_oracle.c is compiled with -ffp-contract=off).  The kernel is memory bound.
 #pragma clang fp contract(off)
 
-template <typename T>
-__device__ __forceinline__ bool inv_one(const T* m, T* inv) {
-  T cof00 = m[4] * m[8] - m[5] * m[7];
-  T cof01 = -m[3] * m[8] + m[5] * m[6];
-  T cof02 = m[3] * m[7] - m[4] * m[6];
-  T cof10 = -m[1] * m[8] + m[2] * m[7];
-  T cof11 = m[0] * m[8] - m[2] * m[6];
-  T cof12 = -m[0] * m[7] + m[1] * m[6];
-  T cof20 = m[1] * m[5] - m[2] * m[4];
-  T cof21 = -m[0] * m[5] + m[2] * m[3];
-  T cof22 = m[0] * m[4] - m[1] * m[3];
-  T det = m[0] * cof00 + m[1] * cof01 + m[2] * cof02;
-  // reference: fabs(det) < 0.0001 with a double literal -> the comparison is done in double
-  if (fabs((double)det) < 0.0001) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) inv[i] = (T)0;
-    return false;
-  }
-  inv[0] = cof00 / det;
-  inv[1] = cof10 / det;
-  inv[2] = cof20 / det;
-  inv[3] = cof01 / det;
-  inv[4] = cof11 / det;
-  inv[5] = cof21 / det;
-  inv[6] = cof02 / det;
-  inv[7] = cof12 / det;
-  inv[8] = cof22 / det;
-  return true;
-}
+#include "inv3x3_one.h"
 
 template <typename T>
 __device__ __forceinline__ void inv_bwd_one(const T* g, const T* c, T* out) {

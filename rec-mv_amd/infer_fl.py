@@ -11,11 +11,14 @@ extracts the canonical meshes at the `fine` pyramid, and for every frame (up to 
   smpl_meshs/smpl_{fid:06d}.obj         body template posed by the skinner
   mask_error.json                       1 - IoU of each garment's silhouette with the frame's mask
 
-Not provided: `infer_garment` / `registration` (template registration with the reference's NR-ICP and
-Laplacian tools: registry_*.obj, render/*.png) and `infer_garment_fl`.  `--nV` is accepted and ignored (the reference
-writes no video either).  The capture is read in this process (no loader workers).
+With `--registry` the garments posed are the registered template meshes `<rec-root>/registry_<garment>.obj` that
+register_fl.py writes (`infer_garment`, :2960-3120) instead of the MC meshes; the per-garment files keep their names, and
+every frame also gets the merged render of all garments in flat colours, render/{fid:06d}.png.
 
-    python rec-mv_amd/infer_fl.py --gpu-ids 0 --rec-root <capture>/<save-folder> --data-type scene
+Not provided: the template cut from the SMPL assets and `infer_garment_fl`.  `--nV` is accepted and ignored
+(the reference writes no video either).  The capture is read in this process (no loader workers).
+
+    python rec-mv_amd/infer_fl.py --gpu-ids 0 --rec-root <capture>/<save-folder> --data-type scene [--registry]
 """
 import argparse
 import json
@@ -40,15 +43,17 @@ def build_parser():
     parser.add_argument('--nColor', action='store_true', help='not render images')
     parser.add_argument('--a_pose', action='store_true', help='using a-pose images to extract garment_meshes')
     parser.add_argument('--conf', default=None, metavar='M', help='config file (default: <rec-root>/config.conf)')
+    parser.add_argument('--registry', action='store_true',
+                        help='pose the registered meshes <rec-root>/registry_*.obj (register_fl.py) and write render/*.png')
     return parser
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
-    assert not (args.nV and args.nI)
+def load_run(args):
+    """The trained run of `args` and its canonical meshes at the fine pyramid: (optNet, dataset, dataloader, TmpVs_list,
+    Tmpfs_list), index 0 the body, then the garments."""
     import torch
-    from recmv import inference, utils
-    from recmv.dataset import getDatasetAndLoader, write_image_bgr
+    from recmv import utils
+    from recmv.dataset import getDatasetAndLoader
     from recmv.hocon import ConfigFactory
     from recmv.loop import RESOLUTIONS
     from recmv.model.network import getOptNet
@@ -79,15 +84,42 @@ def main(argv=None):
     optNet, dataset, _ = utils.load_model(osp.join(rec_root, 'latest.pth'), optNet, dataset, device)
     optNet.dataset = dataset
     optNet.eval()
-    H, W = dataset.H, dataset.W
-
-    ratio = {'sdfRatio': 1., 'deformerRatio': 1., 'renderRatio': 1.}
     with torch.no_grad():
-        TmpVs_list, Tmpfs_list = optNet.discretizeSDF(ratio, None, 0.)
+        TmpVs_list, Tmpfs_list = optNet.discretizeSDF(RATIO, None, 0.)
+    return optNet, dataset, dataloader, TmpVs_list, Tmpfs_list
+
+
+RATIO = {'sdfRatio': 1., 'deformerRatio': 1., 'renderRatio': 1.}
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    assert not (args.nV and args.nI)
+    import torch
+    from recmv import inference, registration, utils
+    from recmv.dataset import write_image_bgr
+    from recmv.utils.constant import render_colors
+
+    rec_root = osp.normpath(args.rec_root)
+    optNet, dataset, dataloader, TmpVs_list, Tmpfs_list = load_run(args)
+    device = TmpVs_list[0].device
+    batch_size = args.batch_size
+    H, W = dataset.H, dataset.W
+    ratio = RATIO
     utils.write_ply(osp.join(rec_root, 'tmp_body.ply'), TmpVs_list[0], Tmpfs_list[0])
     garment_TmpVs, garment_Tmpfs = TmpVs_list[1:], Tmpfs_list[1:]
+    subs = ('colors', 'meshs', 'smpl_meshs', 'def1meshs')
+    if args.registry:
+        paths = [registration.registry_path(rec_root, name) for name in optNet.garment_names]
+        missing = [p for p in paths if not osp.isfile(p)]
+        if missing:
+            raise FileNotFoundError("--registry: %s missing (run register_fl.py first)" % ", ".join(missing))
+        meshes = registration.register_garments(optNet, None, None, None, rec_root)
+        garment_TmpVs, garment_Tmpfs = [v for v, _ in meshes], [f for _, f in meshes]
+        colors_rgb = render_colors(optNet.garment_type, len(optNet.garment_names))
+        subs = subs + ('render',)
     garment_fs_host = [f.cpu() for f in garment_Tmpfs]
-    for sub in ('colors', 'meshs', 'smpl_meshs', 'def1meshs'):
+    for sub in subs:
         os.makedirs(osp.join(rec_root, sub), exist_ok=True)
 
     errors = {name: {} for name in optNet.garment_names}
@@ -116,6 +148,10 @@ def main(argv=None):
             if colors is not None and not args.nI:
                 for fid, color in zip(fids, colors):
                     write_image_bgr(osp.join(rec_root, 'colors/{}_{:06d}.png'.format(name, fid)), color)
+        if args.registry:
+            merged, _ = inference.merged_render(optNet, r['defMeshVs'], garment_Tmpfs, colors_rgb, H, W)
+            for fid, img in zip(fids, merged):
+                write_image_bgr(osp.join(rec_root, 'render/{:06d}.png'.format(fid)), img[:, :, [2, 1, 0]])
         body_vs, body_fs = inference.posed_body(optNet, frame_ids, ratio)
         body_vs, body_fs = body_vs.cpu(), body_fs.cpu()
         for fid, vs in zip(fids, body_vs):

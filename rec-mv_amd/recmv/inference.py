@@ -206,3 +206,25 @@ def posed_body(loop, frame_ids, ratio=None):
     N = frame_ids.numel()
     vs = loop.deformer.defs[1](loop.tmpBodyVs.view(1, -1, 3).expand(N, -1, 3), [poses.detach(), trans.detach()])
     return vs, loop.tmpBodyFs
+
+
+@torch.no_grad()
+def merged_render(loop, defMeshVs_list, Tmpfs_list, colors, H, W):
+    """The merged render of infer_garment (OptimGarmentNetwork.py:3077-3117): every garment's posed mesh of each frame as
+    one mesh, garment g in the flat RGB colour colors[g] (0-255), through the dataset camera and the Phong shader:
+    uint8 [N,H,W,3] RGB and the coverage masks [N,H,W] bool."""
+    device = Tmpfs_list[0].device
+    focals, pps, Rs, Ts, _, _ = loop.dataset.get_camera_parameters(1, device)
+    cameras = RectifiedPerspectiveCameras(focals.detach(), pps.detach(), Rs.detach(), Ts.detach(), image_size=[(W, H)])
+    vs, fs, cs = [], [], []
+    offset = 0
+    for defVs, fc, col in zip(defMeshVs_list, Tmpfs_list, colors):
+        v = torch.as_tensor(defVs).to(device)
+        vs.append(v)
+        fs.append(fc.to(device) + offset)
+        cs.append(torch.tensor(col, dtype=torch.float32, device=device).div(255.).expand(v.shape[1], 3))
+        offset += v.shape[1]
+    verts = torch.cat(vs, 1).contiguous()
+    meshes = shading.Meshes(verts, torch.cat(fs, 0).contiguous(), shading.TexturesVertex(torch.cat(cs, 0)[None].contiguous()))
+    imgs, frags, _ = _render(meshes, cameras, H, W, shading.PointLights())
+    return _to_uint8(imgs[..., :3]), (frags.pix_to_face[..., 0] >= 0).cpu().numpy()

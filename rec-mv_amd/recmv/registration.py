@@ -1,0 +1,92 @@
+"""Garment-template registration: `OptimGarmentNetwork.registration` (engineer/networks/OptimGarmentNetwork.py:2316-2514).
+
+register_garments fits a template mesh to each reconstructed canonical garment by non-rigid ICP and writes
+`root/registry_<garment>.obj`; when every such file exists it loads them instead (:2432-2440).  Per garment:
+  surface_finder (:2321-2387)   12 views (0-330 deg about y, re-centred) through the dataset camera with R = diag(-1,1,-1) and
+                                T = the mean dataset translation, on raster.MeshRasterizer: a target vertex counts when a
+                                face that holds it is hit in some view (the NR-ICP target mask)
+  fl_fit_registry               coarse NR-ICP, 200 epochs (:2411-2418)
+  fl_refine_registry            refine NR-ICP, 100 epochs (:2420-2426)
+Deviations: the templates are inputs (the SMPL-asset cut, `dense_boundary` and the Laplacian alignment to
+the feature curves are not done) and the coarse result keeps its topology (no isotropic remeshing between the passes).
+"""
+import math
+import os.path as osp
+
+import torch
+
+from . import nricp, raster, utils
+from .engineer.optimizer import NRICP_Optimizer_AdamW
+from .model import RectifiedPerspectiveCameras
+
+# engineer/networks/OptimGarmentNetwork.py:2411-2426
+FIT_REGISTRY = dict(epoch=200, dense_pcl=4e4, stiffness_weight=[50, 20, 5, 2, 0.8, 0.5, 0.35, 0.2, 0.1], use_normal=True,
+                    inner_iter=50, mile_stone=[50, 80, 100, 110, 120, 130, 140, 150],
+                    laplacian_weight=[250, 250, 250, 250, 250, 250, 250, 250, 250], threshold=0.3)
+REFINE_REGISTRY = dict(epoch=100, dense_pcl=4e4, stiffness_weight=[2, 0.8, 0.5, 0.35, 0.2, 0.1], use_normal=True,
+                       inner_iter=50, mile_stone=[10, 20, 30, 40, 80], laplacian_weight=[250, 250, 250, 250, 250, 250],
+                       threshold=0.5)
+_VIEW_R = ((-1., 0., 0.), (0., 1., 0.), (0., 0., -1.))
+CULL_BACKFACES = False            # the loop's mask renderer does not cull (loop.py, :2336-2347)
+
+
+def registry_path(root, name):
+    return osp.join(root, 'registry_{}.obj'.format(name))
+
+
+def _rotate_y(degree):
+    """trimesh.transformations.rotation_matrix(radians(degree), [0, 1, 0])[:3, :3]."""
+    a = math.radians(degree)
+    c, s = math.cos(a), math.sin(a)
+    return torch.tensor([[c, 0., s], [0., 1., 0.], [-s, 0., c]], dtype=torch.float32)
+
+
+@torch.no_grad()
+def surface_finder(loop, verts, faces):
+    """bool [V]: the target vertices that some face hit in one of the 12 views holds (:2321-2387)."""
+    device = verts.device
+    focals, pps, _, _, H, W = loop.dataset.get_camera_parameters(1, device)
+    newTs = loop.dataset.trans.detach().mean(0).to(device).view(1, 3)
+    cams = RectifiedPerspectiveCameras(focals.detach(), pps.detach(), torch.tensor([_VIEW_R], device=device), newTs,
+                                       image_size=[(W, H)])
+    rast = raster.MeshRasterizer(cams, (H, W), blur_radius=0., perspective_correct=True, cull_backfaces=CULL_BACKFACES)
+    seen = torch.zeros(verts.shape[0], dtype=torch.bool, device=device)
+    for degree in range(0, 360, 30):
+        v = verts @ _rotate_y(degree).to(device).t()
+        v = v - v.mean(0, keepdim=True)
+        p2f = rast(v[None].contiguous(), faces).pix_to_face[0, ..., 0]
+        hit = p2f[p2f != -1]
+        seen[faces[hit].reshape(-1)] = True
+    return seen
+
+
+def register_garments(loop, templates, target_vs, target_fs, root, fit=None, refine=None, use_kernels=True, log=print):
+    """Registered meshes [(verts [V,3], faces [F,3])] on the targets' device, one per `loop.garment_names` entry.
+    `templates`: one (verts, faces) per garment; `target_vs` / `target_fs`: the canonical garment meshes.  `fit` / `refine`
+    update the NR-ICP settings of the two passes (FIT_REGISTRY, REFINE_REGISTRY)."""
+    names = list(loop.garment_names)
+    device = target_vs[0].device if target_vs else torch.device(loop.device)
+    paths = [registry_path(root, n) for n in names]
+    if all(osp.isfile(p) for p in paths):
+        out = []
+        for p in paths:
+            v, f = utils.read_obj(p)
+            out.append((v.float().to(device), f.long().to(device)))
+        return out
+    if not (len(templates) == len(target_vs) == len(target_fs) == len(names)):
+        raise ValueError("one template and one target mesh per garment (%s)" % ", ".join(names))
+    fit_conf = dict(FIT_REGISTRY, **(fit or {}))
+    refine_conf = dict(REFINE_REGISTRY, **(refine or {}))
+    out = []
+    for name, (tv, tf), gv, gf, path in zip(names, templates, target_vs, target_fs, paths):
+        gv, gf = gv.detach().float().contiguous(), gf.long().contiguous()
+        masks = surface_finder(loop, gv, gf)
+        target = nricp.TriMesh(gv, gf)
+        mesh = nricp.TriMesh(torch.as_tensor(tv).float().to(device), torch.as_tensor(tf).long().to(device))
+        for conf in (fit_conf, refine_conf):
+            opt = NRICP_Optimizer_AdamW(device=device, use_kernels=use_kernels, log=log, **conf)
+            _, mesh = opt(smpl_slice=mesh, cano_meshes=target, save_path=None, garment_name=name, static_pts_type=[],
+                          nricp_masks=masks)
+        utils.write_obj(path, mesh.verts.cpu(), mesh.faces.cpu())
+        out.append((mesh.verts.detach(), mesh.faces))
+    return out

@@ -96,3 +96,25 @@ CURVE_AWARE = {name: 'bottom_curve' for name in ('female_outfit1', 'female_outfi
 # the region masks of a mini-batch a garment list is supervised with (OptimGarmentNetwork.py:1894-1905): one dress-like garment
 # takes the union region, otherwise the upper / lower regions in the order of the garment list
 MASK_KEYS = {True: ['upper_bottom'], False: ['upper', 'bottom']}
+
+# flat RGB colour of each garment (in garment-list order) in the merged registered-mesh render (utils/constant.py:255-263);
+# garment types that are not listed take RENDER_COLORS_DEFAULT
+RENDER_COLORS = {
+    'anran': [[255, 255, 0], [170, 170, 255]],
+    'lingteng_dance': [[170, 170, 127], [72, 152, 170]],
+    'xiaolin': [[193, 210, 240]],
+    'anran_tic': [[255, 99, 128], [193, 210, 240]],
+    'anran_run': [[255, 99, 128], [193, 210, 240]],
+    'leyang_jump': [[193, 210, 240]],
+    'female-3-casual': [[255, 99, 128], [193, 210, 240]],
+}
+RENDER_COLORS_DEFAULT = [[255, 99, 128], [193, 210, 240], [170, 170, 255], [255, 255, 0]]
+
+
+def render_colors(garment_type, n):
+    """n flat RGB colours (0-255) for the garments of `garment_type`: RENDER_COLORS where listed, RENDER_COLORS_DEFAULT
+    (cycled) otherwise."""
+    table = RENDER_COLORS.get(garment_type)
+    if table is None or len(table) < n:
+        table = RENDER_COLORS_DEFAULT
+    return [table[i % len(table)] for i in range(n)]

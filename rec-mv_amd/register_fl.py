@@ -1,0 +1,77 @@
+"""register_fl.py — garment-template registration of a trained run (the `registration` step of the reference's
+`infer_garment`, engineer/networks/OptimGarmentNetwork.py:2316-2514, on recmv.registration).
+
+Loads the run the way infer_fl.py does, extracts the canonical garment meshes at the `fine` pyramid, fits each garment's
+template (`--template <garment>=<obj>`, one per garment) to its mesh by NR-ICP and writes `<rec-root>/registry_<garment>.obj`.
+When every registry file exists they are kept (the reference's cache).  Then `infer_fl.py --registry` poses them.
+
+    python rec-mv_amd/register_fl.py --gpu-ids 0 --rec-root <capture>/<save-folder> --data-type scene \\
+        --template short_sleeve_upper=upper.obj --template short_pants=pants.obj
+"""
+import os.path as osp
+import sys
+
+sys.path.insert(0, osp.dirname(osp.abspath(__file__)))
+
+from infer_fl import build_parser as _infer_parser  # noqa: E402
+
+
+def build_parser():
+    parser = _infer_parser()
+    parser.description = 'garment template registration (NR-ICP)'
+    parser.add_argument('--template', action='append', default=[], metavar='GARMENT=OBJ',
+                        help='template mesh of a garment (repeat for every garment)')
+    parser.add_argument('--fit-epochs', type=int, default=None, help='epochs of the coarse pass (default 200)')
+    parser.add_argument('--refine-epochs', type=int, default=None, help='epochs of the refine pass (default 100)')
+    parser.add_argument('--inner-iter', type=int, default=None, help='inner iterations after the first epoch (default 50)')
+    parser.add_argument('--dense-pcl', type=float, default=None, help='subdivide templates to this many vertices (default 4e4)')
+    parser.add_argument('--torch-path', action='store_true', help='fit with the plain-torch NR-ICP instead of the kernels')
+    return parser
+
+
+def _templates(specs, names):
+    out = {}
+    for spec in specs:
+        if '=' not in spec:
+            raise SystemExit("--template expects GARMENT=OBJ, got %r" % spec)
+        name, path = spec.split('=', 1)
+        out[name] = path
+    unknown = sorted(set(out) - set(names))
+    if unknown:
+        raise SystemExit("--template: unknown garment(s) %s (this run has %s)" % (", ".join(unknown), ", ".join(names)))
+    return out
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    from recmv import registration, utils
+    from infer_fl import load_run
+
+    rec_root = osp.normpath(args.rec_root)
+    optNet, _, _, TmpVs_list, Tmpfs_list = load_run(args)
+    names = list(optNet.garment_names)
+    paths = [registration.registry_path(rec_root, n) for n in names]
+    if all(osp.isfile(p) for p in paths):
+        print('registry meshes exist, loading: ' + ', '.join(paths))
+        return registration.register_garments(optNet, None, None, None, rec_root)
+    given = _templates(args.template, names)
+    missing = [n for n in names if n not in given]
+    if missing:
+        raise SystemExit("--template needed for garment(s) %s" % ", ".join(missing))
+    templates = [utils.read_obj(given[n]) for n in names]
+    over = {}
+    if args.inner_iter is not None:
+        over['inner_iter'] = args.inner_iter
+    if args.dense_pcl is not None:
+        over['dense_pcl'] = args.dense_pcl
+    fit = dict(over, **({'epoch': args.fit_epochs} if args.fit_epochs is not None else {}))
+    refine = dict(over, **({'epoch': args.refine_epochs} if args.refine_epochs is not None else {}))
+    meshes = registration.register_garments(optNet, templates, TmpVs_list[1:], Tmpfs_list[1:], rec_root, fit=fit,
+                                            refine=refine, use_kernels=not args.torch_path)
+    for n, p, (v, f) in zip(names, paths, meshes):
+        print('%s: %d vertices, %d faces -> %s' % (n, v.shape[0], f.shape[0], p))
+    return meshes
+
+
+if __name__ == '__main__':
+    main()
