@@ -636,6 +636,26 @@ int recmv_nricp_energy(const float* A, const float* b, const float* x, const flo
                        float gamma, float stiffness_weight, float laplacian_weight, float threshold, float* scalars,
                        uint8_t* mask, float* dA, float* db, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Laplacian alignment of a garment template to its feature curves (csrc/lap_align.hip; added to ABI v10, no existing
+ * signature changed).  No float atomics: bitwise reproducible.  The neighbour CSR is nricp.neighbours_csr's:
+ * nbr_offsets [V+1] / nbr_idx [nnz] int32, symmetric, degree = row length.
+ * recmv_lap_align_solve: u [V,3] f32 = the solution of (L^T L + diag(cw)) u = L^T (L v) + cwt for the three columns, L the
+ *   uniform Laplacian of pytorch3d's laplacian_packed, v [V,3] f32, cw [V] f64 (weight x constraints on the vertex), cwt
+ *   [V,3] f64 (weight x sum of their targets).  Jacobi-preconditioned CG in f64 from u = v until |r| <= tol |rhs| in every
+ *   column or max_iter iterations; the call synchronises `stream` once every 32 iterations and at the end.
+ *   iterations (host, 1 int32) and residuals (host, 3 doubles: each column's final relative residual) are written on
+ *   return.  V = 0 is a no-op.  Workspace: recmv_lap_align_workspace_bytes(V), 256-byte aligned.
+ * recmv_lap_smooth: out [V,3] f32 = (1/deg_i) sum_{j in N(i)} u_j, accumulated in f64 in CSR order and rounded once; an
+ *   isolated vertex -> 0.  out must not alias u.  V = 0 is a no-op.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t recmv_lap_align_workspace_bytes(int64_t V);
+int recmv_lap_align_solve(const int32_t* nbr_offsets, const int32_t* nbr_idx, int64_t V, int64_t nnz, const float* v,
+                          const double* cw, const double* cwt, double tol, int32_t max_iter, float* u, int32_t* iterations,
+                          double* residuals, void* workspace, int64_t workspace_bytes, void* stream);
+int recmv_lap_smooth(const int32_t* nbr_offsets, const int32_t* nbr_idx, int64_t V, int64_t nnz, const float* u, float* out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

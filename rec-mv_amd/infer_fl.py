@@ -48,9 +48,26 @@ def build_parser():
     return parser
 
 
-def load_run(args):
+def _check_curves(path, optNet):
+    """The checkpoint must hold the feature curves (`inter_free_curve.*`) in the shapes this run builds."""
+    import torch
+    state = torch.load(path, map_location='cpu')['model_state_dict']
+    keys = sorted(k for k in state if k.startswith('inter_free_curve.'))
+    if not keys:
+        raise ValueError("%s holds no feature curves (no inter_free_curve.* keys): the run was trained without the curve "
+                         "branch" % path)
+    mine = optNet.inter_free_curve.state_dict()
+    for k in keys:
+        name = k[len('inter_free_curve.'):]
+        if name in mine and tuple(mine[name].shape) != tuple(state[k].shape):
+            raise ValueError("%s: %s has shape %s, this run builds %s ([curves, samples, ...]: the curve count or sample "
+                             "count differs)" % (path, k, tuple(state[k].shape), tuple(mine[name].shape)))
+
+
+def load_run(args, curves=False):
     """The trained run of `args` and its canonical meshes at the fine pyramid: (optNet, dataset, dataloader, TmpVs_list,
-    Tmpfs_list), index 0 the body, then the garments."""
+    Tmpfs_list), index 0 the body, then the garments.  `curves=True` builds the loop with its feature-curve branch, so that
+    `optNet.inter_free_curve` is restored from the checkpoint (which must hold it)."""
     import torch
     from recmv import utils
     from recmv.dataset import getDatasetAndLoader
@@ -75,11 +92,14 @@ def load_run(args):
     for t in dataset.conds + [dataset.poses, dataset.trans, dataset.shape] + list(dataset.camera_params.values()):
         t.data = t.data.to(device)
     resolutions = RESOLUTIONS['fine']                      # the script's own table, `fine` (infer_fl.py:42-63)
-    optNet, _ = getOptNet(dataset, osp.basename(rec_root), batch_size, None, None, resolutions, device, config)
+    optNet, _ = getOptNet(dataset, osp.basename(rec_root), batch_size, None, None, resolutions, device, config,
+                          **({'curves': True} if curves else {}))
     optNet, dataloader = utils.set_hierarchical_config(config, 'fine', optNet, dataloader, resolutions)
     align = osp.join(rec_root, 'fl_init', 'init_trans_matrix.pth')
     if getattr(optNet, 'curves', False) and osp.isfile(align):
         optNet.align_fl(align)
+    if curves:
+        _check_curves(osp.join(rec_root, 'latest.pth'), optNet)
     print('load model: ' + osp.join(rec_root, 'latest.pth'))
     optNet, dataset, _ = utils.load_model(osp.join(rec_root, 'latest.pth'), optNet, dataset, device)
     optNet.dataset = dataset

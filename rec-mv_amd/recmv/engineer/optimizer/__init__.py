@@ -1,1 +1,2 @@
+from .lap_deform_optimizer import Laplacian_Optimizer  # noqa: F401
 from .nricp_optimizer import Local_Affine, NRICP_Optimizer_AdamW, TriMesh  # noqa: F401

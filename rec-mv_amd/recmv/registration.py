@@ -5,10 +5,13 @@ register_garments fits a template mesh to each reconstructed canonical garment b
   surface_finder (:2321-2387)   12 views (0-330 deg about y, re-centred) through the dataset camera with R = diag(-1,1,-1) and
                                 T = the mean dataset translation, on raster.MeshRasterizer: a target vertex counts when a
                                 face that holds it is hit in some view (the NR-ICP target mask)
+  fl_init_registry              with `curves`: Laplacian alignment of the template's boundary loops to the feature curves,
+                                3 epochs (Laplacian_Optimizer, :2407, :2451-2454)
   fl_fit_registry               coarse NR-ICP, 200 epochs (:2411-2418)
   fl_refine_registry            refine NR-ICP, 100 epochs (:2420-2426)
-Deviations: the templates are inputs (the SMPL-asset cut, `dense_boundary` and the Laplacian alignment to
-the feature curves are not done) and the coarse result keeps its topology (no isotropic remeshing between the passes).
+Deviations: the templates are inputs (the SMPL-asset cut and `dense_boundary` are not done), their
+boundary loops are assigned to the feature lines by centroid (recmv.lap_align.assign_loops), and the coarse result keeps its
+topology (no isotropic remeshing between the passes).
 """
 import math
 import os.path as osp
@@ -16,13 +19,14 @@ import os.path as osp
 import torch
 
 from . import nricp, raster, utils
-from .engineer.optimizer import NRICP_Optimizer_AdamW
+from .engineer.optimizer import Laplacian_Optimizer, NRICP_Optimizer_AdamW
 from .model import RectifiedPerspectiveCameras
 
 # engineer/networks/OptimGarmentNetwork.py:2411-2426
 FIT_REGISTRY = dict(epoch=200, dense_pcl=4e4, stiffness_weight=[50, 20, 5, 2, 0.8, 0.5, 0.35, 0.2, 0.1], use_normal=True,
                     inner_iter=50, mile_stone=[50, 80, 100, 110, 120, 130, 140, 150],
                     laplacian_weight=[250, 250, 250, 250, 250, 250, 250, 250, 250], threshold=0.3)
+INIT_REGISTRY = dict(epoch=3, constrain_weight=1.)            # Laplacian_Optimizer() (:2407)
 REFINE_REGISTRY = dict(epoch=100, dense_pcl=4e4, stiffness_weight=[2, 0.8, 0.5, 0.35, 0.2, 0.1], use_normal=True,
                        inner_iter=50, mile_stone=[10, 20, 30, 40, 80], laplacian_weight=[250, 250, 250, 250, 250, 250],
                        threshold=0.5)
@@ -60,10 +64,13 @@ def surface_finder(loop, verts, faces):
     return seen
 
 
-def register_garments(loop, templates, target_vs, target_fs, root, fit=None, refine=None, use_kernels=True, log=print):
+def register_garments(loop, templates, target_vs, target_fs, root, fit=None, refine=None, use_kernels=True, log=print,
+                      curves=None, align=None):
     """Registered meshes [(verts [V,3], faces [F,3])] on the targets' device, one per `loop.garment_names` entry.
     `templates`: one (verts, faces) per garment; `target_vs` / `target_fs`: the canonical garment meshes.  `fit` / `refine`
-    update the NR-ICP settings of the two passes (FIT_REGISTRY, REFINE_REGISTRY)."""
+    update the NR-ICP settings of the two passes (FIT_REGISTRY, REFINE_REGISTRY).  `curves` ({fl_name: [S,3]}, the run's
+    feature curves): align each template to them by Laplacian deformation before NR-ICP; `align` updates that step's
+    settings (INIT_REGISTRY: epoch, constrain_weight).  Without `curves` the templates go to NR-ICP as they are."""
     names = list(loop.garment_names)
     device = target_vs[0].device if target_vs else torch.device(loop.device)
     paths = [registry_path(root, n) for n in names]
@@ -77,12 +84,18 @@ def register_garments(loop, templates, target_vs, target_fs, root, fit=None, ref
         raise ValueError("one template and one target mesh per garment (%s)" % ", ".join(names))
     fit_conf = dict(FIT_REGISTRY, **(fit or {}))
     refine_conf = dict(REFINE_REGISTRY, **(refine or {}))
+    init_conf = dict(INIT_REGISTRY, **(align or {}))
     out = []
     for name, (tv, tf), gv, gf, path in zip(names, templates, target_vs, target_fs, paths):
         gv, gf = gv.detach().float().contiguous(), gf.long().contiguous()
         masks = surface_finder(loop, gv, gf)
         target = nricp.TriMesh(gv, gf)
         mesh = nricp.TriMesh(torch.as_tensor(tv).float().to(device), torch.as_tensor(tf).long().to(device))
+        if curves is not None:
+            names_fl = list(curves)
+            Laplacian_Optimizer(use_kernels=use_kernels, log=log, **init_conf)(
+                source_fl_meshes=[mesh], target_meshes=[curves[n].to(device) for n in names_fl], source_type=[name],
+                target_fl_type=names_fl, outlayer=True)
         for conf in (fit_conf, refine_conf):
             opt = NRICP_Optimizer_AdamW(device=device, use_kernels=use_kernels, log=log, **conf)
             _, mesh = opt(smpl_slice=mesh, cano_meshes=target, save_path=None, garment_name=name, static_pts_type=[],

@@ -4,6 +4,8 @@
 Loads the run the way infer_fl.py does, extracts the canonical garment meshes at the `fine` pyramid, fits each garment's
 template (`--template <garment>=<obj>`, one per garment) to its mesh by NR-ICP and writes `<rec-root>/registry_<garment>.obj`.
 When every registry file exists they are kept (the reference's cache).  Then `infer_fl.py --registry` poses them.
+`--align-curves` first deforms each template so that its boundary loops land on the run's feature curves (the reference's
+`fl_init_registry`, recmv.engineer.optimizer.Laplacian_Optimizer); the run must have been trained with the curve branch.
 
     python rec-mv_amd/register_fl.py --gpu-ids 0 --rec-root <capture>/<save-folder> --data-type scene \\
         --template short_sleeve_upper=upper.obj --template short_pants=pants.obj
@@ -18,14 +20,18 @@ from infer_fl import build_parser as _infer_parser  # noqa: E402
 
 def build_parser():
     parser = _infer_parser()
-    parser.description = 'garment template registration (NR-ICP)'
+    parser.description = 'garment template registration (Laplacian alignment to the feature curves, NR-ICP)'
     parser.add_argument('--template', action='append', default=[], metavar='GARMENT=OBJ',
                         help='template mesh of a garment (repeat for every garment)')
     parser.add_argument('--fit-epochs', type=int, default=None, help='epochs of the coarse pass (default 200)')
     parser.add_argument('--refine-epochs', type=int, default=None, help='epochs of the refine pass (default 100)')
     parser.add_argument('--inner-iter', type=int, default=None, help='inner iterations after the first epoch (default 50)')
     parser.add_argument('--dense-pcl', type=float, default=None, help='subdivide templates to this many vertices (default 4e4)')
-    parser.add_argument('--torch-path', action='store_true', help='fit with the plain-torch NR-ICP instead of the kernels')
+    parser.add_argument('--torch-path', action='store_true',
+                        help='fit with the plain-torch NR-ICP (and the dense Laplacian solve) instead of the kernels')
+    parser.add_argument('--align-curves', action='store_true',
+                        help="first align each template's boundary loops to the run's feature curves (Laplacian deformation)")
+    parser.add_argument('--align-epochs', type=int, default=None, help='epochs of the curve alignment (default 3)')
     return parser
 
 
@@ -48,7 +54,9 @@ def main(argv=None):
     from infer_fl import load_run
 
     rec_root = osp.normpath(args.rec_root)
-    optNet, _, _, TmpVs_list, Tmpfs_list = load_run(args)
+    if args.align_epochs is not None and not args.align_curves:
+        raise SystemExit("--align-epochs needs --align-curves")
+    optNet, _, _, TmpVs_list, Tmpfs_list = load_run(args, curves=args.align_curves)
     names = list(optNet.garment_names)
     paths = [registration.registry_path(rec_root, n) for n in names]
     if all(osp.isfile(p) for p in paths):
@@ -66,8 +74,13 @@ def main(argv=None):
         over['dense_pcl'] = args.dense_pcl
     fit = dict(over, **({'epoch': args.fit_epochs} if args.fit_epochs is not None else {}))
     refine = dict(over, **({'epoch': args.refine_epochs} if args.refine_epochs is not None else {}))
+    curves, align = None, None
+    if args.align_curves:
+        pts = optNet.inter_free_curve.inference()
+        curves = {n: pts[i] for i, n in enumerate(optNet.fl_names)}
+        align = {'epoch': args.align_epochs} if args.align_epochs is not None else None
     meshes = registration.register_garments(optNet, templates, TmpVs_list[1:], Tmpfs_list[1:], rec_root, fit=fit,
-                                            refine=refine, use_kernels=not args.torch_path)
+                                            refine=refine, use_kernels=not args.torch_path, curves=curves, align=align)
     for n, p, (v, f) in zip(names, paths, meshes):
         print('%s: %d vertices, %d faces -> %s' % (n, v.shape[0], f.shape[0], p))
     return meshes

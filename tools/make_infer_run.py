@@ -1,7 +1,7 @@
 """A small trained run folder for infer_fl.py: a synthetic capture directory (tests/capture_fixture.py, the loop's pinhole),
 two optimiser iterations of the loop on it, and `<capture>/result/{latest.pth, config.conf}` as train.py leaves them.
 
-    python tools/make_infer_run.py OUT_DIR [--size 512]
+    python tools/make_infer_run.py OUT_DIR [--size 512] [--curves]
     python rec-mv_amd/infer_fl.py --gpu-ids 0 --rec-root OUT_DIR/capture/result --data-type scene --frames 2
 """
 import argparse
@@ -19,6 +19,8 @@ def main(argv=None):
     ap.add_argument("out")
     ap.add_argument("--size", type=int, default=512, help="image height = width of the capture")
     ap.add_argument("--iters", type=int, default=2, help="optimiser iterations before the checkpoint (0: the initial surfaces)")
+    ap.add_argument("--curves", action="store_true",
+                    help="train with the feature-curve branch on, so that latest.pth holds inter_free_curve.*")
     args = ap.parse_args(argv)
     import torch
     import capture_fixture as cf
@@ -37,7 +39,8 @@ def main(argv=None):
     for t in ds.conds + [ds.poses, ds.trans, ds.shape] + list(ds.camera_params.values()):
         t.data = t.data.to(dev)
     res = [(9, 13, 7), (17, 25, 13), (33, 49, 25), (65, 97, 49)]
-    optNet, _ = getOptNet(ds, 'result', 3, None, None, res, dev, conf, skin_grid=(17, 33, 17))
+    optNet, _ = getOptNet(ds, 'result', 3, None, None, res, dev, conf, skin_grid=(17, 33, 17),
+                          **({'curves': True} if args.curves else {}))
     optNet, _ = utils.set_hierarchical_config(conf, 'coarse', optNet, None, res)
     optimizer = optNet.rebuild_optimizer()
     for frames in ([0, 2, 3], [5, 6, 8], [1, 4, 7], [9, 10, 11])[:args.iters]:
