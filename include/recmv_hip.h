@@ -656,6 +656,31 @@ int recmv_lap_align_solve(const int32_t* nbr_offsets, const int32_t* nbr_idx, in
 int recmv_lap_smooth(const int32_t* nbr_offsets, const int32_t* nbr_idx, int64_t V, int64_t nnz, const float* u, float* out,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Isotropic remeshing and Loop subdivision of a garment template (csrc/iso_remesh.hip; added to ABI v10, no existing
+ * signature changed).  They replace pymeshlab's meshing_isotropic_explicit_remeshing / meshing_surface_subdivision_loop,
+ * which the reference calls between its two NR-ICP passes.  No float atomics: bitwise reproducible.  The neighbour CSR is
+ * nricp.neighbours_csr's: nbr_offsets [V+1] / nbr_idx [nnz] int32, symmetric, ascending per row.
+ * recmv_closest_point: the exact closest point on the triangle mesh verts [V,3] f32 / faces [F,3] int64 of every query
+ *   point p [P,3] f32 (Ericson's point-triangle test in f32, brute force over the faces): face [P] int64, point [P,3] f32
+ *   and squared distance dist2 [P] f32; ties go to the lowest face id, a face with an index outside [0, V) is skipped.
+ *   P = 0 is a no-op, V = 0 or F = 0 an argument error.  Workspace: recmv_closest_point_workspace_bytes(P), 8-byte aligned.
+ * recmv_iso_relax: out [V,3] f32 = p + (I - n n^T)(c - p) for every vertex with fixed[i] == 0 and at least one neighbour,
+ *   c the mean of its neighbours (f64, CSR order) and n = normals [V,3] (unit); other vertices are copied.  out must not
+ *   alias verts.  V = 0 is a no-op.
+ * recmv_loop_subdivide: Loop's scheme into out [V+E,3] f32.  Rows 0..V-1 (even): a vertex with boundary_nbrs [V,2]
+ *   int64 >= 0 gets 3/4 p + 1/8 (b0 + b1), any other (1 - n beta) p + beta sum of its n neighbours, beta = (5/8 - (3/8 +
+ *   1/4 cos(2 pi / n))^2) / n.  Row V + e (odd): edge_table [E,4] int64 = (a, b, c, d) gives 3/8 (a + b) + 1/8 (c + d), or
+ *   1/2 (a + b) when d = -1 (a boundary edge).  out must not alias verts.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t recmv_closest_point_workspace_bytes(int64_t P);
+int recmv_closest_point(const float* p, int64_t P, const float* verts, int64_t V, const int64_t* faces, int64_t F,
+                        int64_t* face, float* point, float* dist2, void* workspace, int64_t workspace_bytes, void* stream);
+int recmv_iso_relax(const int32_t* nbr_offsets, const int32_t* nbr_idx, int64_t V, int64_t nnz, const float* verts,
+                    const float* normals, const uint8_t* fixed, float* out, void* stream);
+int recmv_loop_subdivide(const int32_t* nbr_offsets, const int32_t* nbr_idx, int64_t V, int64_t nnz, const float* verts,
+                         const int64_t* boundary_nbrs, const int64_t* edge_table, int64_t E, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,17 +8,22 @@ register_garments fits a template mesh to each reconstructed canonical garment b
   fl_init_registry              with `curves`: Laplacian alignment of the template's boundary loops to the feature curves,
                                 3 epochs (Laplacian_Optimizer, :2407, :2451-2454)
   fl_fit_registry               coarse NR-ICP, 200 epochs (:2411-2418)
+  remesh_garment_mesh           with `iso_remesh`: isotropic remeshing, then Loop subdivision of the coarse result (:2477,
+                                engineer/utils/garment_structure.py:440-458; recmv.iso_remesh)
   fl_refine_registry            refine NR-ICP, 100 epochs (:2420-2426)
 Deviations: the templates are inputs (the SMPL-asset cut and `dense_boundary` are not done), their
-boundary loops are assigned to the feature lines by centroid (recmv.lap_align.assign_loops), and the coarse result keeps its
-topology (no isotropic remeshing between the passes).
+boundary loops are assigned to the feature lines by centroid (recmv.lap_align.assign_loops), and the iso-remesh step is opt-in
+(without it the coarse result keeps its topology into the refine pass), refines uniformly (MeshLab's Loop filter refines only
+long edges), is not checked against pymeshlab, keeps boundary and crease vertices fixed and relaxes by the uniform one-ring
+mean.  The reference's remesh_garment_mesh also writes nricp_coarse.obj / remesh.obj scratch files and copies the boundary
+colour labels to the new mesh by nearest neighbour; plain templates carry no labels, so neither is done.
 """
 import math
 import os.path as osp
 
 import torch
 
-from . import nricp, raster, utils
+from . import iso_remesh as IR, nricp, raster, utils
 from .engineer.optimizer import Laplacian_Optimizer, NRICP_Optimizer_AdamW
 from .model import RectifiedPerspectiveCameras
 
@@ -27,6 +32,7 @@ FIT_REGISTRY = dict(epoch=200, dense_pcl=4e4, stiffness_weight=[50, 20, 5, 2, 0.
                     inner_iter=50, mile_stone=[50, 80, 100, 110, 120, 130, 140, 150],
                     laplacian_weight=[250, 250, 250, 250, 250, 250, 250, 250, 250], threshold=0.3)
 INIT_REGISTRY = dict(epoch=3, constrain_weight=1.)            # Laplacian_Optimizer() (:2407)
+ISO_REMESH = dict(iterations=3, target_len_frac=0.01, feature_deg=30., subdiv_levels=1)   # pymeshlab's filter defaults
 REFINE_REGISTRY = dict(epoch=100, dense_pcl=4e4, stiffness_weight=[2, 0.8, 0.5, 0.35, 0.2, 0.1], use_normal=True,
                        inner_iter=50, mile_stone=[10, 20, 30, 40, 80], laplacian_weight=[250, 250, 250, 250, 250, 250],
                        threshold=0.5)
@@ -64,13 +70,28 @@ def surface_finder(loop, verts, faces):
     return seen
 
 
+def _iso_remesh(mesh, conf, use_kernels, log):
+    """`registry_mesh.remesh_garment_mesh(root)` (:2477): isotropic remeshing, then Loop subdivision."""
+    v, f = mesh.verts.detach(), mesh.faces
+    diag = float((v.max(0)[0] - v.min(0)[0]).norm())
+    v, f, _ = IR.isotropic_remesh(v, f, target_len=conf['target_len_frac'] * diag, iterations=conf['iterations'],
+                                  feature_deg=conf['feature_deg'], use_kernels=use_kernels, log=log)
+    v, f = IR.loop_subdivide(v, f, levels=conf['subdiv_levels'], use_kernels=use_kernels)
+    if log is not None:
+        log('iso-remesh: %d -> %d vertices, %d faces after %d Loop level(s)' % (
+            mesh.verts.shape[0], v.shape[0], f.shape[0], conf['subdiv_levels']))
+    return nricp.TriMesh(v.float().contiguous(), f.contiguous())
+
+
 def register_garments(loop, templates, target_vs, target_fs, root, fit=None, refine=None, use_kernels=True, log=print,
-                      curves=None, align=None):
+                      curves=None, align=None, iso_remesh=None):
     """Registered meshes [(verts [V,3], faces [F,3])] on the targets' device, one per `loop.garment_names` entry.
     `templates`: one (verts, faces) per garment; `target_vs` / `target_fs`: the canonical garment meshes.  `fit` / `refine`
     update the NR-ICP settings of the two passes (FIT_REGISTRY, REFINE_REGISTRY).  `curves` ({fl_name: [S,3]}, the run's
     feature curves): align each template to them by Laplacian deformation before NR-ICP; `align` updates that step's
-    settings (INIT_REGISTRY: epoch, constrain_weight).  Without `curves` the templates go to NR-ICP as they are."""
+    settings (INIT_REGISTRY: epoch, constrain_weight).  Without `curves` the templates go to NR-ICP as they are.
+    `iso_remesh` (a dict, possibly empty, updating ISO_REMESH: iterations, target_len_frac, feature_deg, subdiv_levels):
+    iso-remesh the coarse pass's mesh before the refine pass; None leaves it as it is."""
     names = list(loop.garment_names)
     device = target_vs[0].device if target_vs else torch.device(loop.device)
     paths = [registry_path(root, n) for n in names]
@@ -85,6 +106,9 @@ def register_garments(loop, templates, target_vs, target_fs, root, fit=None, ref
     fit_conf = dict(FIT_REGISTRY, **(fit or {}))
     refine_conf = dict(REFINE_REGISTRY, **(refine or {}))
     init_conf = dict(INIT_REGISTRY, **(align or {}))
+    iso_conf = None if iso_remesh is None else dict(ISO_REMESH, **iso_remesh)
+    if iso_conf is not None and set(iso_conf) != set(ISO_REMESH):
+        raise ValueError("iso_remesh: unknown setting(s) %s" % ", ".join(sorted(set(iso_conf) - set(ISO_REMESH))))
     out = []
     for name, (tv, tf), gv, gf, path in zip(names, templates, target_vs, target_fs, paths):
         gv, gf = gv.detach().float().contiguous(), gf.long().contiguous()
@@ -97,6 +121,8 @@ def register_garments(loop, templates, target_vs, target_fs, root, fit=None, ref
                 source_fl_meshes=[mesh], target_meshes=[curves[n].to(device) for n in names_fl], source_type=[name],
                 target_fl_type=names_fl, outlayer=True)
         for conf in (fit_conf, refine_conf):
+            if conf is refine_conf and iso_conf is not None:
+                mesh = _iso_remesh(mesh, iso_conf, use_kernels, log)
             opt = NRICP_Optimizer_AdamW(device=device, use_kernels=use_kernels, log=log, **conf)
             _, mesh = opt(smpl_slice=mesh, cano_meshes=target, save_path=None, garment_name=name, static_pts_type=[],
                           nricp_masks=masks)

@@ -6,6 +6,8 @@ template (`--template <garment>=<obj>`, one per garment) to its mesh by NR-ICP a
 When every registry file exists they are kept (the reference's cache).  Then `infer_fl.py --registry` poses them.
 `--align-curves` first deforms each template so that its boundary loops land on the run's feature curves (the reference's
 `fl_init_registry`, recmv.engineer.optimizer.Laplacian_Optimizer); the run must have been trained with the curve branch.
+`--iso-remesh` iso-remeshes the coarse NR-ICP result before the refine pass (the reference's `remesh_garment_mesh`:
+isotropic remeshing, then Loop subdivision; recmv.iso_remesh).
 
     python rec-mv_amd/register_fl.py --gpu-ids 0 --rec-root <capture>/<save-folder> --data-type scene \\
         --template short_sleeve_upper=upper.obj --template short_pants=pants.obj
@@ -28,10 +30,17 @@ def build_parser():
     parser.add_argument('--inner-iter', type=int, default=None, help='inner iterations after the first epoch (default 50)')
     parser.add_argument('--dense-pcl', type=float, default=None, help='subdivide templates to this many vertices (default 4e4)')
     parser.add_argument('--torch-path', action='store_true',
-                        help='fit with the plain-torch NR-ICP (and the dense Laplacian solve) instead of the kernels')
+                        help='fit with the plain-torch NR-ICP (and the dense Laplacian solve, the torch iso-remesh) instead of the '
+                             'kernels')
     parser.add_argument('--align-curves', action='store_true',
                         help="first align each template's boundary loops to the run's feature curves (Laplacian deformation)")
     parser.add_argument('--align-epochs', type=int, default=None, help='epochs of the curve alignment (default 3)')
+    parser.add_argument('--iso-remesh', action='store_true',
+                        help='iso-remesh the coarse result (isotropic remeshing, then Loop subdivision) before the refine pass')
+    parser.add_argument('--iso-remesh-iters', type=int, default=None, help='isotropic remeshing iterations (default 3)')
+    parser.add_argument('--iso-remesh-len', type=float, default=None,
+                        help='target edge length as a fraction of the bounding-box diagonal (default 0.01)')
+    parser.add_argument('--iso-remesh-subdiv', type=int, default=None, help='Loop subdivision levels (default 1)')
     return parser
 
 
@@ -56,6 +65,9 @@ def main(argv=None):
     rec_root = osp.normpath(args.rec_root)
     if args.align_epochs is not None and not args.align_curves:
         raise SystemExit("--align-epochs needs --align-curves")
+    for flag in ('iters', 'len', 'subdiv'):
+        if getattr(args, 'iso_remesh_' + flag) is not None and not args.iso_remesh:
+            raise SystemExit("--iso-remesh-%s needs --iso-remesh" % flag)
     optNet, _, _, TmpVs_list, Tmpfs_list = load_run(args, curves=args.align_curves)
     names = list(optNet.garment_names)
     paths = [registration.registry_path(rec_root, n) for n in names]
@@ -79,8 +91,13 @@ def main(argv=None):
         pts = optNet.inter_free_curve.inference()
         curves = {n: pts[i] for i, n in enumerate(optNet.fl_names)}
         align = {'epoch': args.align_epochs} if args.align_epochs is not None else None
+    iso = None
+    if args.iso_remesh:
+        iso = {k: v for k, v in (('iterations', args.iso_remesh_iters), ('target_len_frac', args.iso_remesh_len),
+                                 ('subdiv_levels', args.iso_remesh_subdiv)) if v is not None}
     meshes = registration.register_garments(optNet, templates, TmpVs_list[1:], Tmpfs_list[1:], rec_root, fit=fit,
-                                            refine=refine, use_kernels=not args.torch_path, curves=curves, align=align)
+                                            refine=refine, use_kernels=not args.torch_path, curves=curves, align=align,
+                                            iso_remesh=iso)
     for n, p, (v, f) in zip(names, paths, meshes):
         print('%s: %d vertices, %d faces -> %s' % (n, v.shape[0], f.shape[0], p))
     return meshes
