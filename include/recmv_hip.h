@@ -681,6 +681,30 @@ int recmv_iso_relax(const int32_t* nbr_offsets, const int32_t* nbr_idx, int64_t 
 int recmv_loop_subdivide(const int32_t* nbr_offsets, const int32_t* nbr_idx, int64_t V, int64_t nnz, const float* verts,
                          const int64_t* boundary_nbrs, const int64_t* edge_table, int64_t E, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Body-collision repair of posed garment meshes (csrc/mesh_collide.hip; added to ABI v10, no existing signature changed).
+ * Not in the reference: the animation on novel poses (infer_fl_animation.py --fix-collisions) pushes garment vertices
+ * that sank into the posed body back out.  No float atomics: bitwise reproducible.  B frames, one face table faces [F,3]
+ * int64 for all of them (a face with an index outside [0, V) is skipped), body verts [B,V,3] f32.
+ * recmv_point_mesh_nearest: for every point p [B,N,3] f32 the exact nearest triangle of its frame's body mesh (Ericson's
+ *   point-triangle test in f32, brute force over the faces): face [B,N] int64 (-1: none) and squared distance sqdist
+ *   [B,N] f32; ties go to the lowest face id.  B = 0 or N = 0 is a no-op, V = 0 or F = 0 an argument error.  Workspace:
+ *   recmv_point_mesh_nearest_workspace_bytes(B, N), 8-byte aligned.
+ * recmv_collision_push: with face [B,N] of recmv_point_mesh_nearest and the unit vertex normals vnormals [B,V,3]
+ *   (recmv_verts_normals): q = closest point of p on its face with barycentric weights w, n = normalize(sum_i w_i
+ *   vnormal_i), s = (p - q) . n.  s >= eps: p_out = p bit for bit; -max_depth <= s < eps: p_out = p + (eps - s) n and
+ *   moved[b] += 1; s < -max_depth: p_out = p and unresolved[b] += 1 (a vertex that deep is nearer the far side of a limb).
+ *   A vertex without a face or with a vanishing normal is copied.  moved / unresolved: int32 [B], zeroed by the call
+ *   (integer atomics).  p_out may be p.  B = 0 is a no-op; N = 0 only zeroes the counts.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t recmv_point_mesh_nearest_workspace_bytes(int64_t B, int64_t N);
+int recmv_point_mesh_nearest(const float* p, const float* verts, const int64_t* faces, int64_t B, int64_t N, int64_t V,
+                             int64_t F, int64_t* face, float* sqdist, void* workspace, int64_t workspace_bytes,
+                             void* stream);
+int recmv_collision_push(const float* p, const float* verts, const float* vnormals, const int64_t* faces,
+                         const int64_t* face, int64_t B, int64_t N, int64_t V, int64_t F, float eps, float max_depth,
+                         float* p_out, int32_t* moved, int32_t* unresolved, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,7 +88,7 @@ def load_run(args, curves=False):
     dataset, dataloader = getDatasetAndLoader(osp.normpath(osp.join(rec_root, osp.pardir)), condlen, batch_size, False, 0,
                                               config.get_bool('train.opt_pose'), config.get_bool('train.opt_trans'),
                                               config.get_config('train.opt_camera'), garment_type, data_type=args.data_type,
-                                              a_pose=args.a_pose)
+                                              a_pose=args.a_pose, **({'motion': args.motion} if getattr(args, 'motion', None) else {}))
     for t in dataset.conds + [dataset.poses, dataset.trans, dataset.shape] + list(dataset.camera_params.values()):
         t.data = t.data.to(device)
     resolutions = RESOLUTIONS['fine']                      # the script's own table, `fine` (infer_fl.py:42-63)

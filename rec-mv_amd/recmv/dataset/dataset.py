@@ -18,7 +18,9 @@ region masks 'upper' / 'bottom' / 'upper_bottom' / 'body', 'gt_joints2d'})`; the
 (`poses`, `trans`, `conds`, `camera_params`) and are fetched by frame id (`get_grad_parameters`, :425-433).
 
 Images are decoded with Pillow (no OpenCV in this image) into OpenCV's channel order.  The loaders `scene`, `people_snap` and
-`large_pose` are provided; `snug` / `synthe` raise (SNUG motion files and the synthetic-outfit renders are outside this tier)."""
+`large_pose` are provided, and `snug` (a capture animated by a motion file, :1067-1109) when the motion is handed in: the
+reference hard-wires `../snug/assets/CMU/131/131_11_poses.npz`, here the motion is an input like every other outside asset, and
+`data_type='snug'` without one raises."""
 import os
 import os.path as osp
 import random
@@ -31,7 +33,7 @@ from ..engineer.utils.featureline_utils import check_feature_lines, obtain_featu
 from ..engineer.utils.polygons import uniformsample
 from ..utils.constant import ATR_PARSING, FL_INFOS
 
-__all__ = ["SceneDataset", "Synthe_SceneDataset", "Init_Fl_SceneDataset", "People_Snapshot_SceneDataset", "Large_Pose_SceneDataset", "one_euro_smooth", "ClipSampler", "RandomSampler", "getDatasetAndLoader",
+__all__ = ["SceneDataset", "Snug_SceneDataset", "load_motion", "Synthe_SceneDataset", "Init_Fl_SceneDataset", "People_Snapshot_SceneDataset", "Large_Pose_SceneDataset", "one_euro_smooth", "ClipSampler", "RandomSampler", "getDatasetAndLoader",
            "read_image_bgr", "dct_space"]
 
 
@@ -411,6 +413,123 @@ class Synthe_SceneDataset(SceneDataset):
         return idx, out
 
 
+# ------------------------------------------------------------------------------------------------- motion files (snug)
+def _quat_from_rotvec(rv):
+    """Unit quaternions (w, x, y, z) [...,4] of rotation vectors [...,3], float64."""
+    rv = np.asarray(rv, np.float64)
+    angle = np.linalg.norm(rv, axis=-1, keepdims=True)
+    small = angle < 1e-3
+    safe = np.where(small, 1., angle)
+    scale = np.where(small, 0.5 - angle ** 2 / 48. + angle ** 4 / 3840., np.sin(safe / 2.) / safe)     # sin(a/2) / a
+    return np.concatenate([np.cos(angle / 2.), rv * scale], axis=-1)
+
+
+def _quat_mul(a, b):
+    """Hamilton product a (x) b: the rotation b followed by the rotation a."""
+    aw, ax, ay, az = np.moveaxis(a, -1, 0)
+    bw, bx, by, bz = np.moveaxis(b, -1, 0)
+    return np.stack([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                     aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw], axis=-1)
+
+
+def _rotvec_from_quat(q):
+    """Rotation vectors with an angle in [0, pi] (the quaternion with w >= 0), as scipy's `Rotation.as_rotvec`."""
+    q = np.where(q[..., :1] < 0, -q, q)
+    n = np.linalg.norm(q[..., 1:], axis=-1, keepdims=True)
+    angle = 2. * np.arctan2(n, q[..., :1])
+    small = angle < 1e-3
+    scale = np.where(small, 2. + angle ** 2 / 12. + 7. * angle ** 4 / 2880., angle / np.where(small, 1., np.sin(angle / 2.)))
+    return q[..., 1:] * scale
+
+
+def _quat_axis(axis, degrees):
+    half = np.deg2rad(degrees) / 2.
+    q = np.zeros(4)
+    q[0], q[1 + 'xyz'.index(axis)] = np.cos(half), np.sin(half)
+    return q
+
+
+def separate_arms(poses, angle=20, left_arm=17, right_arm=16):
+    """engineer/utils/snug_utils.py:91-103, in place on poses [T, 3J]: the shoulders opened by -/+ `angle` degrees about z
+    (composed in front of the joint's rotation), the hands (joints 22, 23) scaled by 0.1."""
+    p = poses.reshape(poses.shape[0], -1, 3)
+    for joint, sign in ((left_arm, -1.), (right_arm, 1.)):
+        p[:, joint] = _rotvec_from_quat(_quat_mul(_quat_axis('z', sign * angle), _quat_from_rotvec(p[:, joint])))
+    p[:, 23] *= 0.1
+    p[:, 22] *= 0.1
+    return p.reshape(poses.shape[0], -1)
+
+
+def load_motion(path):
+    """engineer/utils/snug_utils.py:67-88 — an AMASS / CMU style .npz (`poses` [T, >= 72], `trans` [T,3], `mocap_framerate`) as
+    (pose [T',72], trans [T',3], trans_vel [T',3]) float32: decimated to 30 fps (every int(rate // 30)-th frame), the arms
+    separated, the root rotation and the translation taken through the axis swap `Rotation.from_euler('zx', [-90, 270])` (about z
+    by -90 degrees, then about the fixed x by 270), the translation centred on the first frame, its velocity by backward
+    differences at 1/30 s (zero in the first frame).  The rotation-vector algebra is restated in numpy (float64 quaternions)
+    and pinned on the reference's own output (tests/golden/motion_out.npz)."""
+    with np.load(path) as motion:
+        step = int(motion['mocap_framerate'] // 30)
+        pose = np.array(motion['poses'][::step, :72])
+        trans = np.array(motion['trans'][::step, :])
+    separate_arms(pose)
+    swap = _quat_mul(_quat_axis('x', 270.), _quat_axis('z', -90.))
+    pose[:, :3] = _rotvec_from_quat(_quat_mul(swap, _quat_from_rotvec(pose[:, :3])))
+    w, x, y, z = swap
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    trans = np.asarray(trans, np.float64) @ R.T
+    trans = trans - trans[0]
+    vel = np.zeros_like(trans)
+    vel[1:] = (trans[1:] - trans[:-1]) / (1 / 30)
+    return pose.astype(np.float32), trans.astype(np.float32), vel.astype(np.float32)
+
+
+class Snug_SceneDataset(SceneDataset):
+    """A capture animated by a motion (:1067-1109): the per-frame tensors, codes and camera are the capture's (`origin_size()`
+    frames), the items are the motion's frames — `(idx, {'poses_y': [72]})`.  The translations come back with z negated and the
+    camera rotation with `diag(1, -1, -1)` behind it, as the reference class does.  `motion`: the path of a motion file
+    (`load_motion`), the tuple `load_motion` returns, or the poses [T,72] themselves (the reference reads
+    ../snug/assets/CMU/131/131_11_poses.npz; here the motion is an input)."""
+
+    def __init__(self, data_root, conds_lens={}, garment_type="", fl_sampling=100, curve_sampling=1, motion=None):
+        if motion is None:
+            raise ValueError("Snug_SceneDataset needs a motion: the path of an AMASS / CMU .npz, or its poses [T,72]")
+        if isinstance(motion, (str, os.PathLike)):
+            motion = load_motion(motion)
+        poses = motion[0] if isinstance(motion, (tuple, list)) else motion
+        poses = poses.detach().cpu().numpy() if torch.is_tensor(poses) else np.asarray(poses)
+        self.anim_poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(poses.shape[0], -1)
+        if self.anim_poses.shape[1] != 72:
+            raise ValueError("Snug_SceneDataset: motion poses must be [T,72] (got %s)" % (poses.shape,))
+        super().__init__(data_root, conds_lens, garment_type, fl_sampling, curve_sampling=curve_sampling)
+
+    def _counts_for_weights(self, idx):          # the capture's frames (len(self) counts the motion's)
+        return idx < min(len(self), self.frame_num) and idx % self.curve_sampling == 0
+
+    def get_grad_parameters(self, idxs, device):
+        conds = [c[idxs].to(device) for c in self.conds]
+        trans = self.trans[idxs].clone()
+        trans[..., -1] = -trans[..., -1]
+        if len(conds) > 1:
+            return (self.poses[idxs].to(device), trans.to(device), *conds)
+        return (self.poses[idxs].to(device), trans.to(device), *conds, None)
+
+    def __getitem__(self, idx):
+        return idx, {'poses_y': torch.from_numpy(self.anim_poses[idx]).float()}
+
+    def __len__(self):
+        return self.anim_poses.shape[0]
+
+    def origin_size(self):
+        return self.frame_num
+
+    def get_camera_parameters(self, N, device):
+        focals, pps, Rs, Ts, H, W = super().get_camera_parameters(N, device)
+        flip = torch.tensor([[[1., 0., 0.], [0., -1., 0.], [0., 0., -1.]]], device=device).repeat(N, 1, 1)
+        return focals, pps, Rs @ flip, Ts, H, W
+
+
 class Init_Fl_SceneDataset(SceneDataset):
     """A capture restricted to the frames `sample_idx` (:894-1000): what `get_init_fl_datasets` hands to the start-up
     registration.  Feature lines come from `mask2fl/` when the capture has it, else `featurelines/`; a frame without an
@@ -575,9 +694,10 @@ class RandomSampler(torch.utils.data.Sampler):
 
 
 def getDatasetAndLoader(root, conds_lens, batch_size, shuffle, num_workers, opt_pose, opt_trans, opt_camera, garment_type,
-                        data_type=None, curve_sampling=1, a_pose=False):
+                        data_type=None, curve_sampling=1, a_pose=False, motion=None):
     """dataset/dataset.py:1159-1183: the capture as a dataset with its learnable tensors switched on, and a DataLoader
-    over a shuffled RandomSampler."""
+    over a shuffled RandomSampler.  `motion` (data_type 'snug' only): the motion that animates the capture, see
+    Snug_SceneDataset."""
     with_a_pose = {'people_snap': People_Snapshot_SceneDataset, 'large_pose': Large_Pose_SceneDataset}
     if data_type == 'scene':
         dataset = SceneDataset(root, conds_lens, garment_type, curve_sampling=curve_sampling)
@@ -585,9 +705,11 @@ def getDatasetAndLoader(root, conds_lens, batch_size, shuffle, num_workers, opt_
         dataset = with_a_pose[data_type](root, conds_lens, garment_type, curve_sampling=curve_sampling, a_pose=a_pose)
     elif data_type == 'synthe':
         dataset = Synthe_SceneDataset(root, conds_lens, garment_type, curve_sampling=curve_sampling)
+    elif data_type == 'snug' and motion is not None:
+        dataset = Snug_SceneDataset(root, conds_lens, garment_type, curve_sampling=curve_sampling, motion=motion)
     elif data_type == 'snug':
         raise NotImplementedError("data type snug: it animates a capture with CMU motion files of the SNUG repository "
-                                  "(../snug/assets, `load_motion`), which are outside this package (recmv/dataset/dataset.py)")
+                                  "(../snug/assets, `load_motion`), which are outside this package: pass motion=<npz path or poses [T,72]>")
     else:
         raise NotImplementedError('data type {} is not implemented'.format(data_type))
     for tensor, learn in ((dataset.poses, opt_pose), (dataset.trans, opt_trans)):

@@ -8,6 +8,9 @@ on, restated on the recmv kernels for every garment of a HotLoop:
   canonical-pose mesh (offset only)  -> `def1imgs` through a camera behind the subject             :3262-3269
   FindSurfacePs + camera rays + OptimizeGarmentSurfaceSinlge + SDF normal + compute_cardinal_rays
   + netRender                        -> `colors` on a white canvas                                 :3271-3300
+`infer_garment_animation` (:2729-2859) is the same chain driven by poses the capture never saw, with the capture's
+conditions averaged over its frames, the posed body rendered beside every garment and, as an addition, the body-collision
+repair of recmv.collide.
 The shading runs on csrc/shade_meshes.hip (recmv.shading), the rest on the kernels the loop uses.  Everything runs
 without autograd except the SDF normal and the cardinal rays, which differentiate the nets as the reference does.
 """
@@ -228,3 +231,93 @@ def merged_render(loop, defMeshVs_list, Tmpfs_list, colors, H, W):
     meshes = shading.Meshes(verts, torch.cat(fs, 0).contiguous(), shading.TexturesVertex(torch.cat(cs, 0)[None].contiguous()))
     imgs, frags, _ = _render(meshes, cameras, H, W, shading.PointLights())
     return _to_uint8(imgs[..., :3]), (frags.pix_to_face[..., 0] >= 0).cpu().numpy()
+
+
+def animation_conditions(loop, N, device):
+    """The conditions an animation is driven with (:2767-2771): every garment's deformer code, the translation and the colour
+    code averaged over the capture's `origin_size()` frames, one (identical) row per animated frame: (d_cond_list over the
+    garments, trans [N,3], rendcond [N,C] or None)."""
+    ds = loop.dataset
+    n_capture = ds.origin_size() if hasattr(ds, 'origin_size') else len(ds)
+    d_cond_list, _, trans, rendcond = loop.get_grad_parameters(torch.arange(n_capture, device=device), device)
+    mean = lambda t: t.detach().mean(0, keepdim=True).expand(N, -1).contiguous()  # noqa: E731
+    return [mean(c) for c in d_cond_list[1:]], mean(trans), (mean(rendcond) if rendcond is not None else None)
+
+
+def animation_meshes(loop, TmpVs_list, Tmpfs_list, root=None):
+    """The meshes an animation poses: the registered templates `root/registry_<garment>.obj` (register_fl.py) when every one
+    of them exists, else the meshes passed in.  (The reference registers on the first call, :2734-2738; here registration
+    stays the separate command it is.)"""
+    import os.path as osp
+    from . import registration
+    if root is not None and all(osp.isfile(registration.registry_path(root, n)) for n in loop.garment_names):
+        meshes = registration.register_garments(loop, None, TmpVs_list, Tmpfs_list, root)
+        return [v for v, _ in meshes], [f for _, f in meshes]
+    return list(TmpVs_list), list(Tmpfs_list)
+
+
+def infer_garment_animation(loop, TmpVs_list, Tmpfs_list, poses_y, H, W, ratio, frame_ids, root=None, notcolor=False,
+                            fix_collisions=False, collision_eps=None, collision_max_depth=None, collision_iters=None,
+                            collision_stats=None, chunk=COLOR_CHUNK):
+    """OptimGarmentNetwork.infer_garment_animation (:2729-2859): the garments driven by the poses `poses_y` [N,72] (or
+    [N,24,3]) with the capture's averaged conditions (`animation_conditions`).  Returns (colors_list, imgs_list,
+    defMeshVs_list) of numpy arrays, one entry per garment: `colors` uint8 [N,H,W,3] (None with `notcolor`), `imgs` uint8
+    [N,H,2W,3] — the Phong render of the posed body template on the left, of the posed garment on the right — and
+    `defMeshVs` float32 [N,V,3].  `root`: the run folder whose registry_<garment>.obj files are posed when present
+    (`animation_meshes`).  The reference runs one frame per call (its averaged conditions have one row); here every row of
+    `poses_y` is a frame.
+    Addition, off by default: `fix_collisions` repairs each garment against the posed body (recmv.collide.resolve with
+    `collision_eps`, `collision_max_depth`, `collision_iters`) before it is rendered and returned; `collision_stats` (a
+    dict) then receives {garment: resolve's stats}.  The colour branch, which renders the implicit surface through the
+    deformer, is not affected by the repair."""
+    from . import collide
+    device = TmpVs_list[0].device
+    N = frame_ids.numel()
+    poses = poses_y.to(device).float().reshape(-1, 24, 3)
+    if poses.shape[0] != N:
+        raise ValueError("infer_garment_animation: %d poses for %d frame ids" % (poses.shape[0], N))
+    TmpVs_list, Tmpfs_list = animation_meshes(loop, TmpVs_list, Tmpfs_list, root)
+    focals, pps, Rs, Ts, _, _ = loop.dataset.get_camera_parameters(1, device)
+    with torch.no_grad():
+        cameras = RectifiedPerspectiveCameras(focals.detach(), pps.detach(), Rs.detach(), Ts.detach(), image_size=[(W, H)])
+        d_cond_list, trans, rendcond = animation_conditions(loop, N, device)
+        loop._ensure_body_template()
+        body_vs = loop.deformer.defs[1](loop.tmpBodyVs.view(1, -1, 3).expand(N, -1, 3), [poses, trans]).contiguous()
+        body = shading.Meshes(body_vs, loop.tmpBodyFs, shading.TexturesVertex(torch.ones_like(loop.tmpBodyVs)[None]))
+        smpl_imgs = _to_uint8(_render(body, cameras, H, W, shading.PointLights())[0][..., :3])
+    colors_list, imgs_list, defMeshVs_list = [], [], []
+    for g_i, (TmpVs, Tmpfs, name) in enumerate(zip(TmpVs_list, Tmpfs_list, loop.garment_names)):
+        TmpVs = TmpVs.detach()
+        d_cond = d_cond_list[g_i]
+        if TmpVs.shape[0] == 0 or Tmpfs.shape[0] == 0:                 # no surface: nothing covers a pixel
+            blank = np.full((N, H, W, 3), 255, np.uint8)
+            colors_list.append(None if notcolor else blank)
+            imgs_list.append(np.concatenate([smpl_imgs, blank], axis=2))
+            defMeshVs_list.append(np.zeros((N, 0, 3), np.float32))
+            continue
+        with torch.no_grad():
+            defTmpVs = loop.deformer(TmpVs[None, :, :].expand(N, -1, 3), [d_cond, [poses, trans]], ratio=ratio,
+                                     offset_type=name).contiguous()
+            if fix_collisions:
+                kw = {k: v for k, v in (('eps', collision_eps), ('max_depth', collision_max_depth),
+                                        ('iters', collision_iters)) if v is not None}
+                defTmpVs, stats = collide.resolve(defTmpVs, body_vs, loop.tmpBodyFs, **kw)
+                if collision_stats is not None:
+                    collision_stats[name] = stats
+            meshes = shading.Meshes(defTmpVs, Tmpfs, shading.TexturesVertex(torch.ones_like(TmpVs)[None]))
+            imgs, frags, _ = _render(meshes, cameras, H, W, shading.PointLights())
+            imgs = np.concatenate([smpl_imgs, _to_uint8(imgs[..., :3])], axis=2)
+            colors = None
+            if not notcolor:
+                batch_inds, row_inds, col_inds, initTmpPs, _ = utils.FindSurfacePs(TmpVs, Tmpfs, frags)
+                rays = cameras.view_rays_pix(col_inds, row_inds)
+        if not notcolor:
+            tcolors = _color_branch(loop, g_i, name, cameras, rays, initTmpPs, batch_inds, [d_cond, [poses, trans]], rendcond,
+                                    ratio, chunk, _Clock(None, device))
+            canvas = torch.ones(N, H, W, 3, device=device) * 255.
+            canvas[batch_inds, row_inds, col_inds, :] = tcolors
+            colors = canvas.cpu().numpy().astype(np.uint8)
+        colors_list.append(colors)
+        imgs_list.append(imgs)
+        defMeshVs_list.append(defTmpVs.cpu().numpy())
+    return colors_list, imgs_list, defMeshVs_list

@@ -766,6 +766,11 @@ class HotLoop:
         from . import inference
         return inference.infer_garments(self, TmpVs_list, Tmpfs_list, H, W, ratio, frame_ids, notcolor, gts, **kwargs)
 
+    def infer_garment_animation(self, TmpVs_list, Tmpfs_list, poses_y, H, W, ratio, frame_ids, root=None, **kwargs):
+        """OptimGarmentNetwork.py:2729-2859 (recmv/inference.py): the garments driven by novel poses, the body beside them."""
+        from . import inference
+        return inference.infer_garment_animation(self, TmpVs_list, Tmpfs_list, poses_y, H, W, ratio, frame_ids, root, **kwargs)
+
     # ------------------------------------------------------------------------------------------ feature curves
     def _ensure_body_template(self):
         """`tmpBodyVs` / `tmpBodyFs`: the SMPL template in canonical space the body z-buffer tests rasterise (6890 vertices in
