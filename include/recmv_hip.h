@@ -705,6 +705,31 @@ int recmv_collision_push(const float* p, const float* verts, const float* vnorma
                          const int64_t* face, int64_t B, int64_t N, int64_t V, int64_t F, float eps, float max_depth,
                          float* p_out, int32_t* moved, int32_t* unresolved, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Feature-curve tubes (csrc/curve_tubes.hip; added to ABI v10, no existing signature changed):
+ * `Intersect_Free_Curve.curve_to_mesh`, engineer/utils/garment_structure.py:176-274.
+ * recmv_curve_tubes: closed curves [L,S,3] f32 with one normal each nx [L,3] f32 -> tubes of num_joints vertices per
+ *   sample: verts [L,S*J,3] f32 (ring-major) and faces [L,2*S*J,3] int64 (indices local to the curve), one launch.
+ *   Tangent d_i = (c_i - c_{i+1}) / (|.| + 1e-6) (the last one closes the curve); ring vertex c_i + radius (n cos t +
+ *   (d x n) sin t + d * (d * n) (1 - cos t)), t = radians(j (360 / J)), the last product ELEMENTWISE as in the
+ *   reference; faces (a_v, b_v, b_v+1), (a_v, b_v+1, a_v+1) for ring a, its successor b.  L, S or J below 1 and a J that
+ *   does not divide 360 are argument errors.
+ * recmv_curve_fit_step: value and gradient of the fit of the curves to polylines (:179-212).  The curves are x = center
+ *   [L,1,3] + dirs [L,S,3] init_scale [L,S,1] relu(scale [L,S,1]) + nx_scale [L,S,1] nx [L,1,3]; pair p fits curve
+ *   target_idx[p] (int32 [P], device) to the polyline targets[p] ([P,M,3] f32):
+ *     loss[p] = w_cham (mean_i min_j |x_i - y_j|^2 + mean_j min_i |x_i - y_j|^2) + w_smooth sum_{k<S-1} (1 - cos(u_k, u_k+1))
+ *   with the unit tangents u of the closed curve.  g_scale, g_nx_scale [L,S,1] f32 receive d(sum_p loss[p]) / d(scale,
+ *   nx_scale) (zero for a curve no pair targets; pairs of one curve add in pair order).  A pair whose index is outside
+ *   [0, L) gets loss 0.  One workgroup per curve with both point sets in LDS: (12 S + 4 M) * 4 bytes must fit 64 KiB - 64.
+ *   No float atomics, fixed summation order: bitwise reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+int recmv_curve_tubes(const float* curves, const float* nx, float radius, int64_t L, int64_t S, int64_t num_joints,
+                      float* verts, int64_t* faces, void* stream);
+int recmv_curve_fit_step(const float* center, const float* dirs, const float* init_scale, const float* nx,
+                         const float* scale, const float* nx_scale, const float* targets, const int32_t* target_idx,
+                         int64_t L, int64_t S, int64_t P, int64_t M, float w_cham, float w_smooth, float* loss,
+                         float* g_scale, float* g_nx_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,8 @@ With `--registry` the garments posed are the registered template meshes `<rec-ro
 register_fl.py writes (`infer_garment`, :2960-3120) instead of the MC meshes; the per-garment files keep their names, and
 every frame also gets the merged render of all garments in flat colours, render/{fid:06d}.png.
 
-Not provided: the template cut from the SMPL assets and `infer_garment_fl`.  `--nV` is accepted and ignored
+Not provided: the template cut from the SMPL assets.  The feature-curve tubes of `infer_garment_fl` are
+infer_fl_curve.py's.  `--nV` is accepted and ignored
 (the reference writes no video either).  The capture is read in this process (no loader workers).
 
     python rec-mv_amd/infer_fl.py --gpu-ids 0 --rec-root <capture>/<save-folder> --data-type scene [--registry]

@@ -1,10 +1,12 @@
 """Feature-curve branch of the iteration (SURVEY.md §8f "next" row 3): explicit curves, their 2-D projection loss and
 z-buffer visibility.
 
-Restates, on torch ops + the HIP mesh rasteriser (no new kernels — the curves hold a few hundred points):
+Restates, on torch ops + the HIP mesh rasteriser (the curves hold a few hundred points; the tube sweep and the fit to boundary
+loops of `curve_to_mesh` run on csrc/curve_tubes.hip):
   * `Intersect_Free_Curve`            engineer/utils/garment_structure.py:36-147 (forward / inference / regularization /
                                       query_canosmpl_verts; the constructor takes the uniformly resampled curves directly —
                                       the reference extracts them from template meshes with `extract_edge`, data path)
+  * `curve_to_mesh` / `fit_curves_to_loops`   :176-274, the tubes infer_fl_curve.py writes and the AdamW fit to boundary loops
   * `fl_proj_loss`                    engineer/core/fl_optimizer.py:72-110, with pytorch3d's `chamfer_distance(
                                       point_reduction='sum')` restated (third party, parity unpinned)
   * `zbuff_check` / `surface_depth_check`   the body of fl_visible_by_body_zbuff, OptimGarmentNetwork.py:1374-1448
@@ -13,7 +15,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib as L
 from .utils.constant import FL_EXTRACT, ZBUF_THRESHOLD  # noqa: E402,F401  (utils/constant.py:65-74, :219-227)
+
+FIT_ITERS = 20000            # AdamW steps of curve_to_mesh's fit to boundary loops (garment_structure.py:188)
 
 
 def _legacy_cross(a, b):
@@ -73,6 +78,121 @@ class Intersect_Free_Curve(nn.Module):
         diff_a = diff_a / (diff_a.norm(dim=-1, keepdim=True) + 1e-6)
         diff_a_loss = 1 - F.cosine_similarity(diff_a[:, :-1, :], diff_a[:, 1:, :], dim=-1)
         return {'center_offset': 0 * center_loss, 'diff_a_loss': diff_a_loss.sum()}
+
+    def curve_to_mesh(self, curve_radius=0.002, num_joints=6, curve_verts=None, curve_idx=None, target_idx=None,
+                      iters=FIT_ITERS, log=None):                                                   # :176-274
+        """One thin tube per curve: a list of `shading.Meshes` (one mesh each: `verts_packed()` [S*J,3], `faces_packed()`
+        [2*S*J,3] int64, indices local to the curve), swept by csrc/curve_tubes.hip.  With `curve_verts` (a list of
+        polylines [M,3]) curve `target_idx[k]` is first fitted to polyline `curve_idx[k]` (`fit_curves_to_loops`; `iters`
+        and `log`, a dict that receives the fit log, are additions).  The reference's `torch.cross(d, n)` carries no
+        `dim`; with exactly three curves its legacy default crosses ALONG the curve axis, which is not reproduced."""
+        from . import shading
+        if curve_verts is not None:
+            if curve_idx is None or target_idx is None or len(curve_idx) != len(target_idx):
+                raise ValueError("curve_to_mesh: curve_verts needs curve_idx and target_idx of one length")
+            info = fit_curves_to_loops(self, [curve_verts[c] for c in curve_idx], list(target_idx), iters=iters)
+            if log is not None:
+                log.update(info)
+        verts, faces = curve_tubes(self.inference(), self.cano_nx[:, 0, :], curve_radius, num_joints)
+        return [shading.Meshes(v[None], f) for v, f in zip(verts, faces)]
+
+
+FIT_W_CHAMFER, FIT_W_SMOOTH = 1000., 0.1                    # garment_structure.py:198, :208
+
+
+def curve_tubes(curves, nx, radius=0.002, num_joints=6):
+    """recmv_curve_tubes: closed curves [L,S,3] and their normals [L,3] -> (verts [L,S*J,3] f32, faces [L,2*S*J,3] int64)."""
+    L.require_cuda(curves, "curves")
+    L.require_cuda(nx, "nx")
+    if curves.dim() != 3 or curves.shape[-1] != 3 or tuple(nx.shape) != (curves.shape[0], 3):
+        raise ValueError("curve_tubes: curves [L,S,3] and nx [L,3], got %s and %s" % (tuple(curves.shape), tuple(nx.shape)))
+    curves, nx = curves.detach().float().contiguous(), nx.detach().float().contiguous()
+    n, S = curves.shape[0], curves.shape[1]
+    J = int(num_joints)
+    verts = L.scratch((n, S * max(J, 0), 3), torch.float32, curves.device)
+    faces = L.scratch((n, 2 * S * max(J, 0), 3), torch.int64, curves.device)
+    with L.device_guard(curves.device):
+        L.check(L.lib().recmv_curve_tubes(L.ptr(curves), L.ptr(nx), float(radius), n, S, J, L.ptr(verts), L.ptr(faces),
+                                          L.stream_ptr(curves.device)), "curve_tubes")
+    return verts, faces
+
+
+def fit_step(curve, targets, target_idx):
+    """recmv_curve_fit_step on the parameters of `curve`: (loss [P] per pair, d sum(loss) / d scale, d sum(loss) / d nx_scale).
+    `targets` [P,M,3] f32 and `target_idx` [P] int32 live on the curve's device."""
+    L.require_cuda(curve.scale, "curve.scale")
+    L.require_cuda(targets, "targets")
+    L.require_cuda(target_idx, "target_idx")
+    if targets.dtype != torch.float32 or target_idx.dtype != torch.int32 or not targets.is_contiguous():
+        raise ValueError("fit_step: targets contiguous float32 [P,M,3] and target_idx int32 [P]")
+    if targets.dim() != 3 or targets.shape[2] != 3 or tuple(target_idx.shape) != (targets.shape[0],):
+        raise ValueError("fit_step: targets [P,M,3] and target_idx [P], got %s and %s"
+                         % (tuple(targets.shape), tuple(target_idx.shape)))
+    n, S = curve.scale.shape[0], curve.scale.shape[1]
+    P, M = targets.shape[0], targets.shape[1]
+    dev = curve.scale.device
+    bufs = [curve.cano_verts_center, curve.cano_v_dirs, curve.init_scale, curve.cano_nx, curve.scale.detach(),
+            curve.nx_scale.detach()]
+    bufs = [b.float().contiguous() for b in bufs]
+    loss = L.scratch((P,), torch.float32, dev)
+    g_scale, g_nx = L.scratch_like(bufs[4]), L.scratch_like(bufs[5])
+    with L.device_guard(dev):
+        L.check(L.lib().recmv_curve_fit_step(*[L.ptr(b) for b in bufs], L.ptr(targets), L.ptr(target_idx), n, S, P, M,
+                                             FIT_W_CHAMFER, FIT_W_SMOOTH, L.ptr(loss), L.ptr(g_scale), L.ptr(g_nx),
+                                             L.stream_ptr(dev)), "curve_fit_step")
+    return loss, g_scale, g_nx
+
+
+def fit_step_torch(curve, targets, target_idx):
+    """The objective of `fit_step` in torch, as the reference writes it (:190-208, pytorch3d's default chamfer_distance
+    restated: mean over the points of each side, both sides added): loss [P] per pair, differentiable with respect to
+    `curve.scale` and `curve.nx_scale`.  Works on any device and dtype; `target_idx` is a sequence of ints."""
+    curves = curve()
+    out = []
+    for gt, t_i in zip(targets, target_idx):
+        x = curves[int(t_i)]
+        d = ((x[:, None, :] - gt[None, :, :].to(x.dtype)) ** 2).sum(-1)
+        cham = d.min(dim=1).values.mean() + d.min(dim=0).values.mean()
+        diff_a = torch.cat([x[:-1, :] - x[1:, :], x[-1:, :] - x[0:1, :]], dim=0)
+        diff_a = diff_a / (diff_a.norm(dim=-1, keepdim=True) + 1e-6)
+        diff_a_loss = (1 - F.cosine_similarity(diff_a[:-1, :], diff_a[1:, :], dim=-1)).sum()
+        out.append(FIT_W_CHAMFER * cham + FIT_W_SMOOTH * diff_a_loss)
+    return torch.stack(out)
+
+
+def fit_curves_to_loops(curve, targets, target_idx, iters=FIT_ITERS, lr=1e-4, step=None):
+    """The fit branch of `curve_to_mesh` (:179-212): curve `target_idx[k]` is pulled onto the polyline `targets[k]` ([M,3],
+    one M for all pairs) by `iters` AdamW steps (torch defaults) over `scale` and `nx_scale`, every step one launch of
+    recmv_curve_fit_step (`step`: another implementation of `fit_step`, e.g. the torch one of tools/curve_fit_timing.py).
+    As the reference does first, `scale[target_idx]` is set to its mean and `init_scale[target_idx]` doubled — in place: the
+    fit changes the module.  Returns {'iters', 'target_idx', 'first_loss', 'last_loss'} (per-pair lists)."""
+    L.require_cuda(curve.scale, "curve.scale")
+    dev = curve.scale.device
+    target_idx = [int(t) for t in target_idx]
+    n = curve.scale.shape[0]
+    if not target_idx or len(targets) != len(target_idx):
+        raise ValueError("fit_curves_to_loops: one polyline per target index, at least one pair")
+    if any(t < 0 or t >= n for t in target_idx):
+        raise ValueError("fit_curves_to_loops: target_idx %s outside the %d curves" % (target_idx, n))
+    tg = torch.stack([torch.as_tensor(t).float().reshape(-1, 3) for t in targets]).to(dev).contiguous()
+    idx = torch.tensor(target_idx, dtype=torch.int32, device=dev)
+    with torch.no_grad():
+        sel = torch.tensor(target_idx, dtype=torch.int64, device=dev)
+        curve.scale[sel] = curve.scale[sel].mean()                                     # :180-181
+        curve.init_scale[sel] *= 2                                                     # :186
+    params = [curve.scale, curve.nx_scale]
+    opt = torch.optim.AdamW(params, lr=lr)
+    step = step or fit_step
+    first = last = None
+    for _ in range(int(iters)):
+        loss, g_scale, g_nx = step(curve, tg, idx)
+        curve.scale.grad, curve.nx_scale.grad = g_scale, g_nx
+        opt.step()
+        if first is None:
+            first = loss
+        last = loss
+    as_list = lambda t: [] if t is None else [float(v) for v in t.detach().cpu()]   # noqa: E731
+    return {'iters': int(iters), 'target_idx': target_idx, 'first_loss': as_list(first), 'last_loss': as_list(last)}
 
 
 def longest_boundary_loop(faces):

@@ -11,6 +11,7 @@ on, restated on the recmv kernels for every garment of a HotLoop:
 `infer_garment_animation` (:2729-2859) is the same chain driven by poses the capture never saw, with the capture's
 conditions averaged over its frames, the posed body rendered beside every garment and, as an addition, the body-collision
 repair of recmv.collide.
+`infer_garment_fl` (:2861-2935) poses the feature curves, swept into thin tubes (csrc/curve_tubes.hip), with the deformer.
 The shading runs on csrc/shade_meshes.hip (recmv.shading), the rest on the kernels the loop uses.  Everything runs
 without autograd except the SDF normal and the cardinal rays, which differentiate the nets as the reference does.
 """
@@ -20,6 +21,7 @@ import numpy as np
 import torch
 
 from . import raster, shading, utils
+from .utils.constant import FL_EXTRACT
 from .model import RectifiedPerspectiveCameras
 
 COLOR_CHUNK = 10000            # rays per root-finder / colour call (:3275)
@@ -321,3 +323,51 @@ def infer_garment_animation(loop, TmpVs_list, Tmpfs_list, poses_y, H, W, ratio, 
         imgs_list.append(imgs)
         defMeshVs_list.append(defTmpVs.cpu().numpy())
     return colors_list, imgs_list, defMeshVs_list
+
+
+class CurveMesh:
+    """What `infer_garment_fl` returns in place of the reference's `trimesh.Trimesh(vertices, faces, process=False)`."""
+
+    def __init__(self, vertices, faces):
+        self.vertices, self.faces = vertices, faces
+
+    def export(self, path):
+        utils.write_obj(path, self.vertices, self.faces)
+
+
+def infer_garment_fl(loop, TmpVs_list, Tmpfs_list, H, W, ratio, frame_ids, notcolor=False, gts=None, root=None,
+                     curve_radius=0.002, num_joints=6):
+    """OptimGarmentNetwork.infer_garment_fl (:2861-2935): the feature curves as thin tubes (`Intersect_Free_Curve.
+    curve_to_mesh`, built on the first call and kept in `loop.fl_curve_meshes`), per garment the tubes of FL_EXTRACT[garment]
+    posed together by the deformer with that garment's code, all merged into one mesh: a `CurveMesh` with `.vertices`
+    [sum S*J,3] float32 and `.faces` int64 on the host and `.export(path)`.  As in the reference only the first frame of
+    `frame_ids` is returned (its `[0]` after the deformer) and the meshes, sizes and `notcolor` / `gts` / `root` play no
+    part.  `curve_radius` / `num_joints` (additions) only count on the call that builds the tubes."""
+    if getattr(loop, 'fl_curve_meshes', None) is None:
+        loop.fl_curve_meshes = loop.inter_free_curve.curve_to_mesh(curve_radius=curve_radius, num_joints=num_joints)
+    fl_map = {name: i for i, name in enumerate(loop.fl_names)}
+    device = loop.fl_curve_meshes[0].verts.device
+    N = frame_ids.numel()
+    verts_list, faces_list = [], []
+    with torch.no_grad():
+        d_cond_list, poses, trans, _ = loop.get_grad_parameters(frame_ids, device)
+        d_cond_list = d_cond_list[1:]                                  # idx 0: the body's code
+        extract = getattr(loop, 'fl_extract', None) or {}
+        for g_i, name in enumerate(loop.garment_names):
+            lines = extract[name] if name in extract else FL_EXTRACT[name]
+            meshes = [loop.fl_curve_meshes[fl_map[fl]] for fl in lines]
+            if not meshes:
+                continue
+            sizes = [m.verts_packed().shape[0] for m in meshes]
+            TmpVs = torch.cat([m.verts_packed() for m in meshes], dim=0)
+            defTmpVs = loop.deformer(TmpVs[None, :, :].expand(N, -1, 3), [d_cond_list[g_i], [poses, trans]], ratio=ratio,
+                                     offset_type=name)[0]
+            verts_list.extend(torch.split(defTmpVs, sizes))
+            faces_list.extend(m.faces_packed() for m in meshes)
+    offset, faces = 0, []
+    for v, f in zip(verts_list, faces_list):
+        faces.append(f + offset)
+        offset += v.shape[0]
+    if not verts_list:
+        return CurveMesh(torch.zeros(0, 3), torch.zeros(0, 3, dtype=torch.int64))
+    return CurveMesh(torch.cat(verts_list).detach().cpu(), torch.cat(faces).detach().cpu())

@@ -771,6 +771,11 @@ class HotLoop:
         from . import inference
         return inference.infer_garment_animation(self, TmpVs_list, Tmpfs_list, poses_y, H, W, ratio, frame_ids, root, **kwargs)
 
+    def infer_garment_fl(self, TmpVs_list, Tmpfs_list, H, W, ratio, frame_ids, notcolor=False, gts=None, root=None, **kwargs):
+        """OptimGarmentNetwork.py:2861-2935 (recmv/inference.py): the feature curves as posed tube meshes, merged into one."""
+        from . import inference
+        return inference.infer_garment_fl(self, TmpVs_list, Tmpfs_list, H, W, ratio, frame_ids, notcolor, gts, root, **kwargs)
+
     # ------------------------------------------------------------------------------------------ feature curves
     def _ensure_body_template(self):
         """`tmpBodyVs` / `tmpBodyFs`: the SMPL template in canonical space the body z-buffer tests rasterise (6890 vertices in

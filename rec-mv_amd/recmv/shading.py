@@ -84,6 +84,15 @@ class Meshes:
     def verts_padded(self):
         return self.verts
 
+    def verts_packed(self):
+        return self.verts.reshape(-1, 3)
+
+    def faces_packed(self):
+        """The face table of a single mesh (a batch shares one table: packing it would need per-mesh offsets)."""
+        if len(self) != 1:
+            raise ValueError("faces_packed: a batch of %d meshes shares one face table" % len(self))
+        return self.faces
+
     def verts_normals_padded(self):
         if self._normals is None:
             if self._adjacency is None:
