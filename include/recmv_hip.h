@@ -286,6 +286,8 @@ int64_t recmv_b3_planes_bytes(int64_t N, int64_t K);
 int recmv_b3_split(const float* B, int64_t ldb, int64_t N, int64_t K, void* planes, int64_t planes_bytes, void* stream);
 int recmv_b3_forget(const float* B);
 int64_t recmv_gemm_tn_workspace_bytes(int64_t M, int64_t N, int64_t K);
+/* C [M,N] = A^T B with A [K,M], B [K,N].  K = 0 (an empty reduction): C is zeroed; A, B, lda, ldb and the workspace are neither read nor
+ * checked (may be NULL). */
 int recmv_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb,
                   float* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
                   void* workspace, int64_t workspace_bytes, void* stream);
@@ -555,6 +557,7 @@ int recmv_rootfind_step(float* p, const float* f, const float* gf, const float* 
  * Backward of one fused layer y = act(x W^T + b) in one call (csrc/linear_bwd.hip) — autograd of nn.Linear +
  * activation in the reference (model/network.py:98-111 etc.).  y, gy [M,N]; x [M,K]; Wt = W^T [K,N];
  * outputs gx [M,K] = (gy . act') W, gW [N,K] = (gy . act')^T x, gb [N] = column sums; any output may be NULL.
+ * M = 0 (an empty batch): gW and gb are zeroed, gx is empty; gy, y, x, Wt and the workspace are neither read nor checked (may be NULL).
  * recmv_colsum: out[c] = sum_r g[r*ld + c], fixed summation order (deterministic).
  * ---------------------------------------------------------------------------------------------- */
 int64_t recmv_colsum_workspace_bytes(int64_t rows, int64_t cols);

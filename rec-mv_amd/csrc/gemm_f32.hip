@@ -1775,14 +1775,15 @@ extern "C" int recmv_gemm_tn(const float* A, int64_t lda, const float* B, int64_
                              void* stream) {
   RECMV_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm_tn: negative size");
   if (M == 0 || N == 0) return RECMV_OK;
-  RECMV_REQUIRE(A && B && C, "gemm_tn: NULL pointer");
-  RECMV_REQUIRE(lda >= M && ldb >= N && ldc >= N, "gemm_tn: leading dimension too small");
   RECMV_REQUIRE(M < (1 << 20) && N < (1 << 20), "gemm_tn: output too large");
   hipStream_t s = (hipStream_t)stream;
-  if (K == 0) {
+  if (K == 0) {                // an empty reduction (its operands carry NULL data pointers): C = 0
+    RECMV_REQUIRE(C && ldc >= N, "gemm_tn: bad output");
     for (int64_t m = 0; m < M; ++m) RECMV_HIP_TRY(hipMemsetAsync(C + m * ldc, 0, N * 4, s));
     return RECMV_OK;
   }
+  RECMV_REQUIRE(A && B && C, "gemm_tn: NULL pointer");
+  RECMV_REQUIRE(lda >= M && ldb >= N && ldc >= N, "gemm_tn: leading dimension too small");
   const int splits = tn_splits(M, N, K);
   const int64_t need = (int64_t)splits * M * N * 4;
   if (!workspace || workspace_bytes < need) {

@@ -176,11 +176,18 @@ extern "C" int64_t recmv_linear_backward_workspace_bytes(int64_t M, int64_t N, i
 
 // y, gy: [M,N] (outputs of the layer and their cotangent); x: [M,K]; Wt: [K,N] = W^T.
 // gx [M,K], gW [N,K], gb [N]: any may be NULL.
+// M = 0: gW and gb are zeroed and the call returns OK; the input pointers, Wt and the workspace are neither read nor checked.
 extern "C" int recmv_linear_backward(const float* gy, int64_t ldgy, const float* y, int64_t ldy, const float* x,
                                      int64_t ldx, const float* Wt, int64_t ldwt, int64_t M, int64_t N, int64_t K,
                                      int act, float act_param, float* gx, int64_t ldgx, float* gW, float* gb,
                                      void* workspace, int64_t workspace_bytes, void* stream) {
   RECMV_REQUIRE(M >= 0 && N >= 0 && K >= 0, "linear_backward: negative size");
+  if (M == 0) {
+    // an empty batch (its tensors carry NULL data pointers): nothing to read, gx is empty, the parameter gradients are zero
+    if (gb && N > 0) RECMV_HIP_TRY(hipMemsetAsync(gb, 0, N * 4, (hipStream_t)stream));
+    if (gW && N > 0 && K > 0) RECMV_HIP_TRY(hipMemsetAsync(gW, 0, N * K * 4, (hipStream_t)stream));
+    return RECMV_OK;
+  }
   RECMV_REQUIRE(gy && (act == RECMV_ACT_NONE || y), "linear_backward: NULL pointer");
   const int64_t need = recmv_linear_backward_workspace_bytes(M, N, K);
   if (!workspace || workspace_bytes < need) {
