@@ -733,6 +733,41 @@ int recmv_curve_fit_step(const float* center, const float* dirs, const float* in
                          int64_t L, int64_t S, int64_t P, int64_t M, float w_cham, float w_smooth, float* loss,
                          float* g_scale, float* g_nx_scale, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Uniform grid over a triangle mesh and the exact closest point through it (csrc/mesh_grid.hip; added to ABI v10, no
+ * existing signature changed).  Not in the reference: the search of the evaluation metrics (recmv/metrics.py, eval_fl.py).
+ * Integer atomics only.  The grid is nx x ny x nz cubic cells of size cell_size with its corner at origin (three floats on
+ * the HOST), chosen by the caller so that it covers the mesh; cell (x, y, z) has index (z ny + y) nx + x; at most 2^26
+ * cells.  A coordinate outside the grid is clamped into its edge cells.  Argument errors (negative sizes, NULL pointers
+ * with non-zero sizes, dims below 1, a cell size that is not positive and finite) are found before any HIP call.
+ * recmv_mesh_grid_count: counts [cells] int32 = the faces of verts [V,3] f32 / faces [F,3] int64 whose axis-aligned box
+ *   overlaps each cell (conservative; a face with an index outside [0, V) is binned nowhere), total [1] int64 (device,
+ *   8-byte aligned) = their sum, the number of (cell, face) entries.  Both are zeroed by the call.
+ * recmv_mesh_grid_fill: offsets [cells + 1] int32 = the exclusive scan of counts (offsets[cells] the total, which must be
+ *   below 2^31), entries [capacity] int32 = the face ids of cell c at offsets[c] .. offsets[c + 1] (in an order that
+ *   depends on scheduling; a slot at or beyond capacity is not written), tris [F,12] f32 (16-byte aligned) = every face as
+ *   (a, b - a, c - a, 0, 0, 0).  Same grid arguments as the count call.  Workspace:
+ *   recmv_mesh_grid_workspace_bytes(cells), 4-byte aligned.
+ * recmv_closest_point_grid: recmv_closest_point's outputs for the query points p [P,3] f32 — face [P] int64 (-1: none),
+ *   point [P,3] f32, dist2 [P] f32, ties to the lowest face id, bit for bit what recmv_closest_point gives on the mesh
+ *   the grid was built from — by visiting the Chebyshev rings of cells around the query's cell until everything outside
+ *   them is farther than the best found.  order: NULL, or a permutation [P] int64 of the queries (thread t handles
+ *   query order[t]: sorted by cell, neighbouring lanes read the same cells); lanes: 1, 8 or 64 lanes of a wave per query.
+ *   P = 0 is a no-op, F = 0 an argument error.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t recmv_mesh_grid_workspace_bytes(int64_t cells);
+int recmv_mesh_grid_count(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* origin,
+                          float cell_size, int64_t nx, int64_t ny, int64_t nz, int32_t* counts, int64_t* total,
+                          void* stream);
+int recmv_mesh_grid_fill(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* origin,
+                         float cell_size, int64_t nx, int64_t ny, int64_t nz, const int32_t* counts, int32_t* offsets,
+                         int32_t* entries, int64_t capacity, float* tris, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+int recmv_closest_point_grid(const float* p, int64_t P, const int64_t* order, const float* tris, int64_t F,
+                             const int32_t* offsets, const int32_t* entries, int64_t n_entries, const float* origin,
+                             float cell_size, int64_t nx, int64_t ny, int64_t nz, int32_t lanes, int64_t* face,
+                             float* point, float* dist2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

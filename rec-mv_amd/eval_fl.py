@@ -1,0 +1,105 @@
+"""eval_fl.py — surface metrics between reconstructed garments and ground-truth (or reference-run) meshes: an addition, the
+reference has no evaluation command (its tools/comparison_results.py stops after loading a mesh).
+
+`--pred` and `--gt` are two `.obj` files or two directories of them; directories are paired by file stem, files without a
+partner are listed in the output and skipped, and no pair at all is an error.  The two meshes of a pair are taken to be in one
+frame: no alignment is attempted (`--scale` multiplies the prediction, for captures in another unit).  Per pair
+recmv.metrics.surface_distance (accuracy, completeness, Chamfer, normal consistency, precision / recall / F-score at
+`--thresholds`, definitions in INTEGRATION.md §5), then the means over the pairs.  When the prediction directory is a sequence
+of one topology the output also holds infer_fl_animation.py's temporal smoothness figure of it.
+
+    python rec-mv_amd/eval_fl.py --gpu-ids 0 --pred <obj|dir> --gt <obj|dir> [--samples N] [--seed S] [--thresholds t ...]
+        [--scale s] [--method auto|grid|brute] [--out metrics.json]
+"""
+import argparse
+import json
+import os
+import os.path as osp
+import sys
+
+sys.path.insert(0, osp.dirname(osp.abspath(__file__)))
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description='surface metrics between predicted and ground-truth meshes')
+    parser.add_argument('--gpu-ids', nargs='+', type=int, default=[0], metavar='IDs', help='gpu ids (the first is used)')
+    parser.add_argument('--pred', required=True, help='predicted mesh (.obj) or a directory of them')
+    parser.add_argument('--gt', required=True, help='ground-truth mesh (.obj) or a directory of them')
+    parser.add_argument('--samples', default=100000, type=int, help='surface samples per direction')
+    parser.add_argument('--seed', default=0, type=int)
+    parser.add_argument('--thresholds', nargs='+', type=float, default=None,
+                        help='distances for precision / recall / F-score, in the meshes\' length unit')
+    parser.add_argument('--scale', default=1.0, type=float, help='factor on the prediction (captures in another unit)')
+    parser.add_argument('--method', default='auto', choices=['auto', 'grid', 'brute'])
+    parser.add_argument('--out', default=None, help='metrics JSON (default: printed only)')
+    return parser
+
+
+def _objs(path):
+    if osp.isdir(path):
+        return {osp.splitext(n)[0]: osp.join(path, n) for n in sorted(os.listdir(path)) if n.lower().endswith('.obj')}
+    return None
+
+
+def pair_files(pred, gt):
+    """(pairs [(stem, pred file, gt file)] sorted by stem, unmatched prediction files, unmatched ground-truth files).  Two
+    files are one pair whatever their names; two directories are paired by stem.  ValueError when nothing pairs."""
+    p, g = _objs(pred), _objs(gt)
+    if (p is None) != (g is None):
+        raise ValueError("--pred and --gt must both be files or both be directories")
+    if p is None:
+        for f in (pred, gt):
+            if not osp.isfile(f):
+                raise ValueError("no such mesh: %s" % f)
+        return [(osp.splitext(osp.basename(pred))[0], pred, gt)], [], []
+    pairs = [(s, p[s], g[s]) for s in sorted(p) if s in g]
+    if not pairs:
+        raise ValueError("no .obj stem is in both %s (%d meshes) and %s (%d meshes)" % (pred, len(p), gt, len(g)))
+    return pairs, [p[s] for s in sorted(p) if s not in g], [g[s] for s in sorted(g) if s not in p]
+
+
+def main(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    try:
+        pairs, only_pred, only_gt = pair_files(args.pred, args.gt)
+    except ValueError as e:
+        parser.error(str(e))
+    import torch
+    from infer_fl_animation import temporal_smoothness
+    from recmv import metrics
+    from recmv.utils import read_obj
+
+    device = torch.device('cuda:%d' % args.gpu_ids[0])
+    thresholds = tuple(args.thresholds) if args.thresholds else metrics.DEFAULT_THRESHOLDS
+    per_pair, sequence = {}, []
+    for stem, pf, gf in pairs:
+        pv, pfaces = read_obj(pf)
+        gv, gfaces = read_obj(gf)
+        pv = pv * args.scale
+        sequence.append((pv, pfaces))
+        per_pair[stem] = metrics.surface_distance(pv.to(device), pfaces.to(device), gv.to(device), gfaces.to(device),
+                                                  samples=args.samples, seed=args.seed, thresholds=thresholds,
+                                                  method=args.method)
+        print('%s: chamfer_l1 %.6g, accuracy %.6g, completeness %.6g, normal consistency %.4f' % (
+            stem, per_pair[stem]['chamfer_l1'], per_pair[stem]['accuracy'], per_pair[stem]['completeness'],
+            per_pair[stem]['normal_consistency']))
+    keys = list(next(iter(per_pair.values())))
+    mean = {k: sum(m[k] for m in per_pair.values()) / len(per_pair) for k in keys}
+    res = {'pairs': per_pair, 'mean': mean, 'samples': args.samples, 'seed': args.seed, 'method': args.method,
+           'thresholds': list(thresholds), 'scale': args.scale, 'unmatched_pred': only_pred, 'unmatched_gt': only_gt}
+    v0, f0 = sequence[0]
+    if osp.isdir(args.pred) and all(v.shape == v0.shape and torch.equal(f, f0) for v, f in sequence):
+        res['temporal_smoothness'] = temporal_smoothness(torch.stack([v for v, _ in sequence]).numpy())
+    print('mean over %d pairs: %s' % (len(per_pair), json.dumps(mean)))
+    if only_pred or only_gt:
+        print('skipped, without a partner: %s' % ', '.join(only_pred + only_gt))
+    if args.out:
+        os.makedirs(osp.dirname(osp.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as fh:
+            json.dump(res, fh, indent=1, sort_keys=True)
+    return res
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,234 @@
+"""Surface metrics between a reconstructed and a ground-truth mesh (csrc/mesh_grid.hip) — an ADDITION to the reference,
+whose tools/comparison_results.py stops after loading a mesh.
+
+  MeshGrid          a uniform grid over a triangle mesh (recmv_mesh_grid_count / recmv_mesh_grid_fill); `.closest_point(p)`
+                    is iso_remesh.closest_point's exact search through it (recmv_closest_point_grid): the same bits
+  sample_surface    loop.sample_fan_mesh's area-weighted surface samples, with the picked faces
+  surface_distance  accuracy / completeness / Chamfer / normal consistency / precision, recall and F-score at thresholds
+                    between two meshes taken to be in one frame (no alignment), from surface samples in both directions
+
+Definitions (d the unsquared distance sqrt(dist2) of a sample to the other SURFACE, in the meshes' length unit; every
+reduction in float64 on the device, one read-back):
+  accuracy            mean d over the samples of the prediction (accuracy_rms, accuracy_max: its rms and maximum)
+  completeness        the same over the samples of the ground truth (completeness_rms, completeness_max)
+  chamfer_l1          (accuracy + completeness) / 2
+  chamfer_l2          mean d^2 over the prediction's samples + mean d^2 over the ground truth's
+  normal_consistency  per direction (…_pred_to_gt, …_gt_to_pred) the mean of |n_source_face . n_nearest_face| with unit face
+                      normals; `normal_consistency` is the average of the two
+  precision_<t>       the share of the prediction's samples with d <= t; recall_<t> the same for the ground truth's;
+                      fscore_<t> their harmonic mean (0 when both are 0)
+"""
+import ctypes as C
+import math
+
+import torch
+
+from . import _lib as L
+
+FACES_PER_CELL = 3.0           # the cell size aims at this many faces per occupied cell (h about 1.5 mean edges on a closed surface)
+MAX_CELLS = 1 << 22            # offsets table of 16 MiB
+MAX_ENTRIES = 1 << 28          # (cell, face) entries of 1 GiB: beyond that the grid is coarsened
+QUERY_LANES = 1                # lanes of a wave per query and whether the queries are sorted by cell: to be settled by
+QUERY_SORTED = True            # tools/mesh_distance_timing.py (profiles/mesh_distance_timing.json); not measured yet, a guess
+# method='auto': the grid (build + query) from this many point-triangle tests P * F on, brute force below.  The crossover
+# comes from profiles/mesh_distance_timing.json (tools/mesh_distance_timing.py; DESIGN.md §8 "Evaluation"); that file has not
+# been recorded yet, so the value is unreachable and 'auto' chooses the brute force at every size.
+AUTO_GRID_MIN_TESTS = 1 << 62
+DEFAULT_THRESHOLDS = (0.005, 0.01, 0.02)
+
+
+def choose_grid(lo, hi, n_faces, faces_per_cell=FACES_PER_CELL, max_cells=MAX_CELLS):
+    """Grid over the box lo .. hi (three floats each) for a mesh of `n_faces`: (cell size, (nx, ny, nz)).  Cubic cells; the
+    size aims at `faces_per_cell` faces per cell a surface of the box's area passes through, h^2 = area * faces_per_cell /
+    n_faces; a zero-extent axis gets one cell; the cells are enlarged until there are at most `max_cells`."""
+    ext = [max(float(b) - float(a), 0.) for a, b in zip(lo, hi)]
+    if not all(math.isfinite(e) for e in ext):
+        raise ValueError("choose_grid: the bounding box is not finite")
+    area = 2. * (ext[0] * ext[1] + ext[1] * ext[2] + ext[2] * ext[0])
+    n = max(int(n_faces), 1)
+    if area > 0:
+        h = math.sqrt(area * faces_per_cell / n)
+    elif max(ext) > 0:
+        h = max(ext) * faces_per_cell / n
+    else:
+        h = 1.
+    h = max(h, max(ext) * 2. ** -20, 1e-30)
+    while True:
+        h = float(torch.tensor(h, dtype=torch.float32))                     # the kernels get a float32
+        dims = tuple(int(e / h) + 1 if e > 0 else 1 for e in ext)
+        cells = dims[0] * dims[1] * dims[2]
+        if cells <= max_cells:
+            return h, dims
+        h *= 1.02 * (cells / max_cells) ** (1. / max(sum(d > 1 for d in dims), 1))
+
+
+def _check_mesh(verts, faces):
+    L.require_cuda(verts, "verts")
+    L.require_cuda(faces, "faces")
+    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError("verts must be float32 of shape [V,3]")
+    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("faces must be int64 of shape [F,3]")
+    if faces.shape[0] == 0 or verts.shape[0] == 0:
+        raise ValueError("the surface is empty")
+
+
+class MeshGrid:
+    """A uniform grid over the mesh verts [V,3] f32 / faces [F,3] int64 (CUDA).  The bounding box and the number of
+    (cell, face) entries are read back: two host synchronisations per build.  `dims` (and optionally `cell_size`) force a
+    grid instead of choose_grid's (tests, tools)."""
+
+    def __init__(self, verts, faces, dims=None, cell_size=None, faces_per_cell=FACES_PER_CELL):
+        _check_mesh(verts, faces)
+        self.verts, self.faces = verts.contiguous(), faces.contiguous()
+        dev = verts.device
+        box = torch.stack([self.verts.amin(0), self.verts.amax(0)]).cpu()
+        if not bool(torch.isfinite(box).all()):
+            raise ValueError("MeshGrid: the vertices are not finite")
+        lo, hi = box[0].tolist(), box[1].tolist()
+        forced = dims is not None
+        if forced:
+            dims = tuple(int(d) for d in dims)
+            if cell_size is None:
+                cell_size = max(max((b - a) / d for a, b, d in zip(lo, hi, dims)) * (1 + 1e-6), 1e-30)
+            h = float(torch.tensor(float(cell_size), dtype=torch.float32))
+        else:
+            h, dims = choose_grid(lo, hi, faces.shape[0], faces_per_cell)
+        lib = L.lib()
+        V, F = self.verts.shape[0], self.faces.shape[0]
+        self.origin = (C.c_float * 3)(*lo)
+        while True:
+            cells = dims[0] * dims[1] * dims[2]
+            counts = L.scratch((cells,), torch.int32, dev)
+            total = L.scratch((1,), torch.int64, dev)
+            with L.device_guard(dev):
+                L.check(lib.recmv_mesh_grid_count(L.ptr(self.verts), V, L.ptr(self.faces), F, self.origin, h, *dims,
+                                                  L.ptr(counts), L.ptr(total), L.stream_ptr(dev)), "mesh_grid_count")
+            n = int(total.item())
+            if n <= MAX_ENTRIES:
+                break
+            if forced:
+                raise ValueError("MeshGrid: %d (cell, face) entries in the forced grid, at most %d" % (n, MAX_ENTRIES))
+            h, dims = float(torch.tensor(2 * h, dtype=torch.float32)), tuple((d + 1) // 2 for d in dims)
+        self.cell_size, self.dims, self.n_entries = h, dims, n
+        self.offsets = L.scratch((cells + 1,), torch.int32, dev)
+        self.entries = L.scratch((max(n, 1),), torch.int32, dev)
+        self.tris = L.scratch((F, 12), torch.float32, dev)
+        nbytes = int(lib.recmv_mesh_grid_workspace_bytes(cells))
+        ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
+        with L.device_guard(dev):
+            L.check(lib.recmv_mesh_grid_fill(L.ptr(self.verts), V, L.ptr(self.faces), F, self.origin, h, *dims,
+                                             L.ptr(counts), L.ptr(self.offsets), L.ptr(self.entries), n, L.ptr(self.tris),
+                                             L.ptr(ws), nbytes, L.stream_ptr(dev)), "mesh_grid_fill")
+        self.counts = counts
+
+    def cell_of(self, p):
+        """Linear cell index [P] int64 of the points p (clamped into the grid), for sorting the queries."""
+        o = torch.tensor(list(self.origin), dtype=torch.float32, device=p.device)
+        n = torch.tensor(self.dims, dtype=torch.float32, device=p.device)
+        c = torch.minimum(((p - o) / self.cell_size).floor().nan_to_num(0.).clamp_(min=0.), n - 1).long()
+        return (c[:, 2] * self.dims[1] + c[:, 1]) * self.dims[0] + c[:, 0]
+
+    def closest_point(self, p, lanes=None, sort=None):
+        """iso_remesh.closest_point(p, verts, faces) through the grid: (face [P] int64, point [P,3] f32, squared distance
+        [P] f32), ties to the lowest face id, the same bits.  `lanes` (1, 8 or 64 lanes per query) and `sort` (queries
+        ordered by cell) choose the launch shape; they do not change the result."""
+        L.require_cuda(p, "p")
+        if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
+            raise ValueError("p must be float32 of shape [P,3]")
+        if p.device != self.verts.device:
+            raise ValueError("p and the mesh must be on one device")
+        p = p.contiguous()
+        P, dev = p.shape[0], p.device
+        face = L.scratch((P,), torch.int64, dev)
+        point = L.scratch((P, 3), torch.float32, dev)
+        dist2 = L.scratch((P,), torch.float32, dev)
+        if P == 0:
+            return face, point, dist2
+        lanes = QUERY_LANES if lanes is None else int(lanes)
+        order = torch.sort(self.cell_of(p))[1].contiguous() if (QUERY_SORTED if sort is None else sort) else None
+        with L.device_guard(dev):
+            L.check(L.lib().recmv_closest_point_grid(L.ptr(p), P, L.ptr(order), L.ptr(self.tris), self.faces.shape[0],
+                                                     L.ptr(self.offsets), L.ptr(self.entries), self.n_entries, self.origin,
+                                                     self.cell_size, *self.dims, lanes, L.ptr(face), L.ptr(point),
+                                                     L.ptr(dist2), L.stream_ptr(dev)), "closest_point_grid")
+        return face, point, dist2
+
+
+def sample_surface(verts, faces, count, generator=None):
+    """loop.sample_fan_mesh's samples (faces picked in proportion to their area by the inverse CDF, a uniform point of each
+    from two uniforms reflected into the lower-left half of the unit square) with the picked faces: (points [count,3],
+    face [count] int64)."""
+    tri = verts[faces]                                                                     # [F,3,3]
+    e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+    area = 0.5 * torch.linalg.cross(e1, e2, dim=-1).norm(dim=-1)
+    cum = torch.cumsum(area, 0)
+    u = torch.rand(count, device=verts.device, generator=generator) * cum[-1]
+    f = torch.searchsorted(cum, u).clamp_(max=faces.shape[0] - 1)
+    r = torch.rand(count, 2, device=verts.device, generator=generator)
+    r = torch.where((r.sum(1, keepdim=True) > 1.0), r - 1.0, r).abs()
+    return tri[f, 0] + e1[f] * r[:, 0:1] + e2[f] * r[:, 1:2], f
+
+
+def face_normals(verts, faces):
+    """Unit face normals [F,3] f32 (zero for a face without area)."""
+    tri = verts[faces]
+    n = torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=-1)
+    return torch.nan_to_num(n / n.norm(dim=-1, keepdim=True), nan=0., posinf=0., neginf=0.)
+
+
+def use_grid(method, n_points, n_faces):
+    if method not in ('auto', 'grid', 'brute'):
+        raise ValueError("method must be 'auto', 'grid' or 'brute' (got %r)" % (method,))
+    return method == 'grid' or (method == 'auto' and n_points * n_faces >= AUTO_GRID_MIN_TESTS)
+
+
+def _nearest(p, verts, faces, method):
+    if use_grid(method, p.shape[0], faces.shape[0]):
+        return MeshGrid(verts, faces).closest_point(p)
+    from .iso_remesh import closest_point
+    return closest_point(p, verts, faces)
+
+
+def _direction(p, src_face, src_v, src_f, dst_v, dst_f, thresholds, method):
+    """Device scalars (float64) of one direction: mean d, mean d^2, max d, normal consistency, share of d <= t per t."""
+    face, _, dist2 = _nearest(p, dst_v, dst_f, method)
+    d2 = dist2.double()
+    d = d2.sqrt()
+    dots = (face_normals(src_v, src_f)[src_face] * face_normals(dst_v, dst_f)[face.clamp(min=0)]).double().sum(-1).abs()
+    vals = [d.mean(), d2.mean(), d.max(), dots.mean()] + [(d <= float(t)).double().mean() for t in thresholds]
+    return torch.stack(vals), face
+
+
+@torch.no_grad()
+def surface_distance(pred_v, pred_f, gt_v, gt_f, samples=100000, seed=0, thresholds=DEFAULT_THRESHOLDS, method='auto',
+                     return_samples=False):
+    """The metrics of the module docstring between the prediction (pred_v [V,3] f32, pred_f [F,3] int64) and the ground truth
+    (CUDA tensors on one device): a dict of python floats.  `samples` surface samples per direction from a generator seeded
+    with `seed` (the prediction's first).  `return_samples`: also {'pred': (points, source face, nearest face of the ground
+    truth), 'gt': (…)}."""
+    _check_mesh(pred_v, pred_f)
+    _check_mesh(gt_v, gt_f)
+    use_grid(method, 0, 0)
+    if samples < 1:
+        raise ValueError("surface_distance: at least one sample")
+    pred_v, pred_f, gt_v, gt_f = (t.contiguous() for t in (pred_v, pred_f, gt_v, gt_f))
+    gen = torch.Generator(device=pred_v.device).manual_seed(int(seed))
+    thresholds = tuple(float(t) for t in thresholds)
+    pp, pf = sample_surface(pred_v, pred_f, samples, gen)
+    gp, gf = sample_surface(gt_v, gt_f, samples, gen)
+    a, a_near = _direction(pp, pf, pred_v, pred_f, gt_v, gt_f, thresholds, method)
+    c, c_near = _direction(gp, gf, gt_v, gt_f, pred_v, pred_f, thresholds, method)
+    a, c = torch.stack([a, c]).cpu().tolist()                                     # the one read-back
+    out = {'accuracy': a[0], 'accuracy_rms': math.sqrt(a[1]), 'accuracy_max': a[2],
+           'completeness': c[0], 'completeness_rms': math.sqrt(c[1]), 'completeness_max': c[2],
+           'chamfer_l1': 0.5 * (a[0] + c[0]), 'chamfer_l2': a[1] + c[1],
+           'normal_consistency_pred_to_gt': a[3], 'normal_consistency_gt_to_pred': c[3],
+           'normal_consistency': 0.5 * (a[3] + c[3])}
+    for k, t in enumerate(thresholds):
+        pr, rc = a[4 + k], c[4 + k]
+        out['precision_%g' % t], out['recall_%g' % t] = pr, rc
+        out['fscore_%g' % t] = 2. * pr * rc / (pr + rc) if pr + rc > 0 else 0.
+    if return_samples:
+        return out, {'pred': (pp, pf, a_near), 'gt': (gp, gf, c_near)}
+    return out

@@ -1,0 +1,190 @@
+"""Mesh evaluation metrics without a GPU: the float64 restatement (tests/mesh_metrics_reference.py) on hand-computed cases,
+the argument checks of the three new C entry points, the grid the wrapper chooses, eval_fl.py's pairing of files, and the
+refusal of CPU tensors."""
+import ctypes as C
+import math
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+HERE = Path(__file__).resolve().parent
+REPO = HERE.parent
+sys.path[:0] = [str(HERE), str(REPO / "rec-mv_amd")]
+import collide_reference as CR  # noqa: E402
+import mesh_metrics_reference as MR  # noqa: E402
+
+
+def test_reference_on_two_parallel_unit_squares():
+    """Two unit squares over each other, h apart: every sample is h from the other surface, so accuracy = completeness =
+    chamfer_l1 = h, chamfer_l2 = 2 h^2, the normals agree, and F = 1 for a threshold above h, 0 below."""
+    h = 0.125
+    av, af = MR.square(0., n=3)
+    bv, bf = MR.square(h, n=2)
+    ap, asrc = MR.sample(av, af, 500, 0)
+    bp, bsrc = MR.sample(bv, bf, 500, 1)
+    m = MR.surface_distance(ap, asrc, av, af, bp, bsrc, bv, bf, (0.5 * h, 2 * h))
+    for key in ('accuracy', 'completeness', 'chamfer_l1', 'accuracy_rms', 'completeness_rms', 'accuracy_max'):
+        assert abs(m[key] - h) < 1e-12, (key, m[key])
+    assert abs(m['chamfer_l2'] - 2 * h * h) < 1e-12
+    assert abs(m['normal_consistency'] - 1.) < 1e-12
+    assert m['fscore_%g' % (2 * h)] == 1. and m['precision_%g' % (2 * h)] == 1. and m['recall_%g' % (2 * h)] == 1.
+    assert m['fscore_%g' % (0.5 * h)] == 0. and m['precision_%g' % (0.5 * h)] == 0.
+
+
+def test_reference_on_a_tilted_square():
+    """A square against the same square turned by theta about its edge y = 0: both are flat, so the normal consistency is
+    cos(theta) in both directions; a sample at height y of the turned square is y sin(theta) from the flat one (its foot
+    (x, y cos(theta)) lies inside the square), so completeness = sin(theta) / 2 over uniform samples — checked on the
+    samples' own mean height."""
+    theta = 0.3
+    av, af = MR.square(0., n=2)
+    bv, bf = MR.square(0., tilt=theta, n=2)
+    ap, asrc = MR.sample(av, af, 400, 2)
+    bp, bsrc = MR.sample(bv, bf, 400, 3)
+    m = MR.surface_distance(ap, asrc, av, af, bp, bsrc, bv, bf, (0.1,))
+    for key in ('normal_consistency', 'normal_consistency_pred_to_gt', 'normal_consistency_gt_to_pred'):
+        assert abs(m[key] - math.cos(theta)) < 1e-12, (key, m[key])
+    assert abs(m['completeness'] - bp[:, 2].mean()) < 1e-12
+    # from the flat square, a sample at (x, y) is y sin(theta) from the turned one while its foot y cos(theta) is inside it
+    assert abs(m['accuracy'] - (ap[:, 1] * math.sin(theta)).mean()) < 1e-12
+    assert abs(m['recall_0.1'] - (bp[:, 2] <= 0.1).mean()) < 1e-12
+
+
+def test_reference_search_equals_the_brute_force():
+    rng = np.random.RandomState(0)
+    v = rng.randn(60, 3)
+    f = rng.randint(0, 60, (150, 3))
+    f[100:110] = f[:10]                                    # duplicates: the lowest index
+    p = rng.randn(300, 3) * 1.5
+    p[:20] = v[:20]                                        # on vertices: ties between the faces around them
+    face, d2 = MR.nearest(p, v, f)
+    face0, d20, _, _ = CR.nearest(p, v, f)
+    assert np.array_equal(face, face0) and np.array_equal(d2, d20)
+
+
+def test_argument_errors_of_the_grid_entry_points_do_not_need_a_gpu():
+    """Negative sizes, NULL pointers with non-zero sizes, dims below 1 and a non-positive cell size are found before any HIP
+    call and reported through recmv_last_error."""
+    from recmv import _lib
+    lib = _lib.lib()
+    o = (C.c_float * 3)(0., 0., 0.)
+    one = C.c_void_p(16)                                   # a non-NULL pointer that is never followed
+    assert lib.recmv_mesh_grid_workspace_bytes(0) == 0 and lib.recmv_mesh_grid_workspace_bytes(1025) == (1025 + 2) * 4
+    # count
+    assert lib.recmv_mesh_grid_count(None, -1, None, 0, o, 1., 1, 1, 1, one, one, None) == -1
+    assert b"V=-1" in lib.recmv_last_error()
+    assert lib.recmv_mesh_grid_count(one, 3, one, 1, o, 1., 0, 1, 1, one, one, None) == -1
+    assert b"dims=(0,1,1)" in lib.recmv_last_error()
+    assert lib.recmv_mesh_grid_count(one, 3, one, 1, o, 0., 1, 1, 1, one, one, None) == -1
+    assert b"cell size" in lib.recmv_last_error()
+    assert lib.recmv_mesh_grid_count(one, 3, one, 1, o, float("nan"), 1, 1, 1, one, one, None) == -1
+    assert lib.recmv_mesh_grid_count(one, 3, one, 1, None, 1., 1, 1, 1, one, one, None) == -1
+    assert b"origin" in lib.recmv_last_error()
+    assert lib.recmv_mesh_grid_count(one, 3, one, 1, o, 1., 1, 1, 1, None, one, None) == -1
+    assert b"NULL" in lib.recmv_last_error()
+    assert lib.recmv_mesh_grid_count(one, 3, None, 1, o, 1., 1, 1, 1, one, one, None) == -1
+    assert b"NULL" in lib.recmv_last_error()
+    assert lib.recmv_mesh_grid_count(one, 3, one, 1, o, 1., 1 << 20, 1 << 20, 1, one, one, None) == -1
+    assert b"cells" in lib.recmv_last_error()
+    # fill
+    assert lib.recmv_mesh_grid_fill(one, 3, one, 1, o, 1., 1, 1, 1, one, one, one, -1, one, one, 64, None) == -1
+    assert b"capacity=-1" in lib.recmv_last_error()
+    assert lib.recmv_mesh_grid_fill(one, 3, one, 1, o, 1., 1, 1, -2, one, one, one, 1, one, one, 64, None) == -1
+    assert b"dims" in lib.recmv_last_error()
+    assert lib.recmv_mesh_grid_fill(one, 3, one, 1, o, -1., 1, 1, 1, one, one, one, 1, one, one, 64, None) == -1
+    assert b"cell size" in lib.recmv_last_error()
+    assert lib.recmv_mesh_grid_fill(one, 3, one, 1, o, 1., 1, 1, 1, one, one, None, 1, one, one, 64, None) == -1
+    assert b"NULL" in lib.recmv_last_error()
+    assert lib.recmv_mesh_grid_fill(one, 3, one, 1, o, 1., 1, 1, 1, one, one, one, 1, one, one, 4, None) == -1
+    assert b"workspace" in lib.recmv_last_error()
+    # query
+    args = (one, one, 5, one, one, 7, o, 1., 2, 2, 2, 1, one, one, one, None)
+    assert lib.recmv_closest_point_grid(one, 0, *args) == 0                      # P = 0 is a no-op
+    assert lib.recmv_closest_point_grid(one, -1, *args) == -1
+    assert b"P=-1" in lib.recmv_last_error()
+    assert lib.recmv_closest_point_grid(one, 4, one, one, 0, one, one, 7, o, 1., 2, 2, 2, 1, one, one, one, None) == -1
+    assert b"must not be empty" in lib.recmv_last_error()
+    assert lib.recmv_closest_point_grid(one, 4, one, one, 5, one, one, 7, o, 1., 2, 0, 2, 1, one, one, one, None) == -1
+    assert b"dims" in lib.recmv_last_error()
+    assert lib.recmv_closest_point_grid(one, 4, one, one, 5, one, one, 7, o, 0., 2, 2, 2, 1, one, one, one, None) == -1
+    assert b"cell size" in lib.recmv_last_error()
+    assert lib.recmv_closest_point_grid(one, 4, one, one, 5, one, one, 7, o, 1., 2, 2, 2, 3, one, one, one, None) == -1
+    assert b"lanes" in lib.recmv_last_error()
+    assert lib.recmv_closest_point_grid(None, 4, one, one, 5, one, one, 7, o, 1., 2, 2, 2, 1, one, one, one, None) == -1
+    assert b"NULL" in lib.recmv_last_error()
+    assert lib.recmv_closest_point_grid(one, 4, one, one, 5, one, None, 7, o, 1., 2, 2, 2, 1, one, one, one, None) == -1
+    assert b"NULL" in lib.recmv_last_error()
+
+
+def test_host_build_of_the_grid_kernels_returns_the_brute_force_bits(tmp_path):
+    """tools/mesh_grid_host_check: csrc/mesh_grid.hip's count, fill and one-lane query kernels compiled for the CPU against a
+    brute force with the same closest_tri.h, bit for bit, on seven meshes and grids."""
+    import shutil
+    import subprocess
+    clang = "/opt/rocm/lib/llvm/bin/clang++"
+    if not Path(clang).exists():
+        pytest.skip("ROCm's clang++ not present")
+    src = REPO / "tools" / "mesh_grid_host_check"
+    for f in (src / "common.h", src / "main.cpp", REPO / "rec-mv_amd" / "csrc" / "closest_tri.h"):
+        shutil.copy(f, tmp_path)
+    hip = (REPO / "rec-mv_amd" / "csrc" / "mesh_grid.hip").read_text()
+    cut = hip.index("\nusing namespace recmv;")
+    (tmp_path / "kernels.inc").write_text(hip[:cut + 1])
+    subprocess.run([clang, "-std=c++17", "-O2", "-ffp-contract=off", "-I.", "main.cpp", "-o", "check"], cwd=tmp_path, check=True)
+    r = subprocess.run([str(tmp_path / "check")], cwd=tmp_path, capture_output=True, text=True)
+    print(r.stdout)
+    assert r.returncode == 0 and "all ok" in r.stdout and r.stdout.count(" 0 mismatches") == 7, r.stdout + r.stderr
+
+
+def test_the_chosen_grid():
+    from recmv import metrics
+    h, dims = metrics.choose_grid((0, 0, 0), (1, 1, 1), 6000)
+    assert dims[0] == dims[1] == dims[2] and abs(h - math.sqrt(6 * metrics.FACES_PER_CELL / 6000)) < 1e-6
+    assert all(d * h >= 1. for d in dims)                  # the cells cover the box
+    h, dims = metrics.choose_grid((0, 0, 2), (4, 1, 2), 800)                     # a flat mesh: one cell along z
+    assert dims[2] == 1 and dims[0] > dims[1] > 1 and dims[0] * h >= 4.
+    h, dims = metrics.choose_grid((1, 1, 1), (1, 1, 1), 10)                      # a point
+    assert dims == (1, 1, 1) and h > 0
+    h, dims = metrics.choose_grid((0, 0, 0), (1, 1, 1), 10 ** 9)                 # capped: the offsets table stays small
+    assert dims[0] * dims[1] * dims[2] <= metrics.MAX_CELLS and all(d * h >= 1. for d in dims)
+    with pytest.raises(ValueError):
+        metrics.choose_grid((0, 0, 0), (float("inf"), 1, 1), 10)
+    assert metrics.use_grid('grid', 1, 1) and not metrics.use_grid('brute', 10 ** 9, 10 ** 9)
+    assert metrics.use_grid('auto', 1, 1) == (1 >= metrics.AUTO_GRID_MIN_TESTS)
+    with pytest.raises(ValueError):
+        metrics.use_grid('fast', 1, 1)
+
+
+def test_eval_fl_pairs_files_by_stem(tmp_path):
+    import eval_fl
+    pred, gt, empty = tmp_path / "pred", tmp_path / "gt", tmp_path / "empty"
+    for d in (pred, gt, empty):
+        d.mkdir()
+    for name in ("a.obj", "b.obj", "only_pred.obj", "notes.txt"):
+        (pred / name).write_text("")
+    for name in ("b.obj", "a.obj", "only_gt.obj"):
+        (gt / name).write_text("")
+    pairs, only_pred, only_gt = eval_fl.pair_files(str(pred), str(gt))
+    assert [(s, Path(p).name, Path(g).name) for s, p, g in pairs] == [("a", "a.obj", "a.obj"), ("b", "b.obj", "b.obj")]
+    assert [Path(p).name for p in only_pred] == ["only_pred.obj"] and [Path(g).name for g in only_gt] == ["only_gt.obj"]
+    with pytest.raises(ValueError):                        # nothing pairs
+        eval_fl.pair_files(str(pred), str(empty))
+    with pytest.raises(ValueError):                        # a file against a directory
+        eval_fl.pair_files(str(pred / "a.obj"), str(gt))
+    pairs, _, _ = eval_fl.pair_files(str(pred / "a.obj"), str(gt / "only_gt.obj"))   # two files are one pair
+    assert len(pairs) == 1 and pairs[0][0] == "a"
+    with pytest.raises(SystemExit):                        # the command reports it as a usage error, before any device work
+        eval_fl.main(["--pred", str(pred), "--gt", str(empty)])
+
+
+def test_metrics_refuse_cpu_tensors():
+    from recmv import metrics
+    v, f = MR.square(0., n=2)
+    v, f = torch.from_numpy(v).float(), torch.from_numpy(f)
+    with pytest.raises(RuntimeError):
+        metrics.MeshGrid(v, f)
+    with pytest.raises(RuntimeError):
+        metrics.surface_distance(v, f, v, f, samples=10)
