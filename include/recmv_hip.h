@@ -768,6 +768,42 @@ int recmv_closest_point_grid(const float* p, int64_t P, const int64_t* order, co
                              float cell_size, int64_t nx, int64_t ny, int64_t nz, int32_t lanes, int64_t* face,
                              float* point, float* dist2, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Which faces of two triangle meshes cross (csrc/mesh_intersect.hip, csrc/tri_tri.h; added to ABI v10, no existing
+ * signature changed).  Not in the reference.  Meshes as above: verts [V,3] f32, faces [F,3] int64.  A result is a pair
+ * (i, j), face i of A and face j of B, whose closed boxes meet and that cross PROPERLY: one of the six edge-against-triangle
+ * tests holds with every inequality strict, so touching (a shared vertex or edge, a vertex exactly in the other's plane),
+ * coplanar overlap, a face without area and anything with a NaN are no crossing; a face with an index outside [0, V) crosses
+ * nothing.  self_mode = 1: A and B are the same mesh (the same pointers and sizes), only i < j; skip_shared = 1 (self_mode
+ * only, an argument error otherwise): a pair of faces that share a vertex index is skipped.  Integer atomics only.
+ * Two passes.  Count pass: counts [FA] int32 = the pairs of each face of A, total [1] int64 (device, 8-byte aligned) = their
+ *   sum; both zeroed by the call.  The caller scans counts into offsets [FA + 1] int32 (exclusive; offsets[FA] the total).
+ *   Fill pass: pairs [capacity,2] int32 = the pairs of face i at offsets[i] .. offsets[i + 1], in an order that depends on
+ *   scheduling; cursor [FA] int32 is workspace; dropped [1] int64 (device, 8-byte aligned) = the pairs found that had no
+ *   slot below their face's end and below capacity (0 when the passes agree and capacity >= total) — they are not written.
+ * recmv_mesh_intersect_brute: every pair of faces.  counts and total given, offsets NULL: the count pass; offsets given,
+ *   counts NULL: the fill pass.
+ * recmv_mesh_intersect_grid_count / _fill: through the grid built over B by recmv_mesh_grid_count / _fill (cell_offsets
+ *   [cells + 1], entries [n_entries], the grid arguments of those calls): the same pairs as the brute force.  lanes: 1, 8 or
+ *   64 lanes of a wave per face of A; it does not change the result.
+ * Argument errors are found before any HIP call.  An empty A or B gives no pair (counts and total zeroed).
+ * ---------------------------------------------------------------------------------------------- */
+int recmv_mesh_intersect_brute(const float* a_verts, int64_t VA, const int64_t* a_faces, int64_t FA, const float* b_verts,
+                               int64_t VB, const int64_t* b_faces, int64_t FB, int32_t self_mode, int32_t skip_shared,
+                               int32_t* counts, int64_t* total, const int32_t* offsets, int32_t* pairs, int64_t capacity,
+                               int32_t* cursor, int64_t* dropped, void* stream);
+int recmv_mesh_intersect_grid_count(const float* a_verts, int64_t VA, const int64_t* a_faces, int64_t FA,
+                                    const float* b_verts, int64_t VB, const int64_t* b_faces, int64_t FB,
+                                    const int32_t* cell_offsets, const int32_t* entries, int64_t n_entries,
+                                    const float* origin, float cell_size, int64_t nx, int64_t ny, int64_t nz, int32_t lanes,
+                                    int32_t self_mode, int32_t skip_shared, int32_t* counts, int64_t* total, void* stream);
+int recmv_mesh_intersect_grid_fill(const float* a_verts, int64_t VA, const int64_t* a_faces, int64_t FA,
+                                   const float* b_verts, int64_t VB, const int64_t* b_faces, int64_t FB,
+                                   const int32_t* cell_offsets, const int32_t* entries, int64_t n_entries,
+                                   const float* origin, float cell_size, int64_t nx, int64_t ny, int64_t nz, int32_t lanes,
+                                   int32_t self_mode, int32_t skip_shared, const int32_t* offsets, int32_t* pairs,
+                                   int64_t capacity, int32_t* cursor, int64_t* dropped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,55 +28,13 @@ namespace {
 
 #pragma clang fp contract(off)
 
-#include "closest_tri.h"                                   // Tri, closest_st, load_tri
+#include "closest_tri.h"                                   // Tri, closest_st, load_tri; Grid, Range, face_range, the table
 
 constexpr int kGridBlock = 256;
 constexpr int kBigFace = 256;                              // cells of a face's range above which its wave shares the work
 constexpr int kScanPer = 4;                                // cells per thread of the scan
 constexpr int kScanTile = kGridBlock * kScanPer;           // cells per workgroup of the scan
 constexpr float kEps32 = 1.1920929e-7f;                    // 2^-23
-
-struct Grid {
-  float ox, oy, oz, h, inv_h;
-  int nx, ny, nz;
-};
-
-struct Range {
-  int x0, x1, y0, y1, z0, z1;
-};
-
-// A coordinate in cell units relative to the grid's origin: the ONE expression binning and query share.
-__device__ __forceinline__ float cell_coord(float x, float o, float inv_h) { return (x - o) * inv_h; }
-
-// The cell of a coordinate in cell units, clamped into [0, n) (NaN gives 0: fmaxf returns its other argument).
-__device__ __forceinline__ int cell_index(float u, int n) {
-  return (int)fminf(fmaxf(floorf(u), 0.f), (float)(n - 1));
-}
-
-// The cells face k's axis-aligned box overlaps (false: an index outside [0, V), the face is binned nowhere).  Used by the
-// count and the fill pass alike.
-__device__ __forceinline__ bool face_range(const float* __restrict__ v, const int64_t* __restrict__ f, int64_t V,
-                                           int64_t k, const Grid& g, Range& r) {
-  const int64_t i0 = f[3 * k], i1 = f[3 * k + 1], i2 = f[3 * k + 2];
-  if ((uint64_t)i0 >= (uint64_t)V || (uint64_t)i1 >= (uint64_t)V || (uint64_t)i2 >= (uint64_t)V) return false;
-  const float ax = v[3 * i0], ay = v[3 * i0 + 1], az = v[3 * i0 + 2];
-  const float bx = v[3 * i1], by = v[3 * i1 + 1], bz = v[3 * i1 + 2];
-  const float cx = v[3 * i2], cy = v[3 * i2 + 1], cz = v[3 * i2 + 2];
-  r.x0 = cell_index(cell_coord(fminf(fminf(ax, bx), cx), g.ox, g.inv_h), g.nx);
-  r.x1 = cell_index(cell_coord(fmaxf(fmaxf(ax, bx), cx), g.ox, g.inv_h), g.nx);
-  r.y0 = cell_index(cell_coord(fminf(fminf(ay, by), cy), g.oy, g.inv_h), g.ny);
-  r.y1 = cell_index(cell_coord(fmaxf(fmaxf(ay, by), cy), g.oy, g.inv_h), g.ny);
-  r.z0 = cell_index(cell_coord(fminf(fminf(az, bz), cz), g.oz, g.inv_h), g.nz);
-  r.z1 = cell_index(cell_coord(fmaxf(fmaxf(az, bz), cz), g.oz, g.inv_h), g.nz);
-  if (r.x1 < r.x0) r.x1 = r.x0;                            // (non-finite coordinates)
-  if (r.y1 < r.y0) r.y1 = r.y0;
-  if (r.z1 < r.z0) r.z1 = r.z0;
-  return true;
-}
-
-__device__ __forceinline__ int64_t range_cells(const Range& r) {
-  return (int64_t)(r.x1 - r.x0 + 1) * (r.y1 - r.y0 + 1) * (r.z1 - r.z0 + 1);
-}
 
 // op(cell, face) for every cell of the ranges the lanes of a wave hold.  Every lane of the wave must call it (ballot);
 // small ranges run in their own lane, a range of more than kBigFace cells is spread over the wave.
@@ -142,9 +100,7 @@ grid_fill_kernel(const float* __restrict__ v, int64_t V, const int64_t* __restri
         q.ax = q.ay = q.az = __builtin_nanf("");
         q.bx = q.by = q.bz = q.cx = q.cy = q.cz = 0.f;
       }
-      tris[3 * k] = make_float4(q.ax, q.ay, q.az, q.bx);
-      tris[3 * k + 1] = make_float4(q.by, q.bz, q.cx, q.cy);
-      tris[3 * k + 2] = make_float4(q.cz, 0.f, 0.f, 0.f);
+      tri_table_store(tris, k, q);
     }
     for_each_cell(r, valid, (int)k, g, [&](int cell, int face) {
       const int slot = atomicAdd(cursor + cell, 1);
@@ -321,8 +277,7 @@ closest_point_grid_kernel(const float* __restrict__ p, int64_t P, const int64_t*
       for (int e = e0; e < e1; ++e) {
         const int k2 = entries[e];
         if ((uint64_t)k2 >= (uint64_t)F) continue;
-        const float4 t0 = tris[3 * (int64_t)k2], t1 = tris[3 * (int64_t)k2 + 1], t2 = tris[3 * (int64_t)k2 + 2];
-        const Tri q{t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x};
+        const Tri q = tri_table_load(tris, k2);
         float s, t;
         take_min(closest_st(px, py, pz, q, s, t), k2, best, bidx);
       }
@@ -349,8 +304,7 @@ closest_point_grid_kernel(const float* __restrict__ p, int64_t P, const int64_t*
   }
   if (sub != 0) return;
   if (bidx >= 0) {
-    const float4 t0 = tris[3 * (int64_t)bidx], t1 = tris[3 * (int64_t)bidx + 1], t2 = tris[3 * (int64_t)bidx + 2];
-    const Tri q{t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x};
+    const Tri q = tri_table_load(tris, bidx);
     float s, t;
     closest_st(px, py, pz, q, s, t);
     face[i] = bidx;

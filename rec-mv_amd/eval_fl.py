@@ -6,10 +6,14 @@ partner are listed in the output and skipped, and no pair at all is an error.  T
 frame: no alignment is attempted (`--scale` multiplies the prediction, for captures in another unit).  Per pair
 recmv.metrics.surface_distance (accuracy, completeness, Chamfer, normal consistency, precision / recall / F-score at
 `--thresholds`, definitions in INTEGRATION.md §5), then the means over the pairs.  When the prediction directory is a sequence
-of one topology the output also holds infer_fl_animation.py's temporal smoothness figure of it.
+of one topology the output also holds infer_fl_animation.py's temporal smoothness figure of it.  `--intersections` adds per
+pair the faces of the prediction that take part in a crossing of the prediction with itself and their share of its faces
+(`self_intersecting_faces`, `self_intersection_ratio`), the same for the ground truth (`…_gt`), and with `--body` (a mesh or
+a directory paired by stem, like `--gt`) the prediction's faces that cross that body (`body_intersecting_faces`,
+`body_intersection_ratio`); definitions in INTEGRATION.md §5.
 
     python rec-mv_amd/eval_fl.py --gpu-ids 0 --pred <obj|dir> --gt <obj|dir> [--samples N] [--seed S] [--thresholds t ...]
-        [--scale s] [--method auto|grid|brute] [--out metrics.json]
+        [--scale s] [--method auto|grid|brute] [--intersections [--body <obj|dir>]] [--out metrics.json]
 """
 import argparse
 import json
@@ -31,6 +35,9 @@ def build_parser():
                         help='distances for precision / recall / F-score, in the meshes\' length unit')
     parser.add_argument('--scale', default=1.0, type=float, help='factor on the prediction (captures in another unit)')
     parser.add_argument('--method', default='auto', choices=['auto', 'grid', 'brute'])
+    parser.add_argument('--intersections', action='store_true',
+                        help='also count the self-crossing faces of both meshes (and the body-crossing ones with --body)')
+    parser.add_argument('--body', default=None, help='body mesh (.obj) or a directory of them paired by stem; needs --intersections')
     parser.add_argument('--out', default=None, help='metrics JSON (default: printed only)')
     return parser
 
@@ -65,6 +72,15 @@ def main(argv=None):
         pairs, only_pred, only_gt = pair_files(args.pred, args.gt)
     except ValueError as e:
         parser.error(str(e))
+    if args.body and not args.intersections:
+        parser.error("--body needs --intersections")
+    bodies = None
+    if args.body:
+        bodies = _objs(args.body)
+        if bodies is None and not osp.isfile(args.body):
+            parser.error("no such mesh: %s" % args.body)
+        if bodies is not None and not all(stem in bodies for stem, _, _ in pairs):
+            parser.error("--body %s has no mesh for: %s" % (args.body, ', '.join(s for s, _, _ in pairs if s not in bodies)))
     import torch
     from infer_fl_animation import temporal_smoothness
     from recmv import metrics
@@ -81,6 +97,19 @@ def main(argv=None):
         per_pair[stem] = metrics.surface_distance(pv.to(device), pfaces.to(device), gv.to(device), gfaces.to(device),
                                                   samples=args.samples, seed=args.seed, thresholds=thresholds,
                                                   method=args.method)
+        if args.intersections:
+            own = metrics.self_intersections(pv.to(device), pfaces.to(device), method=args.method)
+            own_gt = metrics.self_intersections(gv.to(device), gfaces.to(device), method=args.method)
+            per_pair[stem].update({'self_intersecting_faces': int(own['faces'].shape[0]),
+                                   'self_intersection_ratio': own['ratio'],
+                                   'self_intersecting_faces_gt': int(own_gt['faces'].shape[0]),
+                                   'self_intersection_ratio_gt': own_gt['ratio']})
+            if args.body:
+                bv, bfaces = read_obj(bodies[stem] if bodies is not None else args.body)
+                hit = metrics.mesh_intersections(pv.to(device), pfaces.to(device), bv.to(device), bfaces.to(device),
+                                                 method=args.method)
+                per_pair[stem].update({'body_intersecting_faces': int(hit['faces_a'].shape[0]),
+                                       'body_intersection_ratio': hit['ratio_a']})
         print('%s: chamfer_l1 %.6g, accuracy %.6g, completeness %.6g, normal consistency %.4f' % (
             stem, per_pair[stem]['chamfer_l1'], per_pair[stem]['accuracy'], per_pair[stem]['completeness'],
             per_pair[stem]['normal_consistency']))

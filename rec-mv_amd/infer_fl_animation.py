@@ -11,19 +11,24 @@ what the reference writes:
   animation/<data-type>/meshs/<garment>_<fid:06d>.png        Phong renders, posed body | posed garment (not with --nI)
   animation/<data-type>/colors/<garment>_<fid:06d>.png       colour render (not with --nColor / --nI)
 
-and two additions:
+and three additions:
 
   animation/<data-type>/smoothness.json   per garment the reference's temporal smoothness figure (tools/compute_CSI.py): the
                                           mean over the inner frames of the mean vertex norm of the second difference
   animation/<data-type>/collisions.json   with --fix-collisions: per garment and frame the vertices moved, the vertices left
                                           unresolved and the passes run by the body-collision repair (recmv/collide.py)
 
+  animation/<data-type>/intersections.json  with --report-intersections: per frame and garment the garment faces that cross
+                                          the posed body, those that cross the garment itself, and per pair of garments
+                                          the faces that cross each other (recmv.collide.intersection_report), on the meshes
+                                          written — after the repair when --fix-collisions is given too
+
 Deviations: the motion is an input (`--motion`; the reference reads ../snug/assets/CMU/131/131_11_poses.npz),
 registration is register_fl.py's job (the reference registers on the first frame), and the collision repair is not in the
 reference (off unless asked for).  `--nV` is accepted and ignored (the reference writes no video either).
 
     python rec-mv_amd/infer_fl_animation.py --gpu-ids 0 --rec-root <capture>/<save-folder> --data-type snug \\
-        --motion <motion.npz> [--fix-collisions]
+        --motion <motion.npz> [--fix-collisions] [--report-intersections]
 """
 import argparse
 import json
@@ -53,6 +58,8 @@ def build_parser():
     parser.add_argument('--collision-eps', default=None, type=float,
                         help='margin kept between garment and body, in the capture\'s length unit (default 2e-3)')
     parser.add_argument('--collision-iters', default=None, type=int, help='passes of the collision repair (default 3)')
+    parser.add_argument('--report-intersections', action='store_true',
+                        help='write intersections.json: garment faces crossing the body, themselves and each other')
     parser.set_defaults(a_pose=False)
     return parser
 
@@ -97,17 +104,21 @@ def main(argv=None):
 
     sequences = {name: {} for name in names}
     collisions = {name: {} for name in names}
+    intersections = {}
     n_frames = 0
     for data_index, (frame_ids, outs) in enumerate(dataloader):
         if (data_index * batch_size > args.frames) if args.frames >= 0 else False:
             break
         frame_ids = frame_ids.long().to(device)
         stats = {}
+        extra = {'intersection_stats': []} if args.report_intersections else {}
         colors_list, imgs_list, defVs_list = optNet.infer_garment_animation(
             garment_TmpVs, garment_Tmpfs, outs['poses_y'], H, W, RATIO, frame_ids, rec_root, notcolor=args.nColor,
             fix_collisions=args.fix_collisions, collision_eps=args.collision_eps, collision_iters=args.collision_iters,
-            collision_stats=stats)
+            collision_stats=stats, **extra)
         fids = frame_ids.cpu().numpy().reshape(-1)
+        for fid, frame in zip(fids, extra.get('intersection_stats', [])):
+            intersections[str(int(fid))] = frame
         for colors, imgs, defVs, name in zip(colors_list, imgs_list, defVs_list, names):
             for j, (fid, img, defV) in enumerate(zip(fids, imgs, defVs)):
                 np.save(osp.join(save_path, 'meshs/{}_{:06d}.npy'.format(name, fid)), defV.reshape(-1, 3))
@@ -134,8 +145,18 @@ def main(argv=None):
             c = collisions[name].values()
             print('collision repair of %s: %d vertices moved, %d unresolved over %d frames' % (
                 name, sum(v['moved'] for v in c), sum(v['unresolved'] for v in c), len(c)))
+    if args.report_intersections:
+        with open(osp.join(save_path, 'intersections.json'), 'w') as fh:
+            json.dump(intersections, fh, indent=1)
+        for name in names:
+            c = [f[name] for f in intersections.values()]
+            print('crossing faces of %s over %d frames: %d against the body, %d against itself' % (
+                name, len(c), sum(v['body_faces'] for v in c), sum(v['self_faces'] for v in c)))
     print('done')
-    return {'frames': n_frames, 'smoothness': smooth, 'collisions': collisions if args.fix_collisions else None}
+    res = {'frames': n_frames, 'smoothness': smooth, 'collisions': collisions if args.fix_collisions else None}
+    if args.report_intersections:
+        res['intersections'] = intersections
+    return res
 
 
 if __name__ == '__main__':

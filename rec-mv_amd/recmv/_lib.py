@@ -192,6 +192,12 @@ def _declare(lib):
                                            i64, vp]),
         "recmv_closest_point_grid": (C.c_int, [vp, i64, vp, vp, i64, vp, vp, i64, C.POINTER(f32), f32, i64, i64, i64, i32,
                                                vp, vp, vp, vp]),
+        "recmv_mesh_intersect_brute": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, i64, vp, vp,
+                                                 vp]),
+        "recmv_mesh_intersect_grid_count": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, C.POINTER(f32), f32,
+                                                      i64, i64, i64, i32, i32, i32, vp, vp, vp]),
+        "recmv_mesh_intersect_grid_fill": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, C.POINTER(f32), f32,
+                                                     i64, i64, i64, i32, i32, i32, vp, vp, i64, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)       # AttributeError if the symbol is missing: fail loudly

@@ -8,6 +8,8 @@ n interpolated there and the signed distance s = (p - q) . n, and a vertex with 
   point_mesh_nearest   recmv_point_mesh_nearest: nearest body triangle and squared distance of every vertex of every frame
   collision_push       recmv_collision_push: the push and the per-frame counts
   resolve              `iters` passes of the two (a push can change which face is nearest)
+  intersection_report  what the repair leaves: per frame the garment FACES that still cut through the body, through the
+                       garment itself and through another garment (recmv.metrics, csrc/mesh_intersect.hip); detection only
   point_mesh_nearest_torch   the same search in plain torch (chunked point-triangle distances + argmin), the baseline of
                        tools/collide_timing.py
 
@@ -113,6 +115,45 @@ def resolve(garment_vs, body_vs, body_fs, eps=COLLISION_EPS, max_depth=COLLISION
             break
     changed = (vs != garment_vs).any(-1).sum(1).cpu().tolist() if B else []
     return vs, {'moved': changed, 'unresolved': unresolved, 'passes': len(per_pass), 'moved_per_pass': per_pass}
+
+
+@torch.no_grad()
+def intersection_report(garments, body_vs, body_fs, method='auto'):
+    """Crossing faces of posed garments, frame by frame.  `garments` maps a name to (vs [B,N,3] f32, faces [F,3] int64), the
+    body is body_vs [B,V,3] f32 / body_fs [F,3] int64 (CUDA, one device, the same B).  Returns a list of B dicts:
+    {name: {'body_faces': garment faces that cross a body face, 'self_faces': garment faces in a crossing pair of the
+    garment with itself, 'faces': the garment's face count}, ..., 'between': {'<a>|<b>': {'faces_a', 'faces_b'}}} with one
+    entry of 'between' per pair of garments (in the order given).  Crossing as in INTEGRATION.md §5 (strict: touching is
+    none); a garment without faces reports zeros.  The vertex repair above judges vertices; this judges faces."""
+    from . import metrics
+    names = list(garments)
+    B = body_vs.shape[0]
+    for name in names:
+        vs, fs = garments[name]
+        _check(vs, body_vs, body_fs)
+    report = []
+    for b in range(B):
+        frame, between = {}, {}
+        for name in names:
+            vs, fs = garments[name]
+            if fs.shape[0] == 0 or vs.shape[1] == 0:
+                frame[name] = {'body_faces': 0, 'self_faces': 0, 'faces': int(fs.shape[0])}
+                continue
+            body = metrics.mesh_intersections(vs[b], fs, body_vs[b], body_fs, method=method)
+            own = metrics.self_intersections(vs[b], fs, method=method)
+            frame[name] = {'body_faces': int(body['faces_a'].shape[0]), 'self_faces': int(own['faces'].shape[0]),
+                           'faces': int(fs.shape[0])}
+        for x, a in enumerate(names):
+            for c in names[x + 1:]:
+                (va, fa), (vc, fc) = garments[a], garments[c]
+                if min(fa.shape[0], fc.shape[0], va.shape[1], vc.shape[1]) == 0:
+                    between['%s|%s' % (a, c)] = {'faces_a': 0, 'faces_b': 0}
+                    continue
+                m = metrics.mesh_intersections(va[b], fa, vc[b], fc, method=method)
+                between['%s|%s' % (a, c)] = {'faces_a': int(m['faces_a'].shape[0]), 'faces_b': int(m['faces_b'].shape[0])}
+        frame['between'] = between
+        report.append(frame)
+    return report
 
 
 def point_mesh_nearest_torch(p, verts, faces, chunk_elems=1 << 22):

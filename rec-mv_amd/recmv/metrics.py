@@ -3,6 +3,10 @@ whose tools/comparison_results.py stops after loading a mesh.
 
   MeshGrid          a uniform grid over a triangle mesh (recmv_mesh_grid_count / recmv_mesh_grid_fill); `.closest_point(p)`
                     is iso_remesh.closest_point's exact search through it (recmv_closest_point_grid): the same bits
+                    `.intersections(verts, faces)` / `.self_intersections()` the faces of another mesh / of its own that
+                    cross its faces (recmv_mesh_intersect_grid_count / _fill, csrc/mesh_intersect.hip)
+  mesh_intersections, self_intersections   the crossing face pairs of two meshes / of one mesh, the faces involved and their
+                    share of the mesh — through the grid or by the brute force (recmv_mesh_intersect_brute)
   sample_surface    loop.sample_fan_mesh's area-weighted surface samples, with the picked faces
   surface_distance  accuracy / completeness / Chamfer / normal consistency / precision, recall and F-score at thresholds
                     between two meshes taken to be in one frame (no alignment), from surface samples in both directions
@@ -17,6 +21,9 @@ reduction in float64 on the device, one read-back):
                       normals; `normal_consistency` is the average of the two
   precision_<t>       the share of the prediction's samples with d <= t; recall_<t> the same for the ground truth's;
                       fscore_<t> their harmonic mean (0 when both are 0)
+Crossing (csrc/tri_tri.h): two faces cross when an edge of one properly pierces the other — every
+inequality strict, so touching, coplanar overlap, faces without area and NaN are no crossing.  Exact integers: the grid and
+the brute force give the same pairs.
 """
 import ctypes as C
 import math
@@ -35,6 +42,13 @@ QUERY_SORTED = True            # tools/mesh_distance_timing.py (profiles/mesh_di
 # been recorded yet, so the value is unreachable and 'auto' chooses the brute force at every size.
 AUTO_GRID_MIN_TESTS = 1 << 62
 DEFAULT_THRESHOLDS = (0.005, 0.01, 0.02)
+# The crossing query.  Both constants are to be read off profiles/mesh_intersect_timing.json (tools/mesh_intersect_timing.py;
+# DESIGN.md §8 "Crossing faces"): the lanes per face of A with the lowest summed query time, and the number of face pairs
+# FA * FB from which the grid (build + count + fill) is faster than the brute force (count + fill).  That file has not been
+# recorded on an MI355X yet: the lanes are a guess, and the crossover is unreachable, so 'auto' chooses the brute force at
+# every size until it exists (method='grid' is there for large meshes).
+INTERSECT_LANES = 8
+AUTO_GRID_MIN_PAIRS = 1 << 62
 
 
 def choose_grid(lo, hi, n_faces, faces_per_cell=FACES_PER_CELL, max_cells=MAX_CELLS):
@@ -62,14 +76,14 @@ def choose_grid(lo, hi, n_faces, faces_per_cell=FACES_PER_CELL, max_cells=MAX_CE
         h *= 1.02 * (cells / max_cells) ** (1. / max(sum(d > 1 for d in dims), 1))
 
 
-def _check_mesh(verts, faces):
+def _check_mesh(verts, faces, allow_empty=False):
     L.require_cuda(verts, "verts")
     L.require_cuda(faces, "faces")
     if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
         raise ValueError("verts must be float32 of shape [V,3]")
     if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
         raise ValueError("faces must be int64 of shape [F,3]")
-    if faces.shape[0] == 0 or verts.shape[0] == 0:
+    if not allow_empty and (faces.shape[0] == 0 or verts.shape[0] == 0):
         raise ValueError("the surface is empty")
 
 
@@ -153,6 +167,125 @@ class MeshGrid:
                                                      self.cell_size, *self.dims, lanes, L.ptr(face), L.ptr(point),
                                                      L.ptr(dist2), L.stream_ptr(dev)), "closest_point_grid")
         return face, point, dist2
+
+
+    def _crossings(self, verts, faces, self_mode, lanes):
+        lanes = INTERSECT_LANES if lanes is None else int(lanes)
+        dev = self.verts.device
+        FA = faces.shape[0]
+        grid = (L.ptr(self.offsets), L.ptr(self.entries), self.n_entries, self.origin, self.cell_size, *self.dims, lanes,
+                int(self_mode), int(self_mode))
+        mesh = (L.ptr(verts), verts.shape[0], L.ptr(faces), FA, L.ptr(self.verts), self.verts.shape[0], L.ptr(self.faces),
+                self.faces.shape[0])
+        lib = L.lib()
+
+        def count(counts, total):
+            L.check(lib.recmv_mesh_intersect_grid_count(*mesh, *grid, L.ptr(counts), L.ptr(total), L.stream_ptr(dev)),
+                    "mesh_intersect_grid_count")
+
+        def fill(offsets, pairs, capacity, cursor, dropped):
+            L.check(lib.recmv_mesh_intersect_grid_fill(*mesh, *grid, L.ptr(offsets), L.ptr(pairs), capacity, L.ptr(cursor),
+                                                       L.ptr(dropped), L.stream_ptr(dev)), "mesh_intersect_grid_fill")
+        return _two_passes(count, fill, FA, dev)
+
+    def intersections(self, verts, faces, lanes=None):
+        """The faces of the mesh verts [V,3] f32 / faces [F,3] int64 (mesh A) that cross faces of the grid's mesh (B): (pairs
+        [K,2] int64 of (face of A, face of B) sorted by (i, j), counts [F] int32 of pairs per face of A).  One read-back, for
+        K.  `lanes` (1, 8 or 64 lanes per face of A) chooses the launch shape; it does not change the result."""
+        _check_mesh(verts, faces, allow_empty=True)
+        if verts.device != self.verts.device:
+            raise ValueError("the two meshes must be on one device")
+        return self._crossings(verts.contiguous(), faces.contiguous(), False, lanes)
+
+    def self_intersections(self, lanes=None):
+        """The pairs i < j of the grid's own faces that cross and share no vertex index: (pairs [K,2] int64 sorted, counts
+        [F] int32 per lower face)."""
+        return self._crossings(self.verts, self.faces, True, lanes)
+
+
+def _two_passes(count, fill, FA, dev):
+    """count(counts, total), the scan, fill(offsets, pairs, capacity, cursor, dropped); the pairs sorted by (i, j)."""
+    counts = L.scratch((FA,), torch.int32, dev)
+    total = L.scratch((1,), torch.int64, dev)
+    with L.device_guard(dev):
+        count(counts, total)
+    K = int(total.item())                                                         # the one read-back
+    if K >= 1 << 30:
+        raise ValueError("%d crossing pairs: at most 2^30 - 1" % K)
+    if K == 0:
+        return torch.zeros((0, 2), dtype=torch.int64, device=dev), counts
+    offsets = torch.zeros(FA + 1, dtype=torch.int32, device=dev)
+    offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64).to(torch.int32)
+    pairs = L.scratch((K, 2), torch.int32, dev)
+    cursor = L.scratch((FA,), torch.int32, dev)
+    dropped = L.scratch((1,), torch.int64, dev)
+    with L.device_guard(dev):
+        fill(offsets, pairs, K, cursor, dropped)
+    pairs = pairs.long()
+    order = torch.sort(pairs[:, 0] * (1 << 31) + pairs[:, 1])[1]                   # face ids are below 2^31
+    return pairs[order].contiguous(), counts
+
+
+def _brute_crossings(a_v, a_f, b_v, b_f, self_mode):
+    dev = a_v.device
+    FA = a_f.shape[0]
+    mesh = (L.ptr(a_v), a_v.shape[0], L.ptr(a_f), FA, L.ptr(b_v), b_v.shape[0], L.ptr(b_f), b_f.shape[0], int(self_mode),
+            int(self_mode))
+    lib = L.lib()
+
+    def count(counts, total):
+        L.check(lib.recmv_mesh_intersect_brute(*mesh, L.ptr(counts), L.ptr(total), None, None, 0, None, None,
+                                               L.stream_ptr(dev)), "mesh_intersect_brute")
+
+    def fill(offsets, pairs, capacity, cursor, dropped):
+        L.check(lib.recmv_mesh_intersect_brute(*mesh, None, None, L.ptr(offsets), L.ptr(pairs), capacity, L.ptr(cursor),
+                                               L.ptr(dropped), L.stream_ptr(dev)), "mesh_intersect_brute")
+    return _two_passes(count, fill, FA, dev)
+
+
+def use_grid_for_pairs(method, n_faces_a, n_faces_b):
+    if method not in ('auto', 'grid', 'brute'):
+        raise ValueError("method must be 'auto', 'grid' or 'brute' (got %r)" % (method,))
+    return method == 'grid' or (method == 'auto' and n_faces_a * n_faces_b >= AUTO_GRID_MIN_PAIRS)
+
+
+def _involved(faces_col, n_faces):
+    f = torch.unique(faces_col)
+    return f, float(f.shape[0]) / max(int(n_faces), 1)
+
+
+@torch.no_grad()
+def mesh_intersections(a_v, a_f, b_v, b_f, method='auto', lanes=None):
+    """The crossings of mesh A (a_v [V,3] f32, a_f [F,3] int64) and mesh B (CUDA tensors on one device): a dict with `pairs`
+    [K,2] int64 (face of A, face of B) sorted by (i, j), `n_pairs`, `faces_a` / `faces_b` (the distinct faces involved,
+    sorted) and `ratio_a` / `ratio_b` (their number over the mesh's face count).  'grid': a MeshGrid over B; 'brute': every
+    pair of faces; 'auto': by the number of face pairs.  The same integers either way."""
+    _check_mesh(a_v, a_f)
+    _check_mesh(b_v, b_f)
+    if a_v.device != b_v.device:
+        raise ValueError("the two meshes must be on one device")
+    a_v, a_f, b_v, b_f = (t.contiguous() for t in (a_v, a_f, b_v, b_f))
+    if use_grid_for_pairs(method, a_f.shape[0], b_f.shape[0]):
+        pairs, _ = MeshGrid(b_v, b_f).intersections(a_v, a_f, lanes=lanes)
+    else:
+        pairs, _ = _brute_crossings(a_v, a_f, b_v, b_f, False)
+    fa, ra = _involved(pairs[:, 0], a_f.shape[0])
+    fb, rb = _involved(pairs[:, 1], b_f.shape[0])
+    return {'pairs': pairs, 'n_pairs': int(pairs.shape[0]), 'faces_a': fa, 'faces_b': fb, 'ratio_a': ra, 'ratio_b': rb}
+
+
+@torch.no_grad()
+def self_intersections(v, f, method='auto', lanes=None):
+    """The crossings of a mesh with itself: pairs i < j of faces that cross and share no vertex index.  A dict with `pairs`
+    [K,2] int64 sorted, `n_pairs`, `faces` (the distinct faces involved) and `ratio` (their number over the face count)."""
+    _check_mesh(v, f)
+    v, f = v.contiguous(), f.contiguous()
+    if use_grid_for_pairs(method, f.shape[0], f.shape[0]):
+        pairs, _ = MeshGrid(v, f).self_intersections(lanes=lanes)
+    else:
+        pairs, _ = _brute_crossings(v, f, v, f, True)
+    faces, ratio = _involved(pairs.reshape(-1), f.shape[0])
+    return {'pairs': pairs, 'n_pairs': int(pairs.shape[0]), 'faces': faces, 'ratio': ratio}
 
 
 def sample_surface(verts, faces, count, generator=None):

@@ -59,7 +59,7 @@ def _templates(specs, names):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    from recmv import registration, utils
+    from recmv import metrics, registration, utils
     from infer_fl import load_run
 
     rec_root = osp.normpath(args.rec_root)
@@ -100,6 +100,11 @@ def main(argv=None):
                                             iso_remesh=iso)
     for n, p, (v, f) in zip(names, paths, meshes):
         print('%s: %d vertices, %d faces -> %s' % (n, v.shape[0], f.shape[0], p))
+        if v.shape[0] and f.shape[0]:                      # a fit or a remesh can fold the template: say so (a log line only)
+            dev = TmpVs_list[0].device
+            own = metrics.self_intersections(v.detach().to(dev).float(), f.to(dev).long())
+            print('%s: %d of %d faces take part in a self-intersection (%d crossing pairs)' % (
+                n, own['faces'].shape[0], f.shape[0], own['n_pairs']))
     return meshes
 
 
