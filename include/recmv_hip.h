@@ -804,6 +804,34 @@ int recmv_mesh_intersect_grid_fill(const float* a_verts, int64_t VA, const int64
                                    int32_t self_mode, int32_t skip_shared, const int32_t* offsets, int32_t* pairs,
                                    int64_t capacity, int32_t* cursor, int64_t* dropped, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Segments against a triangle mesh (csrc/segment_mesh.hip, csrc/seg_tri.h; added to ABI v10, no existing signature
+ * changed).  The reference casts rays with pyembree (engineer/optimizer/surface_intesection.py).  Segments p [S,3], q [S,3]
+ * f32, the mesh as above.  Segment pq HITS face abc iff orient(a,b,c,p) and orient(a,b,c,q) have strictly opposite signs and
+ * orient(p,q,a,b), orient(p,q,b,c), orient(p,q,c,a) strictly the same sign (csrc/tri_tri.h's edge-against-triangle test), and
+ * the segment passes the face's box (csrc/seg_tri.h's gate, implied by a hit in exact arithmetic).  Strict: touching (an
+ * endpoint exactly in the plane, a segment through a vertex or along an edge), a segment in the face's plane, a face without
+ * area, a segment whose endpoints are the same bits and anything not finite are no hit; a face with an index outside [0, V)
+ * is hit by nothing.  t = sp / (sp - sq), sp = orient(a,b,c,p), sq = orient(a,b,c,q), kept within the parameters at which
+ * the segment is within 40 eps32 S (S the largest |coordinate| of p and q) of the face's box (csrc/seg_tri.h's seg_clamp_t:
+ * no change where the determinants mean something, and what lets the first-hit walk stop where they are noise).
+ * Outputs: face [S] int64 = the hit with the smallest t, ties to the lowest face id (-1: none), t [S] f32 (NaN: none),
+ *   count [S] int32 = the number of faces hit.  No atomics.  S = 0 is a no-op; F = 0 hits nothing.
+ * recmv_segment_mesh_brute: every face.
+ * recmv_segment_mesh_grid: through the grid built over the mesh by recmv_mesh_grid_count / _fill (cell_offsets [cells + 1],
+ *   entries [n_entries], the grid arguments of those calls): bit for bit the brute force's outputs.  lanes: 1, 8 or 64 lanes
+ *   of a wave per segment; it does not change the result.  want_count = 1: the whole segment is walked and count written;
+ *   want_count = 0: the walk may stop behind the first hit, count is not written and may be NULL.
+ * Argument errors (negative sizes, NULL pointers, lanes, dims below 1, a cell size that is not positive and finite,
+ * want_count = 1 without count) are found before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+int recmv_segment_mesh_brute(const float* p, const float* q, int64_t S, const float* verts, int64_t V, const int64_t* faces,
+                             int64_t F, int64_t* face, float* t, int32_t* count, void* stream);
+int recmv_segment_mesh_grid(const float* p, const float* q, int64_t S, const float* verts, int64_t V, const int64_t* faces,
+                            int64_t F, const int32_t* cell_offsets, const int32_t* entries, int64_t n_entries,
+                            const float* origin, float cell_size, int64_t nx, int64_t ny, int64_t nz, int32_t lanes,
+                            int32_t want_count, int64_t* face, float* t, int32_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

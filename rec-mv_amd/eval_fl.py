@@ -10,10 +10,11 @@ of one topology the output also holds infer_fl_animation.py's temporal smoothnes
 pair the faces of the prediction that take part in a crossing of the prediction with itself and their share of its faces
 (`self_intersecting_faces`, `self_intersection_ratio`), the same for the ground truth (`…_gt`), and with `--body` (a mesh or
 a directory paired by stem, like `--gt`) the prediction's faces that cross that body (`body_intersecting_faces`,
-`body_intersection_ratio`); definitions in INTEGRATION.md §5.
+`body_intersection_ratio`), and with `--penetration` besides the prediction's vertices inside that body and the largest
+distance of one of them to its surface (`body_inside_vertices`, `body_max_depth`); definitions in INTEGRATION.md §5.
 
     python rec-mv_amd/eval_fl.py --gpu-ids 0 --pred <obj|dir> --gt <obj|dir> [--samples N] [--seed S] [--thresholds t ...]
-        [--scale s] [--method auto|grid|brute] [--intersections [--body <obj|dir>]] [--out metrics.json]
+        [--scale s] [--method auto|grid|brute] [--intersections [--body <obj|dir> [--penetration]]] [--out metrics.json]
 """
 import argparse
 import json
@@ -38,6 +39,8 @@ def build_parser():
     parser.add_argument('--intersections', action='store_true',
                         help='also count the self-crossing faces of both meshes (and the body-crossing ones with --body)')
     parser.add_argument('--body', default=None, help='body mesh (.obj) or a directory of them paired by stem; needs --intersections')
+    parser.add_argument('--penetration', action='store_true',
+                        help='with --intersections --body: also the vertices of the prediction inside the body and their largest depth')
     parser.add_argument('--out', default=None, help='metrics JSON (default: printed only)')
     return parser
 
@@ -74,6 +77,8 @@ def main(argv=None):
         parser.error(str(e))
     if args.body and not args.intersections:
         parser.error("--body needs --intersections")
+    if args.penetration and not (args.intersections and args.body):
+        parser.error("--penetration needs --intersections and --body")
     bodies = None
     if args.body:
         bodies = _objs(args.body)
@@ -110,6 +115,9 @@ def main(argv=None):
                                                  method=args.method)
                 per_pair[stem].update({'body_intersecting_faces': int(hit['faces_a'].shape[0]),
                                        'body_intersection_ratio': hit['ratio_a']})
+                if args.penetration:
+                    pen = metrics.penetration(pv.to(device), bv.to(device), bfaces.to(device), method=args.method)
+                    per_pair[stem].update({'body_inside_vertices': pen['count'], 'body_max_depth': pen['max_depth']})
         print('%s: chamfer_l1 %.6g, accuracy %.6g, completeness %.6g, normal consistency %.4f' % (
             stem, per_pair[stem]['chamfer_l1'], per_pair[stem]['accuracy'], per_pair[stem]['completeness'],
             per_pair[stem]['normal_consistency']))

@@ -21,14 +21,16 @@ and three additions:
   animation/<data-type>/intersections.json  with --report-intersections: per frame and garment the garment faces that cross
                                           the posed body, those that cross the garment itself, and per pair of garments
                                           the faces that cross each other (recmv.collide.intersection_report), on the meshes
-                                          written — after the repair when --fix-collisions is given too
+                                          written — after the repair when --fix-collisions is given too; with --penetration
+                                          also the garment vertices inside the body (`inside_vertices`) and the largest
+                                          distance of one of them to the body's surface (`max_depth`)
 
 Deviations: the motion is an input (`--motion`; the reference reads ../snug/assets/CMU/131/131_11_poses.npz),
 registration is register_fl.py's job (the reference registers on the first frame), and the collision repair is not in the
 reference (off unless asked for).  `--nV` is accepted and ignored (the reference writes no video either).
 
     python rec-mv_amd/infer_fl_animation.py --gpu-ids 0 --rec-root <capture>/<save-folder> --data-type snug \\
-        --motion <motion.npz> [--fix-collisions] [--report-intersections]
+        --motion <motion.npz> [--fix-collisions] [--report-intersections [--penetration]]
 """
 import argparse
 import json
@@ -60,6 +62,8 @@ def build_parser():
     parser.add_argument('--collision-iters', default=None, type=int, help='passes of the collision repair (default 3)')
     parser.add_argument('--report-intersections', action='store_true',
                         help='write intersections.json: garment faces crossing the body, themselves and each other')
+    parser.add_argument('--penetration', action='store_true',
+                        help='with --report-intersections: also the garment vertices inside the body and their largest depth')
     parser.set_defaults(a_pose=False)
     return parser
 
@@ -81,6 +85,8 @@ def main(argv=None):
     assert not (args.nV and args.nI)
     if args.data_type != 'snug':
         parser.error("--data-type %s: only the snug loader yields the poses an animation is driven with" % args.data_type)
+    if args.penetration and not args.report_intersections:
+        parser.error("--penetration needs --report-intersections")
     if not args.motion:
         parser.error("--data-type snug needs --motion <npz>")
     import numpy as np
@@ -112,6 +118,8 @@ def main(argv=None):
         frame_ids = frame_ids.long().to(device)
         stats = {}
         extra = {'intersection_stats': []} if args.report_intersections else {}
+        if args.penetration:
+            extra['intersection_penetration'] = True
         colors_list, imgs_list, defVs_list = optNet.infer_garment_animation(
             garment_TmpVs, garment_Tmpfs, outs['poses_y'], H, W, RATIO, frame_ids, rec_root, notcolor=args.nColor,
             fix_collisions=args.fix_collisions, collision_eps=args.collision_eps, collision_iters=args.collision_iters,

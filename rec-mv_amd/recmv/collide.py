@@ -9,7 +9,8 @@ n interpolated there and the signed distance s = (p - q) . n, and a vertex with 
   collision_push       recmv_collision_push: the push and the per-frame counts
   resolve              `iters` passes of the two (a push can change which face is nearest)
   intersection_report  what the repair leaves: per frame the garment FACES that still cut through the body, through the
-                       garment itself and through another garment (recmv.metrics, csrc/mesh_intersect.hip); detection only
+                       garment itself and through another garment (recmv.metrics, csrc/mesh_intersect.hip), optionally the
+                       garment VERTICES inside the body and their depth (csrc/segment_mesh.hip); detection only
   point_mesh_nearest_torch   the same search in plain torch (chunked point-triangle distances + argmin), the baseline of
                        tools/collide_timing.py
 
@@ -118,13 +119,16 @@ def resolve(garment_vs, body_vs, body_fs, eps=COLLISION_EPS, max_depth=COLLISION
 
 
 @torch.no_grad()
-def intersection_report(garments, body_vs, body_fs, method='auto'):
+def intersection_report(garments, body_vs, body_fs, method='auto', penetration=False):
     """Crossing faces of posed garments, frame by frame.  `garments` maps a name to (vs [B,N,3] f32, faces [F,3] int64), the
     body is body_vs [B,V,3] f32 / body_fs [F,3] int64 (CUDA, one device, the same B).  Returns a list of B dicts:
     {name: {'body_faces': garment faces that cross a body face, 'self_faces': garment faces in a crossing pair of the
     garment with itself, 'faces': the garment's face count}, ..., 'between': {'<a>|<b>': {'faces_a', 'faces_b'}}} with one
     entry of 'between' per pair of garments (in the order given).  Crossing as in INTEGRATION.md §5 (strict: touching is
-    none); a garment without faces reports zeros.  The vertex repair above judges vertices; this judges faces."""
+    none); a garment without faces reports zeros.  The vertex repair above judges vertices; this judges faces.
+    `penetration`: every garment entry also gets 'inside_vertices', the garment vertices inside the (closed) body by
+    metrics.points_inside — also those of a patch that lies wholly inside, where no face crosses — and 'max_depth', the
+    largest distance of such a vertex to the body's surface (0. when there is none)."""
     from . import metrics
     names = list(garments)
     B = body_vs.shape[0]
@@ -138,11 +142,15 @@ def intersection_report(garments, body_vs, body_fs, method='auto'):
             vs, fs = garments[name]
             if fs.shape[0] == 0 or vs.shape[1] == 0:
                 frame[name] = {'body_faces': 0, 'self_faces': 0, 'faces': int(fs.shape[0])}
+                if penetration:
+                    frame[name].update(_penetration_entry(vs[b], body_vs[b], body_fs, method))
                 continue
             body = metrics.mesh_intersections(vs[b], fs, body_vs[b], body_fs, method=method)
             own = metrics.self_intersections(vs[b], fs, method=method)
             frame[name] = {'body_faces': int(body['faces_a'].shape[0]), 'self_faces': int(own['faces'].shape[0]),
                            'faces': int(fs.shape[0])}
+            if penetration:
+                frame[name].update(_penetration_entry(vs[b], body_vs[b], body_fs, method))
         for x, a in enumerate(names):
             for c in names[x + 1:]:
                 (va, fa), (vc, fc) = garments[a], garments[c]
@@ -154,6 +162,14 @@ def intersection_report(garments, body_vs, body_fs, method='auto'):
         frame['between'] = between
         report.append(frame)
     return report
+
+
+def _penetration_entry(vs, body_v, body_fs, method):
+    from . import metrics
+    if vs.shape[0] == 0:
+        return {'inside_vertices': 0, 'max_depth': 0.}
+    m = metrics.penetration(vs.contiguous(), body_v, body_fs, method=method)
+    return {'inside_vertices': m['count'], 'max_depth': m['max_depth']}
 
 
 def point_mesh_nearest_torch(p, verts, faces, chunk_elems=1 << 22):

@@ -260,7 +260,8 @@ def animation_meshes(loop, TmpVs_list, Tmpfs_list, root=None):
 
 def infer_garment_animation(loop, TmpVs_list, Tmpfs_list, poses_y, H, W, ratio, frame_ids, root=None, notcolor=False,
                             fix_collisions=False, collision_eps=None, collision_max_depth=None, collision_iters=None,
-                            collision_stats=None, chunk=COLOR_CHUNK, intersection_stats=None):
+                            collision_stats=None, chunk=COLOR_CHUNK, intersection_stats=None,
+                            intersection_penetration=False):
     """OptimGarmentNetwork.infer_garment_animation (:2729-2859): the garments driven by the poses `poses_y` [N,72] (or
     [N,24,3]) with the capture's averaged conditions (`animation_conditions`).  Returns (colors_list, imgs_list,
     defMeshVs_list) of numpy arrays, one entry per garment: `colors` uint8 [N,H,W,3] (None with `notcolor`), `imgs` uint8
@@ -272,7 +273,8 @@ def infer_garment_animation(loop, TmpVs_list, Tmpfs_list, poses_y, H, W, ratio, 
     `collision_eps`, `collision_max_depth`, `collision_iters`) before it is rendered and returned; `collision_stats` (a
     dict) then receives {garment: resolve's stats}.  The colour branch, which renders the implicit surface through the
     deformer, is not affected by the repair.  `intersection_stats` (a list) receives recmv.collide.intersection_report of
-    the meshes returned (after the repair when both are asked for), one entry per frame."""
+    the meshes returned (after the repair when both are asked for), one entry per frame; `intersection_penetration` is
+    its `penetration` option (the garment vertices inside the body and their largest depth)."""
     from . import collide
     device = TmpVs_list[0].device
     N = frame_ids.numel()
@@ -326,7 +328,8 @@ def infer_garment_animation(loop, TmpVs_list, Tmpfs_list, poses_y, H, W, ratio, 
         defMeshVs_list.append(defTmpVs.cpu().numpy())
         posed[name] = (defTmpVs, Tmpfs)
     if intersection_stats is not None:
-        intersection_stats.extend(collide.intersection_report(posed, body_vs, loop.tmpBodyFs))
+        intersection_stats.extend(collide.intersection_report(posed, body_vs, loop.tmpBodyFs,
+                                                              penetration=intersection_penetration))
     return colors_list, imgs_list, defMeshVs_list
 
 

@@ -5,6 +5,11 @@ whose tools/comparison_results.py stops after loading a mesh.
                     is iso_remesh.closest_point's exact search through it (recmv_closest_point_grid): the same bits
                     `.intersections(verts, faces)` / `.self_intersections()` the faces of another mesh / of its own that
                     cross its faces (recmv_mesh_intersect_grid_count / _fill, csrc/mesh_intersect.hip)
+                    `.segment_hits(p, q)` the first face every segment p -> q hits and the number of faces it hits
+                    (recmv_segment_mesh_grid, csrc/segment_mesh.hip)
+  segment_hits      the same through the grid or by the brute force (recmv_segment_mesh_brute)
+  points_inside     which points lie inside a closed mesh: the majority of three crossing parities
+  penetration       inside test plus the closest-point distance of the points inside: how deep a garment sinks into a body
   mesh_intersections, self_intersections   the crossing face pairs of two meshes / of one mesh, the faces involved and their
                     share of the mesh — through the grid or by the brute force (recmv_mesh_intersect_brute)
   sample_surface    loop.sample_fan_mesh's area-weighted surface samples, with the picked faces
@@ -24,6 +29,10 @@ reduction in float64 on the device, one read-back):
 Crossing (csrc/tri_tri.h): two faces cross when an edge of one properly pierces the other — every
 inequality strict, so touching, coplanar overlap, faces without area and NaN are no crossing.  Exact integers: the grid and
 the brute force give the same pairs.
+Segment hit (csrc/seg_tri.h): the segment pq hits a face when its endpoints lie strictly on opposite sides
+of the face's plane and the segment passes strictly inside the three edges — touching, a segment in the face's plane, a face
+without area, a segment without length and anything not finite are no hit; t = sp / (sp - sq) from the two plane
+determinants.  The grid and the brute force give the same bits.
 """
 import ctypes as C
 import math
@@ -49,6 +58,19 @@ DEFAULT_THRESHOLDS = (0.005, 0.01, 0.02)
 # every size until it exists (method='grid' is there for large meshes).
 INTERSECT_LANES = 8
 AUTO_GRID_MIN_PAIRS = 1 << 62
+# The segment query.  Both constants are to be read off profiles/segment_mesh_timing.json (tools/segment_mesh_timing.py;
+# DESIGN.md §8 "Segment queries"): the lanes per segment with the lowest summed time, and the smallest number of
+# segment-face tests S * F from which the grid (build + query) was faster than the brute force in every repeat.  NOT MEASURED:
+# that file has not been recorded on an MI355X yet, so the lanes are a guess (a segment's slab holds a handful of cells: one
+# lane has them all to itself, 64 would mostly idle) and the crossover is unreachable: 'auto' chooses the brute force at every
+# size until the file exists (method='grid' is there for large inputs).
+SEGMENT_LANES = 8
+AUTO_GRID_MIN_SEGMENT_TESTS = 1 << 62
+# points_inside: three fixed unit directions, mutually non-parallel, none along an axis or a diagonal of the axes (a ray along
+# a coordinate axis runs in the planes, edges and vertices of every axis-aligned mesh and would touch instead of cross)
+INSIDE_DIRECTIONS = ((0.5310514366481575, 0.6638142958101968, 0.5266260080094228),
+                     (-0.7072061522754515, 0.32773186373169966, 0.6264593232434947),
+                     (0.3090895268685805, -0.8275622816158767, 0.46861960525236396))
 
 
 def choose_grid(lo, hi, n_faces, faces_per_cell=FACES_PER_CELL, max_cells=MAX_CELLS):
@@ -168,6 +190,27 @@ class MeshGrid:
                                                      L.ptr(dist2), L.stream_ptr(dev)), "closest_point_grid")
         return face, point, dist2
 
+    def segment_hits(self, p, q, count=False, lanes=None):
+        """The faces of the grid's mesh the segments p [S,3] -> q [S,3] (f32, CUDA) hit: a dict with `face` [S] int64 (the hit
+        with the smallest t, ties to the lowest face id; -1: none), `t` [S] f32 (NaN: none), `point` [S,3] = p + t (q - p)
+        (NaN: none) and `count` [S] int32, the number of faces hit (None unless `count`; without it the walk may stop behind
+        the first hit).  `lanes` (1, 8 or 64 lanes per segment) chooses the launch shape; it does not change the result."""
+        p, q = _check_segments(p, q, self.verts.device)
+        S, dev = p.shape[0], p.device
+        face = L.scratch((S,), torch.int64, dev)
+        t = L.scratch((S,), torch.float32, dev)
+        cnt = L.scratch((S,), torch.int32, dev) if count else None
+        lanes = SEGMENT_LANES if lanes is None else int(lanes)
+        if lanes not in (1, 8, 64):
+            raise ValueError("lanes must be 1, 8 or 64 (got %r)" % (lanes,))
+        if S:
+            with L.device_guard(dev):
+                L.check(L.lib().recmv_segment_mesh_grid(L.ptr(p), L.ptr(q), S, L.ptr(self.verts), self.verts.shape[0],
+                                                        L.ptr(self.faces), self.faces.shape[0], L.ptr(self.offsets),
+                                                        L.ptr(self.entries), self.n_entries, self.origin, self.cell_size,
+                                                        *self.dims, lanes, int(bool(count)), L.ptr(face), L.ptr(t), L.ptr(cnt),
+                                                        L.stream_ptr(dev)), "segment_mesh_grid")
+        return _segment_result(p, q, face, t, cnt)
 
     def _crossings(self, verts, faces, self_mode, lanes):
         lanes = INTERSECT_LANES if lanes is None else int(lanes)
@@ -286,6 +329,95 @@ def self_intersections(v, f, method='auto', lanes=None):
         pairs, _ = _brute_crossings(v, f, v, f, True)
     faces, ratio = _involved(pairs.reshape(-1), f.shape[0])
     return {'pairs': pairs, 'n_pairs': int(pairs.shape[0]), 'faces': faces, 'ratio': ratio}
+
+
+def _check_segments(p, q, device=None):
+    for x, name in ((p, "p"), (q, "q")):
+        L.require_cuda(x, name)
+        if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 3:
+            raise ValueError("%s must be float32 of shape [S,3]" % name)
+    if p.shape != q.shape:
+        raise ValueError("p and q must have the same shape (got %s and %s)" % (tuple(p.shape), tuple(q.shape)))
+    if p.device != q.device or (device is not None and p.device != device):
+        raise ValueError("the segments and the mesh must be on one device")
+    return p.contiguous(), q.contiguous()
+
+
+def _segment_result(p, q, face, t, count):
+    return {'face': face, 't': t, 'point': p + t[:, None] * (q - p), 'count': count}
+
+
+def use_grid_for_segments(method, n_segments, n_faces):
+    if method not in ('auto', 'grid', 'brute'):
+        raise ValueError("method must be 'auto', 'grid' or 'brute' (got %r)" % (method,))
+    return method == 'grid' or (method == 'auto' and n_segments * n_faces >= AUTO_GRID_MIN_SEGMENT_TESTS)
+
+
+@torch.no_grad()
+def segment_hits(p, q, verts, faces, count=False, method='auto', lanes=None):
+    """MeshGrid.segment_hits for the mesh verts [V,3] f32 / faces [F,3] int64 (CUDA tensors on one device).  'grid': through a
+    MeshGrid; 'brute': every face (it always counts; `count` only decides whether the counts are returned); 'auto': by the
+    number of segment-face tests.  The same bits either way."""
+    _check_mesh(verts, faces)
+    p, q = _check_segments(p, q, verts.device)
+    if use_grid_for_segments(method, p.shape[0], faces.shape[0]):
+        return MeshGrid(verts, faces).segment_hits(p, q, count=count, lanes=lanes)
+    verts, faces = verts.contiguous(), faces.contiguous()
+    S, dev = p.shape[0], p.device
+    face = L.scratch((S,), torch.int64, dev)
+    t = L.scratch((S,), torch.float32, dev)
+    cnt = L.scratch((S,), torch.int32, dev)
+    if S:
+        with L.device_guard(dev):
+            L.check(L.lib().recmv_segment_mesh_brute(L.ptr(p), L.ptr(q), S, L.ptr(verts), verts.shape[0], L.ptr(faces),
+                                                     faces.shape[0], L.ptr(face), L.ptr(t), L.ptr(cnt), L.stream_ptr(dev)),
+                    "segment_mesh_brute")
+    return _segment_result(p, q, face, t, cnt if count else None)
+
+
+@torch.no_grad()
+def points_inside(points, verts, faces, method='auto'):
+    """Which of the points [P,3] f32 lie inside the mesh verts / faces (CUDA): bool [P].  Every point casts three segments
+    along INSIDE_DIRECTIONS, each ending beyond the mesh's bounding box (1.5 box diagonals plus the point's distance to the
+    box's centre away), and the result is the majority of the three parities of the number of faces crossed: a ray that
+    grazes an edge or a vertex (touching is no hit, so it may count one face too few or too many) is outvoted.  The mesh
+    is taken to be closed and free of self-intersections; a mesh that is not closed gives whatever the parities give.  A point
+    that is not finite is outside."""
+    _check_mesh(verts, faces)
+    L.require_cuda(points, "points")
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be float32 of shape [P,3]")
+    if points.device != verts.device:
+        raise ValueError("the points and the mesh must be on one device")
+    use_grid_for_segments(method, 0, 0)
+    P = points.shape[0]
+    if P == 0:
+        return torch.zeros(0, dtype=torch.bool, device=points.device)
+    points = points.contiguous()
+    lo, hi = verts.amin(0), verts.amax(0)
+    reach = 1.5 * (hi - lo).norm() + (points - 0.5 * (lo + hi)).norm(dim=1, keepdim=True)                    # [P,1]
+    dirs = torch.tensor(INSIDE_DIRECTIONS, dtype=torch.float32, device=points.device)                        # [3,3]
+    p = points[None].expand(3, P, 3).reshape(-1, 3)
+    q = (points[None] + reach[None] * dirs[:, None, :]).reshape(-1, 3)
+    grid = use_grid_for_segments(method, 3 * P, faces.shape[0])
+    cnt = segment_hits(p, q, verts, faces, count=True, method='grid' if grid else 'brute')['count'].reshape(3, P)
+    return (cnt & 1).sum(0) >= 2
+
+
+@torch.no_grad()
+def penetration(points, body_v, body_f, method='auto'):
+    """How deep the points [P,3] f32 (a garment's vertices) lie inside the closed mesh body_v / body_f: a dict with `inside`
+    [P] bool (points_inside), `depth` [P] f32 = the distance to the nearest point of the surface for the points inside and 0
+    for the others (the closest-point query of this module, unchanged), `count` (points inside), `max_depth` and `mean_depth`
+    (over the points inside; 0 when there are none) — python numbers, one read-back."""
+    inside = points_inside(points, body_v, body_f, method=method)
+    if points.shape[0] == 0:
+        return {'inside': inside, 'depth': points.new_zeros(0), 'count': 0, 'max_depth': 0., 'mean_depth': 0.}
+    _, _, dist2 = _nearest(points.contiguous(), body_v.contiguous(), body_f.contiguous(), method)
+    depth = torch.where(inside, dist2.sqrt(), torch.zeros_like(dist2))
+    n = inside.sum()
+    stats = torch.stack([n.double(), depth.max().double(), depth.double().sum() / n.clamp(min=1).double()]).cpu().tolist()
+    return {'inside': inside, 'depth': depth, 'count': int(stats[0]), 'max_depth': stats[1], 'mean_depth': stats[2]}
 
 
 def sample_surface(verts, faces, count, generator=None):
