@@ -20,6 +20,7 @@
 // FLOPs: 2*M*N*K.  With K=N=512 the arithmetic intensity is 128 FLOP/B >> 157e12/8e12, so every layer
 // is MFMA-bound, not HBM-bound.
 #include <mutex>
+#include <string>
 #include <unordered_map>
 #include <type_traits>
 #include <vector>
@@ -427,11 +428,30 @@ __global__ __launch_bounds__(kBlk) void gemm_nt_kernel(const float* __restrict__
 // exactly three: 94 + 64 accumulators): either one K-tile of 32 columns (SINGLE: the next tile waits in registers, two barriers per
 // tile) or two K-tiles of 16 columns; the epilogue goes through LDS in two halves of 64 rows.  Same products in the same order
 // as gemm_nt_kernel<2, true, ...>: bit-identical results.
-template <bool AMUL, int BKT, bool SINGLE, int MI, int NI>
+// 4 consecutive floats at a 4-byte aligned address, zero-filled past `limit`: whole groups as ONE load whose type promises only
+// dword alignment (the compiler picks the widest access the target allows for it), the row tail element by element
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ float4 load4_dword(const float* __restrict__ p, int limit) {
+  if (limit >= 4) {
+    const f32x4_a4 v = *reinterpret_cast<const f32x4_a4*>(p);
+    return make_float4(v.x, v.y, v.z, v.w);
+  }
+  return load4_guard(p, limit, false);
+}
+
+// the first `limit` of 4 consecutive elements, the others zero (they may be row padding: anything, NaN included)
+__device__ __forceinline__ float4 keep4(float4 v, int limit) {
+  return make_float4(limit > 0 ? v.x : 0.f, limit > 1 ? v.y : 0.f, limit > 2 ? v.z : 0.f, limit > 3 ? v.w : 0.f);
+}
+
+// SCAL: operands that miss the 16-byte conditions (a leading dimension or K that is no multiple of 4, an unaligned base) are staged with
+// loads that need only dword alignment (load4_dword), the last group of a row's K range element by element — the LDS image is that of the aligned kernel on a
+// zero-padded copy and the MFMA order is the same, so the results are bit-identical to it.
+template <bool AMUL, int BKT, bool SINGLE, int MI, int NI, bool SCAL = false>
 __global__ __launch_bounds__(kBlk, (MI * NI == 4 ? (BKT <= 16 ? 4 : 3) : 5))
 void gemm_nt_occ_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
                         const float* __restrict__ bias, float* __restrict__ C, int64_t ldc, int M, int N, int K, int act,
-                        float act_param, float out_scale, int nbm, int nbn, bool c_vec, AMul am) {
+                        float act_param, float out_scale, int nbm, int nbn, bool c_vec, AMul am, bool a_vec, bool b_vec) {
   constexpr int TBM = 64 * MI, TBN = 64 * NI;   // workgroup tile; 2 x 2 waves of (32 MI) x (32 NI)
   constexpr int LDKT = BKT + 4;                 // padded k stride (floats) of an LDS row
   constexpr int C4R = BKT / 4;                  // float4 per operand row and K-tile
@@ -461,6 +481,7 @@ void gemm_nt_occ_kernel(const float* __restrict__ A, int64_t lda, const float* _
   const float* pa[NLA];
   const float* pb[NLB];
   const float* py[NLA];
+  bool va[NLA], vb[NLB];
 #pragma unroll
   for (int r = 0; r < NLA; ++r) {
     const int idx = tid + kBlk * r;
@@ -468,6 +489,7 @@ void gemm_nt_occ_kernel(const float* __restrict__ A, int64_t lda, const float* _
     gm = gm < M ? gm : M - 1;                   // clamped rows are computed and never stored
     pa[r] = A + (int64_t)gm * lda + (idx % C4R) * 4;
     if (AMUL) py[r] = am.Y + (int64_t)gm * am.ldy + (idx % C4R) * 4;
+    va[r] = a_vec && gm < M - 1;                // SCAL: the last row's padding need not exist
   }
 #pragma unroll
   for (int r = 0; r < NLB; ++r) {
@@ -475,17 +497,34 @@ void gemm_nt_occ_kernel(const float* __restrict__ A, int64_t lda, const float* _
     int gn = n0 + idx / C4R;
     gn = gn < N ? gn : N - 1;
     pb[r] = B + (int64_t)gn * ldb + (idx % C4R) * 4;
+    vb[r] = b_vec && gn < N - 1;
   }
   auto gload = [&](int k0) {
 #pragma unroll
     for (int r = 0; r < NLA; ++r) {
-      const bool in = k0 + ((tid + kBlk * r) % C4R) * 4 < K;       // K % 4 == 0: a float4 is entirely inside or outside
+      const int k = k0 + ((tid + kBlk * r) % C4R) * 4;
+      if (SCAL) {
+        // 16-byte aligned rows (lda % 4 == 0, so the next row starts past K rounded up to 4): one 16-byte load, the elements past K dropped
+        ra[r] = va[r] ? keep4(k < K ? *reinterpret_cast<const float4*>(pa[r] + k0) : make_float4(0, 0, 0, 0), K - k)
+                      : load4_dword(pa[r] + k0, K - k);
+        if (AMUL && k < K)
+          ra[r] = amul4(ra[r], va[r] ? keep4(*reinterpret_cast<const float4*>(py[r] + k0), K - k)
+                                     : load4_dword(py[r] + k0, K - k), am);
+        continue;
+      }
+      const bool in = k < K;       // K % 4 == 0: a float4 is entirely inside or outside
       ra[r] = in ? *reinterpret_cast<const float4*>(pa[r] + k0) : make_float4(0, 0, 0, 0);
       if (AMUL && in) ra[r] = amul4(ra[r], *reinterpret_cast<const float4*>(py[r] + k0), am);
     }
 #pragma unroll
     for (int r = 0; r < NLB; ++r) {
-      const bool in = k0 + ((tid + kBlk * r) % C4R) * 4 < K;
+      const int k = k0 + ((tid + kBlk * r) % C4R) * 4;
+      if (SCAL) {
+        rb[r] = vb[r] ? keep4(k < K ? *reinterpret_cast<const float4*>(pb[r] + k0) : make_float4(0, 0, 0, 0), K - k)
+                      : load4_dword(pb[r] + k0, K - k);
+        continue;
+      }
+      const bool in = k < K;
       rb[r] = in ? *reinterpret_cast<const float4*>(pb[r] + k0) : make_float4(0, 0, 0, 0);
     }
   };
@@ -568,6 +607,180 @@ void gemm_nt_occ_kernel(const float* __restrict__ A, int64_t lda, const float* _
         break;
       default:
         nt_epilogue_rows<HR, TBN, RECMV_ACT_NONE>(Cs, bias, C, ldc, M, N, mh, n0, act_param, out_scale, c_vec, em);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------ NT, skinny shapes (f32 mode)
+// The networks end in layers of 1 or 3 outputs (SDF value, offset MLP).  On the MFMA kernels their forward is a 128-column tile of
+// which 1-3 columns are real, and their input gradient (K = 1 or 3) is a 32-deep K-tile of which 1-3 steps are real.  Both are
+// bounded by ONE pass over the [M, 512] side of the product, and both are done here on the VALU with the summation order of the
+// MFMA kernels, so every launch keeps the bits it had on them (the route depends on N and K only).
+//
+// Order of the MFMA kernels above: a v_mfma_f32_32x32x2_f32 is acc = fma(a[k1], b[k1], fma(a[k0], b[k0], acc)) with k0 from lanes
+// 0-31 and k1 from lanes 32-63, and the lanes 32-63 read their operands 4 columns further (khalf) — so within every group of 8
+// consecutive k the chain runs k = 0, 4, 1, 5, 2, 6, 3, 7, the groups in ascending order, columns past K as exact zeros.  The 64 x 32
+// kernel of the small launches keeps columns 0-15 and 16-31 of every K-tile on two chains and adds them before the bias; for K <= 4 that
+// makes no difference, for N <= 4 the thin kernel does the same (`halves`) at the row counts where that kernel had the launch.
+__device__ __forceinline__ float apply_act_rt(float z, int act, float p, float inv_p) {
+  switch (act) {
+    case RECMV_ACT_RELU: return apply_act<RECMV_ACT_RELU>(z, p, inv_p);
+    case RECMV_ACT_SOFTPLUS: return apply_act<RECMV_ACT_SOFTPLUS>(z, p, inv_p);
+    case RECMV_ACT_TANH: return apply_act<RECMV_ACT_TANH>(z, p, inv_p);
+    default: return z;
+  }
+}
+
+// N = NN <= 4 outputs, any K.  128 rows per workgroup, one thread per row: the [128][32] activation tile goes through LDS (coalesced
+// 128-byte row segments from HBM, 16-byte conflict-free reads: row stride 36 floats), the NN weight rows ride along as a [4][32]
+// tile that every lane reads at the same address.  VEC: 16-byte staging loads (aligned A, lda and K multiples of 4).
+constexpr int kThinRows = 128;
+template <int NN, bool VEC>
+__global__ __launch_bounds__(kThinRows) void gemm_nt_thin_n_kernel(const float* __restrict__ A, int64_t lda,
+                                                                   const float* __restrict__ B, int64_t ldb,
+                                                                   const float* __restrict__ bias, float* __restrict__ C,
+                                                                   int64_t ldc, int M, int K, int act, float act_param,
+                                                                   float out_scale, bool halves, AMul am) {
+  __shared__ __attribute__((aligned(16))) float As[kThinRows * LDK];
+  __shared__ __attribute__((aligned(16))) float Bs[4 * LDK];
+  const int tid = threadIdx.x;
+  const int m0 = blockIdx.x * kThinRows;
+  if (am.B2 && m0 >= am.split) {              // second weight set for the rows of the second net (see AMul)
+    B = am.B2;
+    bias = am.bias2;
+  }
+  constexpr int NLD = kThinRows * 8 / kThinRows;   // float4 per thread and K-tile
+  float4 ra[NLD];
+  float rb;
+  const float* pa[NLD];
+#pragma unroll
+  for (int r = 0; r < NLD; ++r) {
+    const int idx = tid + kThinRows * r;
+    int gm = m0 + (idx >> 3);
+    gm = gm < M ? gm : M - 1;                   // clamped rows are computed and never stored
+    pa[r] = A + (int64_t)gm * lda + (idx & 7) * 4;
+  }
+  const int bn = tid >> 5, bk = tid & 31;
+  auto gload = [&](int k0) {
+#pragma unroll
+    for (int r = 0; r < NLD; ++r) {
+      const int k = k0 + ((tid + kThinRows * r) & 7) * 4;
+      if (VEC)
+        ra[r] = k < K ? *reinterpret_cast<const float4*>(pa[r] + k0) : make_float4(0, 0, 0, 0);
+      else
+        ra[r] = load4_dword(pa[r] + k0, K - k);
+    }
+    rb = (bn < NN && k0 + bk < K) ? B[(int64_t)bn * ldb + k0 + bk] : 0.f;
+  };
+  auto lstore = [&]() {
+#pragma unroll
+    for (int r = 0; r < NLD; ++r) {
+      const int idx = tid + kThinRows * r;
+      *reinterpret_cast<float4*>(As + (idx >> 3) * LDK + (idx & 7) * 4) = ra[r];
+    }
+    Bs[bn * LDK + bk] = rb;
+  };
+  float acc[2][NN];
+#pragma unroll
+  for (int n = 0; n < NN; ++n) acc[0][n] = acc[1][n] = 0.f;
+  const int nk = (K + BK - 1) / BK;
+  gload(0);
+  lstore();
+  __syncthreads();
+  const float* as = As + tid * LDK;
+  for (int kt = 0; kt < nk; ++kt) {
+    if (kt + 1 < nk) gload((kt + 1) * BK);
+#pragma unroll
+    for (int kk = 0; kk < BK / 8; ++kk) {
+      const float4 a0 = *reinterpret_cast<const float4*>(as + kk * 8);
+      const float4 a1 = *reinterpret_cast<const float4*>(as + kk * 8 + 4);
+#pragma unroll
+      for (int n = 0; n < NN; ++n) {
+        const float4 b0 = *reinterpret_cast<const float4*>(Bs + n * LDK + kk * 8);
+        const float4 b1 = *reinterpret_cast<const float4*>(Bs + n * LDK + kk * 8 + 4);
+        const int h = (halves && kk >= BK / 16) ? 1 : 0;      // `halves`: columns 16-31 of every K-tile on a chain of their own
+        float s = acc[h][n];
+        s = fmaf(a0.x, b0.x, s);
+        s = fmaf(a1.x, b1.x, s);
+        s = fmaf(a0.y, b0.y, s);
+        s = fmaf(a1.y, b1.y, s);
+        s = fmaf(a0.z, b0.z, s);
+        s = fmaf(a1.z, b1.z, s);
+        s = fmaf(a0.w, b0.w, s);
+        s = fmaf(a1.w, b1.w, s);
+        acc[h][n] = s;
+      }
+    }
+    __syncthreads();                             // every thread has read the tile: the buffer may be overwritten
+    if (kt + 1 < nk) lstore();
+    __syncthreads();
+  }
+  const int gm = m0 + tid;
+  if (gm >= M) return;
+  const float inv_p = act_param != 0.f ? 1.f / act_param : 0.f;
+#pragma unroll
+  for (int n = 0; n < NN; ++n) {
+    const float z = halves ? acc[0][n] + acc[1][n] : acc[0][n];
+    float v = apply_act_rt(z + (bias ? bias[n] : 0.f), act, act_param, inv_p) * out_scale;
+    if (am.Y) v *= dact_y(am.Y[(int64_t)gm * am.ldy + n] * am.y_scale, am.act, am.param) * am.a_scale;
+    C[(int64_t)gm * ldc + n] = v;
+  }
+}
+
+// K = KK <= 4, any N: C = act(A' . B^T + bias) * out_scale as one element-wise pass, A' = A or (AMUL) A (.) act'(y_scale Y) a_scale.
+// 32 rows per workgroup; `cw` = 2^cw_log2 threads span the float4 column strips of a row (a wave writes 1 KB of a row at N = 512),
+// the other 256 / cw take turns over the rows; a thread keeps its 4 x KK weights in registers across its rows.
+constexpr int kThinKRows = 32;
+template <int KK, bool AMUL>
+__global__ __launch_bounds__(kBlk) void gemm_nt_thin_k_kernel(const float* __restrict__ A, int64_t lda,
+                                                              const float* __restrict__ B, int64_t ldb,
+                                                              const float* __restrict__ bias, float* __restrict__ C,
+                                                              int64_t ldc, int M, int N, int act, float act_param,
+                                                              float out_scale, int cw_log2, bool c_vec, AMul am) {
+  const int tid = threadIdx.x;
+  const int cw = 1 << cw_log2, cl = tid & (cw - 1), rsub = tid >> cw_log2, rstep = kBlk >> cw_log2;
+  const int m0 = blockIdx.x * kThinKRows;
+  const int mend = m0 + kThinKRows < M ? m0 + kThinKRows : M;
+  if (am.B2 && m0 >= am.split) {              // split is a multiple of 128 (or M): uniform over the 32 rows of a workgroup
+    B = am.B2;
+    bias = am.bias2;
+  }
+  const float inv_p = act_param != 0.f ? 1.f / act_param : 0.f;
+  for (int gn = cl * 4; gn < N; gn += cw * 4) {
+    float b[4][KK], bv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      bv[j] = (bias && gn + j < N) ? bias[gn + j] : 0.f;
+#pragma unroll
+      for (int k = 0; k < KK; ++k) b[j][k] = gn + j < N ? B[(int64_t)(gn + j) * ldb + k] : 0.f;
+    }
+    const bool full4 = c_vec && gn + 4 <= N;
+    for (int gm = m0 + rsub; gm < mend; gm += rstep) {
+      float a[KK];
+#pragma unroll
+      for (int k = 0; k < KK; ++k) {
+        a[k] = A[(int64_t)gm * lda + k];
+        if (AMUL) a[k] *= dact_y(am.Y[(int64_t)gm * am.ldy + k] * am.y_scale, am.act, am.param) * am.a_scale;
+      }
+      float o[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < KK; ++k) s = fmaf(a[k], b[j][k], s);
+        o[j] = apply_act_rt(s + bv[j], act, act_param, inv_p) * out_scale;
+      }
+      float4 v = make_float4(o[0], o[1], o[2], o[3]);
+      if (!AMUL && am.Y) v = emul4(v, am, gm, gn, N);
+      float* dst = C + (int64_t)gm * ldc + gn;
+      if (full4) {
+        *reinterpret_cast<float4*>(dst) = v;
+      } else {
+        dst[0] = v.x;
+        if (gn + 1 < N) dst[1] = v.y;
+        if (gn + 2 < N) dst[2] = v.z;
+        if (gn + 3 < N) dst[3] = v.w;
+      }
     }
   }
 }
@@ -1214,7 +1427,9 @@ __global__ __launch_bounds__(kBlk) void gemm_tn_kernel(const float* __restrict__
 // The same partial products with ONE 16-row K-tile in LDS (17 KB instead of 68 KB) and at most 128 registers: four workgroups
 // per CU instead of two (the same step the NT kernel took: a workgroup's barriers, prologue and register -> HBM epilogue are
 // covered by three neighbours instead of one).  f32 mode, aligned whole-float4 operands only; same summation order.
-template <int BKT>
+// SCAL: operands that miss the 16-byte conditions (a leading dimension that is no multiple of 4, an unaligned base) are staged with
+// loads that need only dword alignment (load4_dword), the last group of a row element by element; same LDS image and MFMA order as the aligned loads on a zero-padded copy.
+template <int BKT, bool SCAL = false>
 __global__ __launch_bounds__(kBlk, 4) void gemm_tn_occ_kernel(const float* __restrict__ A, int64_t lda,
                                                               const float* __restrict__ B, int64_t ldb,
                                                               float* __restrict__ P, int M, int N, int64_t K, int nbm,
@@ -1259,7 +1474,10 @@ __global__ __launch_bounds__(kBlk, 4) void gemm_tn_occ_kernel(const float* __res
       const int krow = idx >> 5, c4 = idx & 31;
       const int64_t k = k0 + krow;
       const int cm = m0 + c4 * 4, cn = n0 + c4 * 4;
-      if (whole) {
+      if (SCAL) {
+        ra[r] = k < kend ? load4_dword(A + k * lda + cm, M - cm) : make_float4(0, 0, 0, 0);
+        rb[r] = k < kend ? load4_dword(B + k * ldb + cn, N - cn) : make_float4(0, 0, 0, 0);
+      } else if (whole) {
         ra[r] = *reinterpret_cast<const float4*>(A + k * lda + cm);
         rb[r] = *reinterpret_cast<const float4*>(B + k * ldb + cn);
       } else {
@@ -1324,6 +1542,39 @@ __global__ __launch_bounds__(kBlk, 4) void gemm_tn_occ_kernel(const float* __res
       }
     }
   }
+}
+
+// Skinny TN products (f32 mode): one operand has NT <= 4 columns — the weight gradient of a last layer is NT weighted column sums of
+// X.  T [K, NT] is the thin operand, W [K, NW] the wide one; partial[split][t][w] (SWAP: [w][t], the thin operand is the product's
+// B) = sum over the split's rows of T[k][t] W[k][w].  One wave takes 64 columns of one split, a lane one column: coalesced 256-byte
+// row segments, 16 rows requested ahead of the chain that consumes them.
+// Summation order: per split ONE k-ascending fmaf chain from 0 — the order of the MFMA kernels above (k0 = even k from lanes 0-31,
+// k1 = odd k from lanes 32-63, rows past the split as exact zeros) with the same split lengths — then the splits in ascending order
+// by the split-K reduction below: the results are those of the MFMA route, bit for bit.
+template <int NT, bool SWAP>
+__global__ __launch_bounds__(kWave) void gemm_tn_thin_kernel(const float* __restrict__ T, int64_t ldt,
+                                                             const float* __restrict__ W, int64_t ldw,
+                                                             float* __restrict__ P, int NW, int64_t K, int64_t kchunk,
+                                                             int ntile) {
+  const int tile = blockIdx.x % ntile, split = blockIdx.x / ntile;
+  const int c = tile * kWave + threadIdx.x;
+  if (c >= NW) return;
+  const int64_t kbeg = (int64_t)split * kchunk;
+  int64_t kend = kbeg + kchunk;
+  if (kend > K) kend = K;
+  float acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = 0.f;
+  const float* w = W + c;
+#pragma unroll 16
+  for (int64_t k = kbeg; k < kend; ++k) {
+    const float wv = w[k * ldw];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = fmaf(T[k * ldt + t], wv, acc[t]);
+  }
+  float* Ps = P + (int64_t)split * NT * NW;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) Ps[SWAP ? (int64_t)c * NT + t : (int64_t)t * NW + c] = acc[t];
 }
 
 // C[m][n] = sum_s P[s][m][n]   (fixed order -> deterministic)
@@ -1474,6 +1725,13 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 constexpr int kNtLds = (2 * BM * LDK + 2 * BN * LDK) * 4;   // 73728 B (T=2); half of it for T=1
 constexpr int kTnLds = (4 * BK * LDM) * 4;                  // 67584 B
 
+// RECMV_GEMM_SKINNY=0 (read at every launch, so one process can time both): the routes before the skinny and the SCAL
+// kernels — the tool of profiles/r07_fallback_shapes_ab.txt.  RECMV_GEMM_OCC=0 switches them off as well.
+bool skinny_routes() {
+  const char* e = getenv("RECMV_GEMM_SKINNY");
+  return !(e && e[0] == '0');
+}
+
 bool tn_occ() {     // RECMV_GEMM_OCC=0: the two-workgroups-per-CU kernels (A/B)
   static const bool v = [] { const char* e = getenv("RECMV_GEMM_OCC"); return !(e && e[0] == '0'); }();
   return v;
@@ -1516,18 +1774,79 @@ static int launch_nt(const float* A, int64_t lda, const float* B, int64_t ldb, c
   return check_launch("gemm_nt");
 }
 
-template <bool AMUL, int BKT, bool SINGLE, int MI, int NI>
+// Profile slots: a launch of a kernel added after the 14 slots were fixed is recorded under the slot of the kernel that took the launch
+// before (SCAL and the skinny NT kernels: gemm_nt_kernel<2, false, AMUL> = 1 + 4 AMUL where the old route was that kernel), so the
+// per-step FLOP totals stay comparable.
+template <bool AMUL, int BKT, bool SINGLE, int MI, int NI, bool SCAL = false>
 static int launch_nt_occ(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C,
                          int64_t ldc, int64_t M, int64_t N, int64_t K, int act, float act_param, float out_scale,
-                         bool c_vec, const AMul& am, hipStream_t stream) {
+                         bool c_vec, const AMul& am, hipStream_t stream, bool a_vec = true, bool b_vec = true) {
   constexpr int lds_ops = (SINGLE ? 1 : 2) * 64 * (MI + NI) * (BKT + 4) * 4, lds_c = 32 * MI * (64 * NI + 4) * 4;
   constexpr int lds = lds_ops > lds_c ? lds_ops : lds_c;
   const int nbm = (int)ceil_div(M, 64 * MI), nbn = (int)ceil_div(N, 64 * NI);
-  ScopedLaunchTimer timer(AMUL ? 11 : (MI == 2 ? 9 : 10), (double)M, (double)N, (double)K, stream);
-  hipLaunchKernelGGL((gemm_nt_occ_kernel<AMUL, BKT, SINGLE, MI, NI>), dim3((unsigned)((int64_t)nbm * nbn)), dim3(kBlk), lds,
+  ScopedLaunchTimer timer(SCAL ? (AMUL ? 5 : 1) : (AMUL ? 11 : (MI == 2 ? 9 : 10)), (double)M, (double)N, (double)K, stream);
+  hipLaunchKernelGGL((gemm_nt_occ_kernel<AMUL, BKT, SINGLE, MI, NI, SCAL>), dim3((unsigned)((int64_t)nbm * nbn)), dim3(kBlk), lds,
                      stream, A, lda, B, ldb, bias, C, ldc, (int)M, (int)N, (int)K, act, act_param, out_scale, nbm, nbn, c_vec,
-                     am);
+                     am, a_vec, b_vec);
   return check_launch("gemm_nt(occ)");
+}
+
+// The profile slot of the kernel the parent routes give a launch (see dispatch_nt).
+static int nt_old_slot(int64_t M, int64_t N, bool fast, bool amul) {
+  const int64_t big_blocks = ceil_div(M, BM) * ceil_div(N, BN);
+  if (big_blocks >= 2 * kNumCU) {
+    if (!fast) return amul ? 5 : 1;
+    return amul ? 11 : (big_blocks >= 3600 ? 9 : 10);
+  }
+  if (ceil_div(M, 64) * ceil_div(N, 64) < (5 * kNumCU) / 2) return fast && !amul ? 12 : 13;
+  return 2 * (fast ? 1 : 0) + 4 * (amul ? 1 : 0);
+}
+
+template <int NN>
+static int launch_nt_thin_n(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C,
+                            int64_t ldc, int64_t M, int64_t K, int act, float act_param, float out_scale, bool vec,
+                            const AMul& am, int slot, hipStream_t stream) {
+  ScopedLaunchTimer timer(slot, (double)M, (double)NN, (double)K, stream);
+  const dim3 grid((unsigned)ceil_div(M, kThinRows));
+  // the summation order of the MFMA kernel that the tile choice of dispatch_nt gives a launch of this many rows: below 2.5 tiles of
+  // 64 x 64 per CU that is the 64 x 32 kernel, whose waves split every K-tile in two halves
+  const bool halves = ceil_div(M, 64) < (5 * kNumCU) / 2;
+  if (vec)
+    hipLaunchKernelGGL((gemm_nt_thin_n_kernel<NN, true>), grid, dim3(kThinRows), 0, stream, A, lda, B, ldb, bias, C, ldc, (int)M,
+                       (int)K, act, act_param, out_scale, halves, am);
+  else
+    hipLaunchKernelGGL((gemm_nt_thin_n_kernel<NN, false>), grid, dim3(kThinRows), 0, stream, A, lda, B, ldb, bias, C, ldc, (int)M,
+                       (int)K, act, act_param, out_scale, halves, am);
+  return check_launch("gemm_nt(thin n)");
+}
+
+template <int KK, bool AMUL>
+static int launch_nt_thin_k(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C,
+                            int64_t ldc, int64_t M, int64_t N, int act, float act_param, float out_scale, bool c_vec,
+                            const AMul& am, int slot, hipStream_t stream) {
+  ScopedLaunchTimer timer(slot, (double)M, (double)N, (double)KK, stream);
+  int cw_log2 = 0;
+  while (cw_log2 < 8 && (4ll << cw_log2) < N) ++cw_log2;      // threads across a row: the float4 strips of a row, at most 256
+  hipLaunchKernelGGL((gemm_nt_thin_k_kernel<KK, AMUL>), dim3((unsigned)ceil_div(M, kThinKRows)), dim3(kBlk), 0, stream, A, lda, B,
+                     ldb, bias, C, ldc, (int)M, (int)N, act, act_param, out_scale, cw_log2, c_vec, am);
+  return check_launch("gemm_nt(thin k)");
+}
+
+// RECMV_GEMM_SHAPES=1: every distinct (route, route before the skinny / SCAL kernels, shape, leading dimensions, alignment)
+// of a product of more than 1e8 multiply-adds that those kernels take or that still runs on a two-per-CU kernel is printed once to stderr — how the table of profiles/r07_fallback_shapes.txt was taken.
+static void log_shape(const char* route, const char* parent, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, const void* A, const void* B,
+                      bool amul, bool emul, bool seg) {
+  static const bool on = [] { const char* e = getenv("RECMV_GEMM_SHAPES"); return e && e[0] == '1'; }();
+  if (!on || (double)M * (double)N * (double)K < 1e8) return;
+  static std::mutex mu;
+  static std::unordered_map<std::string, int> seen;
+  char key[256];
+  snprintf(key, sizeof key, "%s (before: %s) M=%lld N=%lld K=%lld lda=%lld ldb=%lld A%%16=%d B%%16=%d amul=%d emul=%d seg=%d", route, parent,
+           (long long)M,
+           (long long)N, (long long)K, (long long)lda, (long long)ldb, (int)(reinterpret_cast<uintptr_t>(A) & 15),
+           (int)(reinterpret_cast<uintptr_t>(B) & 15), (int)amul, (int)emul, (int)seg);
+  std::lock_guard<std::mutex> lk(mu);
+  if (seen[key]++ == 0) fprintf(stderr, "[recmv shapes] %s\n", key);
 }
 
 // Weight matrices whose bf16 planes exist (recmv_b3_split), by the address the products get them under.
@@ -1603,7 +1922,39 @@ static int dispatch_nt(const float* A, int64_t lda, const float* B, int64_t ldb,
   const int64_t big_blocks = ceil_div(M, BM) * ceil_div(N, BN);
   // (which kernel families take the bf16x6 path in mode 1: recmv_set_b3_families, all of them by default)
   const bool bf3_big = g_gemm_mode == 1 && (g_b3_families & 1), bf3_mid = g_gemm_mode == 1 && (g_b3_families & 2);
-#define RECMV_NT(TT, FF)                                                                                          \
+  static const bool occ_env = [] { const char* e = getenv("RECMV_GEMM_OCC"); return !(e && e[0] == '0'); }();
+  const bool occ = occ_env, skinny = occ_env && skinny_routes();
+  const char* parent_route = big_blocks >= 2 * kNumCU ? (fast ? "nt_occ" : "nt_kernel<2,false>") : "below 512 large tiles";
+  // f32 mode, skinny shapes (the route is chosen by N and K alone; every launch keeps the bits its MFMA route gave it): the
+  // rank-K update for K <= 4, the per-row chains for N <= 4.  RECMV_GEMM_OCC=0 keeps the MFMA routes for the A/B.
+  if (g_gemm_mode == 0 && skinny && K >= 1 && K <= 4) {
+    const int slot = nt_old_slot(M, N, fast, AMUL);
+    log_shape("thin_k", parent_route, M, N, K, lda, ldb, A, B, AMUL, !AMUL && am.Y, am.B2 != nullptr);
+#define RECMV_TK(KK) \
+  case KK: return launch_nt_thin_k<KK, AMUL>(A, lda, B, ldb, bias, C, ldc, M, N, act, act_param, out_scale, c_vec, am, slot, s)
+    switch (K) {
+      RECMV_TK(1);
+      RECMV_TK(2);
+      RECMV_TK(3);
+      default: RECMV_TK(4);
+    }
+#undef RECMV_TK
+  }
+  if (g_gemm_mode == 0 && skinny && !AMUL && N <= 4) {
+    const int slot = nt_old_slot(M, N, fast, false);
+    const bool vec = a_vec && K % 4 == 0;
+    log_shape("thin_n", parent_route, M, N, K, lda, ldb, A, B, false, am.Y != nullptr, am.B2 != nullptr);
+#define RECMV_TN_(NN) \
+  case NN: return launch_nt_thin_n<NN>(A, lda, B, ldb, bias, C, ldc, M, K, act, act_param, out_scale, vec, am, slot, s)
+    switch (N) {
+      RECMV_TN_(1);
+      RECMV_TN_(2);
+      RECMV_TN_(3);
+      default: RECMV_TN_(4);
+    }
+#undef RECMV_TN_
+  }
+#define RECMV_NT(TT, FF)                                                                                         \
   ((TT == 2 ? bf3_big : bf3_mid) ? launch_nt<TT, FF, AMUL, true>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, \
                                                     a_vec, b_vec, c_vec, am, s)                                    \
                     : launch_nt<TT, FF, AMUL, false>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param,        \
@@ -1616,12 +1967,20 @@ static int dispatch_nt(const float* A, int64_t lda, const float* B, int64_t ldb,
     // for the largest launches, 64x128 tiles at five per CU below ~3600 large tiles (finer tail, measured crossover between
     // 90 k and 150 k rows at N = 512: profiles/r03_gemm_occupancy_variants.txt).  RECMV_GEMM_OCC=0 keeps the two-per-CU
     // kernel for the A/B.
-    static const bool occ = [] { const char* e = getenv("RECMV_GEMM_OCC"); return !(e && e[0] == '0'); }();
     if (fast && !bf3_big && occ) {
       if (big_blocks >= 3600)
         return launch_nt_occ<AMUL, 16, true, 2, 2>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, c_vec, am, s);
       return launch_nt_occ<AMUL, 16, true, 1, 2>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, c_vec, am, s);
     }
+    // unaligned operands or K % 4 != 0: the same kernels with staging loads that need only dword alignment (bit-identical to the
+    // aligned route on a zero-padded copy) instead of the two-per-CU kernel: 1.2-1.6x per launch (profiles/r07_fallback_shapes_ab.txt)
+    if (!fast && !bf3_big && skinny && K > 0) {
+      log_shape("occ_scal", parent_route, M, N, K, lda, ldb, A, B, AMUL, !AMUL && am.Y, am.B2 != nullptr);
+      if (big_blocks >= 3600)
+        return launch_nt_occ<AMUL, 16, true, 2, 2, true>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, c_vec, am, s, a_vec && lda >= K, b_vec);
+      return launch_nt_occ<AMUL, 16, true, 1, 2, true>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, c_vec, am, s, a_vec && lda >= K, b_vec);
+    }
+    if (!fast) log_shape("nt_kernel<2,false>", parent_route, M, N, K, lda, ldb, A, B, AMUL, !AMUL && am.Y, am.B2 != nullptr);
     return fast ? RECMV_NT(2, true) : RECMV_NT(2, false);
   }
   // 64x64 tiles unless they would give the CUs fewer than ~2.5 workgroups each: then 64x32 tiles (twice as many)
@@ -1805,16 +2164,49 @@ extern "C" int recmv_gemm_tn(const float* A, int64_t lda, const float* B, int64_
   {                          // the events bracket the product kernel alone (slot 8 = one kernel symbol); its reduction pass follows
   ScopedLaunchTimer timer(8, (double)M, (double)N, (double)K, s);
   const bool bf3_tn = g_gemm_mode == 1 && (g_b3_families & 4);
-  if (!bf3_tn && tn_occ() && a_vec && b_vec && lda >= ((M + 3) & ~3ll) && ldb >= ((N + 3) & ~3ll) && M >= 4 && N >= 4) {
+  if (!bf3_tn && tn_occ() && skinny_routes() && (M <= 4 || N <= 4)) {
+    // a skinny output (the weight gradient of a 1- or 3-output layer): weighted column sums on the VALU, the partials and the split
+    // lengths of the MFMA kernel that took the launch before (the aligned high-occupancy kernel rounds them to 16 rows, the other to 32)
+    const bool swap = M > 4;                     // the thin operand is B
+    const float* T = swap ? B : A;
+    const float* W = swap ? A : B;
+    const int64_t ldt = swap ? ldb : lda, ldw = swap ? lda : ldb, NT = swap ? N : M, NW = swap ? M : N;
+    const bool was_occ = a_vec && b_vec && lda >= ((M + 3) & ~3ll) && ldb >= ((N + 3) & ~3ll) && M >= 4 && N >= 4;
+    kchunk = ceil_div(ceil_div(K, splits), was_occ ? 16 : BK) * (was_occ ? 16 : BK);
+    const int ntile = (int)ceil_div(NW, kWave);
+    const dim3 grid((unsigned)((int64_t)ntile * splits));
+    log_shape("tn_thin", was_occ ? "tn_occ" : "tn_kernel<false>", M, N, K, lda, ldb, A, B, false, false, false);
+#define RECMV_TT(NTT, SW) \
+  hipLaunchKernelGGL((gemm_tn_thin_kernel<NTT, SW>), grid, dim3(kWave), 0, s, T, ldt, W, ldw, (float*)workspace, (int)NW, K, kchunk, ntile)
+#define RECMV_TT2(NTT) \
+  case NTT: if (swap) RECMV_TT(NTT, true); else RECMV_TT(NTT, false); break
+    switch (NT) {
+      RECMV_TT2(1);
+      RECMV_TT2(2);
+      RECMV_TT2(3);
+      default: RECMV_TT2(4);
+    }
+#undef RECMV_TT2
+#undef RECMV_TT
+  } else if (!bf3_tn && tn_occ() && a_vec && b_vec && lda >= ((M + 3) & ~3ll) && ldb >= ((N + 3) & ~3ll) && M >= 4 && N >= 4) {
     kchunk = ceil_div(ceil_div(K, splits), 16) * 16;
     hipLaunchKernelGGL(gemm_tn_occ_kernel<16>, dim3((unsigned)(nbm * nbn * splits)), dim3(kBlk), 2 * 16 * LDM * 4, s, A, lda,
+                       B, ldb, (float*)workspace, (int)M, (int)N, K, nbm, nbn, kchunk);
+  } else if (!bf3_tn && tn_occ() && skinny_routes() && M > 4 && N > 4) {
+    // a leading dimension that is no multiple of 4 or an unaligned base: the same kernel with staging loads that need only dword
+    // alignment (1.03-1.2x per launch)
+    // (split lengths rounded to 32 rows like the kernel it replaces, not to 16: the launch keeps its bits)
+    log_shape("tn_occ_scal", "tn_kernel<false>", M, N, K, lda, ldb, A, B, false, false, false);
+    hipLaunchKernelGGL((gemm_tn_occ_kernel<16, true>), dim3((unsigned)(nbm * nbn * splits)), dim3(kBlk), 2 * 16 * LDM * 4, s, A, lda,
                        B, ldb, (float*)workspace, (int)M, (int)N, K, nbm, nbn, kchunk);
   } else if (bf3_tn)
     hipLaunchKernelGGL(gemm_tn_kernel<true>, dim3((unsigned)(nbm * nbn * splits)), dim3(kBlk), kTnLds, s, A, lda, B,
                        ldb, (float*)workspace, (int)M, (int)N, K, nbm, nbn, kchunk, a_vec, b_vec);
-  else
+  else {
+    log_shape("tn_kernel<false>", "tn_kernel<false>", M, N, K, lda, ldb, A, B, false, false, false);
     hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3((unsigned)(nbm * nbn * splits)), dim3(kBlk), kTnLds, s, A, lda, B,
                        ldb, (float*)workspace, (int)M, (int)N, K, nbm, nbn, kchunk, a_vec, b_vec);
+  }
   rc = check_launch("gemm_tn");
   }
   if (rc) return rc;
