@@ -8,7 +8,7 @@
 //
 //   gemm_nt : C[M,N] = act(A[M,K] . B[N,K]^T + bias) * out_scale      forward  (A = activations, B = W)
 //                                                                     and dX = dZ . W^T^T (B = W^T copy)
-//   gemm_tn : C[M,N] = A[K,M]^T . B[K,N]                              dW = dZ^T . X  (K = #points), split-K
+//   gemm_tn : C[M,N] = A[K,M]^T . B[K,N]                              dW = dZ^T . X  (K = #points), split-K   (gemm_tn.hip)
 //
 // Tiling (wave64): 256 threads = 4 waves in 2x2, each wave owns a 64x64 sub-tile = 2x2 MFMA tiles
 // (64 accumulator VGPRs).  gemm_nt keeps both operands k-contiguous in LDS (row stride 36 floats: the
@@ -19,85 +19,22 @@
 //
 // FLOPs: 2*M*N*K.  With K=N=512 the arithmetic intensity is 128 FLOP/B >> 157e12/8e12, so every layer
 // is MFMA-bound, not HBM-bound.
+//
+// Which kernel a launch gets is decided in gemm_route.h (plan_nt), on the host and without HIP; this file launches what the plan names.
+// The profiler that brackets the product launches of both files (recmv_profile_*) is here too.
 #include <mutex>
 #include <string>
 #include <unordered_map>
 #include <type_traits>
 #include <vector>
-#include "common.h"
-// RECMV_LIBM_SOFTPLUS (an experiment build of tools/trajectory_seeds.py, never the product's): the activation through the
-// correctly-rounded-to-an-ulp library functions instead of the hardware exp2 / log2 units.
-#ifdef RECMV_LIBM_SOFTPLUS
-#define RECMV_EXPF(x) expf(x)
-#define RECMV_LOG1PF(t) log1pf(t)
-#else
-#define RECMV_EXPF(x) __expf(x)
-#define RECMV_LOG1PF(t) __logf(1.f + (t))
-#endif
-
 #include <algorithm>
+#include "gemm_common.h"
+#include "gemm_host.h"
 
 namespace recmv {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// ---- 3-way bf16 split of f32 operands (optional matrix mode "bf16x6") ------------------------------------------
-// x = h + m + l exactly, each piece a bf16 (round-to-nearest at every step: |m| <= 2^-9 |x|, |l| <= 2^-17 |x|).
-// A product x*y is then formed from the six piece products of weight >= 2^-18 (hh, hm, mh, hl, lh, mm) on the bf16
-// matrix pipe (16x the f32 matrix rate) with f32 accumulation; the dropped products are <= 2^-25 relative, below
-// f32 rounding.  Each piece product is exact in f32, so the result differs from the f32 MFMA only by the order of
-// the f32 accumulation.
-struct Pieces {
-  bf16x8 h, m, l;
-};
-// Two f32 -> one packed pair of bf16, round to nearest even.  Default: the hardware conversion (v_cvt_pk_bf16_f32, new in gfx950).
-// -DRECMV_SPLIT_INT: the same rounding in integer arithmetic (finite operands; the A/B build of tools/def_regu_stress.py).
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-#ifdef RECMV_SPLIT_INT
-  unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-  ua += 0x7fffu + ((ua >> 16) & 1u);
-  ub += 0x7fffu + ((ub >> 16) & 1u);
-  return (ua >> 16) | (ub & 0xffff0000u);
-#else
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-#endif
-}
-__device__ __forceinline__ void split2(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-  h = pack_bf16(x0, x1);
-  const f32x2 r = {x0 - __uint_as_float(h << 16), x1 - __uint_as_float(h & 0xffff0000u)};
-  m = pack_bf16(r.x, r.y);
-  const f32x2 q = {r.x - __uint_as_float(m << 16), r.y - __uint_as_float(m & 0xffff0000u)};
-  l = pack_bf16(q.x, q.y);
-}
-__device__ __forceinline__ Pieces split8(float4 a, float4 b) {
-  unsigned h[4], m[4], l[4];
-  split2(a.x, a.y, h[0], m[0], l[0]);
-  split2(a.z, a.w, h[1], m[1], l[1]);
-  split2(b.x, b.y, h[2], m[2], l[2]);
-  split2(b.z, b.w, h[3], m[3], l[3]);
-  Pieces p;
-  p.h = __builtin_bit_cast(bf16x8, (u32x4){h[0], h[1], h[2], h[3]});
-  p.m = __builtin_bit_cast(bf16x8, (u32x4){m[0], m[1], m[2], m[3]});
-  p.l = __builtin_bit_cast(bf16x8, (u32x4){l[0], l[1], l[2], l[3]});
-  return p;
-}
-
-constexpr int BM = 128, BN = 128, BK = 32;   // large tile (and the TN kernel's tile)
-constexpr int kBlk = 256;
 constexpr int LDK = BK + 4;    // NT: padded k stride (floats) of an LDS row
-constexpr int LDM = BM + 4;    // TN: padded m stride (floats) of an LDS k-row
-
-__device__ __forceinline__ int64_t xcd_remap(int64_t b, int64_t nb) {
-  const int64_t per = nb / kNumXCD;
-  if (b >= per * kNumXCD) return b;
-  return (b % kNumXCD) * per + b / kNumXCD;
-}
 
 // Activations of the fused epilogue.  ACT is a compile-time constant inside the epilogue loops.
 //   softplus(beta): torch semantics (x*beta > 20 ? x : log1p(exp(x*beta))/beta), evaluated as
@@ -155,20 +92,6 @@ __device__ __forceinline__ float4 amul4(float4 a, float4 y, const AMul& m) {
   a.z *= dact_y(y.z * m.y_scale, m.act, m.param) * m.a_scale;
   a.w *= dact_y(y.w * m.y_scale, m.act, m.param) * m.a_scale;
   return a;
-}
-
-// 4 consecutive floats of a row, zero-filled past `limit` (elements left in the row).
-__device__ __forceinline__ float4 load4_guard(const float* __restrict__ p, int64_t limit, bool vec_ok) {
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (limit >= 4 && vec_ok) {
-    v = *reinterpret_cast<const float4*>(p);
-  } else {
-    if (limit > 0) v.x = p[0];
-    if (limit > 1) v.y = p[1];
-    if (limit > 2) v.z = p[2];
-    if (limit > 3) v.w = p[3];
-  }
-  return v;
 }
 
 // ------------------------------------------------------------------------------------------ NT
@@ -428,21 +351,6 @@ __global__ __launch_bounds__(kBlk) void gemm_nt_kernel(const float* __restrict__
 // exactly three: 94 + 64 accumulators): either one K-tile of 32 columns (SINGLE: the next tile waits in registers, two barriers per
 // tile) or two K-tiles of 16 columns; the epilogue goes through LDS in two halves of 64 rows.  Same products in the same order
 // as gemm_nt_kernel<2, true, ...>: bit-identical results.
-// 4 consecutive floats at a 4-byte aligned address, zero-filled past `limit`: whole groups as ONE load whose type promises only
-// dword alignment (the compiler picks the widest access the target allows for it), the row tail element by element
-typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-__device__ __forceinline__ float4 load4_dword(const float* __restrict__ p, int limit) {
-  if (limit >= 4) {
-    const f32x4_a4 v = *reinterpret_cast<const f32x4_a4*>(p);
-    return make_float4(v.x, v.y, v.z, v.w);
-  }
-  return load4_guard(p, limit, false);
-}
-
-// the first `limit` of 4 consecutive elements, the others zero (they may be row padding: anything, NaN included)
-__device__ __forceinline__ float4 keep4(float4 v, int limit) {
-  return make_float4(limit > 0 ? v.x : 0.f, limit > 1 ? v.y : 0.f, limit > 2 ? v.z : 0.f, limit > 3 ? v.w : 0.f);
-}
 
 // SCAL: operands that miss the 16-byte conditions (a leading dimension or K that is no multiple of 4, an unaligned base) are staged with
 // loads that need only dword alignment (load4_dword), the last group of a row's K range element by element — the LDS image is that of the aligned kernel on a
@@ -1274,403 +1182,16 @@ __global__ __launch_bounds__(kBlk) void gemm_nt_narrow_kernel(const float* __res
   }
 }
 
-// ------------------------------------------------------------------------------------------ TN
-// partial[split][M][N] = sum over k in the split's range of A[k][m]*B[k][n]
-template <bool BF3>
-__global__ __launch_bounds__(kBlk) void gemm_tn_kernel(const float* __restrict__ A, int64_t lda,
-                                                       const float* __restrict__ B, int64_t ldb,
-                                                       float* __restrict__ P, int M, int N, int64_t K, int nbm,
-                                                       int nbn, int64_t kchunk, bool a_vec, bool b_vec) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* As = smem;                       // [2][BK][LDM]
-  float* Bs = smem + 2 * BK * LDM;        // [2][BK][LDM]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int tiles = nbm * nbn;
-  const int split = blockIdx.x / tiles, tile = blockIdx.x % tiles;
-  const int tile_m = tile / nbn, tile_n = tile % nbn;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int64_t kbeg = (int64_t)split * kchunk;
-  int64_t kend = kbeg + kchunk;
-  if (kend > K) kend = K;
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-  // staging: BK rows x 128 floats = 1024 float4 per operand; krow = idx/32, c4 = idx%32
-  float4 ra[4], rb[4];
-  // `fast` (uniform): 16-byte aligned operands whose widths are multiples of 4 — a float4 of a row is entirely inside or
-  // outside the matrix, so every staging load is one unconditional 16-byte load (an outside one reads a clamped address and
-  // is zeroed); whole tiles (the common case: M, N multiples of 128, K-tile inside the split) skip the zeroing too.
-  // Otherwise the element-guarded loader, whose per-lane branches keep the eight loads of a K-tile from overlapping.
-  const bool fast = a_vec && b_vec && (M & 3) == 0 && (N & 3) == 0 && M >= 4 && N >= 4;
-  const bool whole_mn = m0 + BM <= M && n0 + BN <= N;
-  auto gload = [&](int64_t k0) {
-    if (fast) {
-      const bool whole = whole_mn && k0 + BK <= kend;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int idx = tid + kBlk * r;
-        const int krow = idx >> 5, c4 = idx & 31;
-        const int64_t k = k0 + krow;
-        const int cm = m0 + c4 * 4, cn = n0 + c4 * 4;
-        if (whole) {
-          ra[r] = *reinterpret_cast<const float4*>(A + k * lda + cm);
-          rb[r] = *reinterpret_cast<const float4*>(B + k * ldb + cn);
-        } else {
-          const bool kin = k < kend, ain = kin && cm < M, bin = kin && cn < N;
-          const int64_t kc = kin ? k : kend - 1;
-          float4 a = *reinterpret_cast<const float4*>(A + kc * lda + (cm < M ? cm : M - 4));
-          float4 b = *reinterpret_cast<const float4*>(B + kc * ldb + (cn < N ? cn : N - 4));
-          ra[r] = make_float4(ain ? a.x : 0.f, ain ? a.y : 0.f, ain ? a.z : 0.f, ain ? a.w : 0.f);
-          rb[r] = make_float4(bin ? b.x : 0.f, bin ? b.y : 0.f, bin ? b.z : 0.f, bin ? b.w : 0.f);
-        }
-      }
-      return;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int idx = tid + kBlk * r;
-      const int krow = idx >> 5, c4 = idx & 31;
-      const int64_t k = k0 + krow;
-      const int cm = m0 + c4 * 4, cn = n0 + c4 * 4;
-      ra[r] = (k < kend) ? load4_guard(A + k * lda + cm, M - cm, a_vec) : make_float4(0, 0, 0, 0);
-      rb[r] = (k < kend) ? load4_guard(B + k * ldb + cn, N - cn, b_vec) : make_float4(0, 0, 0, 0);
-    }
-  };
-  auto lstore = [&](int buf) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int idx = tid + kBlk * r;
-      const int krow = idx >> 5, c4 = idx & 31;
-      *reinterpret_cast<float4*>(As + (buf * BK + krow) * LDM + c4 * 4) = ra[r];
-      *reinterpret_cast<float4*>(Bs + (buf * BK + krow) * LDM + c4 * 4) = rb[r];
-    }
-  };
-
-  const int nk = (int)((kend - kbeg + BK - 1) / BK);
-  if (nk > 0) {
-    gload(kbeg);
-    lstore(0);
-  }
-  __syncthreads();
-  const int acol = wm * 64 + (lane & 31), bcol = wn * 64 + (lane & 31), kh = lane >> 5;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) gload(kbeg + (int64_t)(kt + 1) * BK);
-    if (BF3) {
-      // bf16x6 (see split2): a lane's 8 consecutive k of column m are 8 rows of the k-major LDS tile
-      const float* as = As + (buf * BK + 8 * kh) * LDM + acol;
-      const float* bs = Bs + (buf * BK + 8 * kh) * LDM + bcol;
-#pragma unroll
-      for (int ks = 0; ks < BK / 16; ++ks) {
-        Pieces pa[2], pb[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const float* ap = as + ks * 16 * LDM + 32 * i;
-          const float* bp = bs + ks * 16 * LDM + 32 * i;
-          pa[i] = split8(make_float4(ap[0], ap[LDM], ap[2 * LDM], ap[3 * LDM]),
-                         make_float4(ap[4 * LDM], ap[5 * LDM], ap[6 * LDM], ap[7 * LDM]));
-          pb[i] = split8(make_float4(bp[0], bp[LDM], bp[2 * LDM], bp[3 * LDM]),
-                         make_float4(bp[4 * LDM], bp[5 * LDM], bp[6 * LDM], bp[7 * LDM]));
-        }
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni) {
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[mi].h, pb[ni].l, acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[mi].l, pb[ni].h, acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[mi].m, pb[ni].m, acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[mi].h, pb[ni].m, acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[mi].m, pb[ni].h, acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[mi].h, pb[ni].h, acc[mi][ni], 0, 0, 0);
-          }
-      }
-    } else {
-    const float* as = As + (buf * BK + kh) * LDM + acol;
-    const float* bs = Bs + (buf * BK + kh) * LDM + bcol;
-#pragma unroll
-    for (int k2 = 0; k2 < BK / 2; ++k2) {
-      const float a0 = as[k2 * 2 * LDM], a1 = as[k2 * 2 * LDM + 32];
-      const float b0 = bs[k2 * 2 * LDM], b1 = bs[k2 * 2 * LDM + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    }
-    if (kt + 1 < nk) lstore(buf ^ 1);
-    __syncthreads();
-  }
-
-  float* Ps = P + (int64_t)split * M * N;
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int gn = n0 + wn * 64 + ni * 32 + (lane & 31);
-    if (gn >= N) continue;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int gm = m0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (gm < M) Ps[(int64_t)gm * N + gn] = acc[mi][ni][r];
-      }
-    }
-  }
-}
-
-// The same partial products with ONE 16-row K-tile in LDS (17 KB instead of 68 KB) and at most 128 registers: four workgroups
-// per CU instead of two (the same step the NT kernel took: a workgroup's barriers, prologue and register -> HBM epilogue are
-// covered by three neighbours instead of one).  f32 mode, aligned whole-float4 operands only; same summation order.
-// SCAL: operands that miss the 16-byte conditions (a leading dimension that is no multiple of 4, an unaligned base) are staged with
-// loads that need only dword alignment (load4_dword), the last group of a row element by element; same LDS image and MFMA order as the aligned loads on a zero-padded copy.
-template <int BKT, bool SCAL = false>
-__global__ __launch_bounds__(kBlk, 4) void gemm_tn_occ_kernel(const float* __restrict__ A, int64_t lda,
-                                                              const float* __restrict__ B, int64_t ldb,
-                                                              float* __restrict__ P, int M, int N, int64_t K, int nbm,
-                                                              int nbn, int64_t kchunk) {
-  constexpr int NLD = BKT * 32 / kBlk;    // float4 per thread per operand tile
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* As = smem;                       // [BKT][LDM]
-  float* Bs = smem + BKT * LDM;           // [BKT][LDM]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int tiles = nbm * nbn;
-  // consecutive workgroup ids go round the 8 XCDs: keep ALL output tiles of a split (they read the same operand rows) on one XCD,
-  // so that its L2 fetches those rows once — XCD x takes the splits x, x + 8, ...
-  int split = blockIdx.x / tiles, tile = blockIdx.x % tiles;
-  const int splits = gridDim.x / tiles;
-  if (splits % kNumXCD == 0) {
-    const int x = blockIdx.x % kNumXCD, j = blockIdx.x / kNumXCD;
-    split = x + kNumXCD * (j / tiles);
-    tile = j % tiles;
-  }
-  const int tile_m = tile / nbn, tile_n = tile % nbn;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int64_t kbeg = (int64_t)split * kchunk;
-  int64_t kend = kbeg + kchunk;
-  if (kend > K) kend = K;
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-  float4 ra[NLD], rb[NLD];
-  const bool whole_mn = m0 + BM <= M && n0 + BN <= N;
-  auto gload = [&](int64_t k0) {
-    const bool whole = whole_mn && k0 + BKT <= kend;
-#pragma unroll
-    for (int r = 0; r < NLD; ++r) {
-      const int idx = tid + kBlk * r;
-      const int krow = idx >> 5, c4 = idx & 31;
-      const int64_t k = k0 + krow;
-      const int cm = m0 + c4 * 4, cn = n0 + c4 * 4;
-      if (SCAL) {
-        ra[r] = k < kend ? load4_dword(A + k * lda + cm, M - cm) : make_float4(0, 0, 0, 0);
-        rb[r] = k < kend ? load4_dword(B + k * ldb + cn, N - cn) : make_float4(0, 0, 0, 0);
-      } else if (whole) {
-        ra[r] = *reinterpret_cast<const float4*>(A + k * lda + cm);
-        rb[r] = *reinterpret_cast<const float4*>(B + k * ldb + cn);
-      } else {
-        const bool kin = k < kend, ain = kin && cm < M, bin = kin && cn < N;
-        const int64_t kc = kin ? k : kend - 1;
-        // widths that are no multiple of 4 (the skip layer's 473 columns inside a 512-wide buffer): the launcher has checked that
-        // the row strides cover the rounded-up widths, so the last float4 of a row reads up to 3 elements of padding — they only
-        // reach output rows / columns >= M / N, which are never stored
-        float4 a = *reinterpret_cast<const float4*>(A + kc * lda + (cm < M ? cm : (M - 1) & ~3));
-        float4 b = *reinterpret_cast<const float4*>(B + kc * ldb + (cn < N ? cn : (N - 1) & ~3));
-        ra[r] = make_float4(ain ? a.x : 0.f, ain ? a.y : 0.f, ain ? a.z : 0.f, ain ? a.w : 0.f);
-        rb[r] = make_float4(bin ? b.x : 0.f, bin ? b.y : 0.f, bin ? b.z : 0.f, bin ? b.w : 0.f);
-      }
-    }
-  };
-  auto lstore = [&]() {
-#pragma unroll
-    for (int r = 0; r < NLD; ++r) {
-      const int idx = tid + kBlk * r;
-      const int krow = idx >> 5, c4 = idx & 31;
-      *reinterpret_cast<float4*>(As + krow * LDM + c4 * 4) = ra[r];
-      *reinterpret_cast<float4*>(Bs + krow * LDM + c4 * 4) = rb[r];
-    }
-  };
-
-  const int nk = (int)((kend - kbeg + BKT - 1) / BKT);
-  if (nk > 0) {
-    gload(kbeg);
-    lstore();
-  }
-  __syncthreads();
-  const int acol = wm * 64 + (lane & 31), bcol = wn * 64 + (lane & 31), kh = lane >> 5;
-  const float* as = As + kh * LDM + acol;
-  const float* bs = Bs + kh * LDM + bcol;
-  for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 1 < nk) gload(kbeg + (int64_t)(kt + 1) * BKT);
-#pragma unroll
-    for (int k2 = 0; k2 < BKT / 2; ++k2) {
-      const float a0 = as[k2 * 2 * LDM], a1 = as[k2 * 2 * LDM + 32];
-      const float b0 = bs[k2 * 2 * LDM], b1 = bs[k2 * 2 * LDM + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    __syncthreads();
-    if (kt + 1 < nk) lstore();
-    __syncthreads();
-  }
-
-  float* Ps = P + (int64_t)split * M * N;
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int gn = n0 + wn * 64 + ni * 32 + (lane & 31);
-    if (gn >= N) continue;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int gm = m0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (gm < M) Ps[(int64_t)gm * N + gn] = acc[mi][ni][r];
-      }
-    }
-  }
-}
-
-// Skinny TN products (f32 mode): one operand has NT <= 4 columns — the weight gradient of a last layer is NT weighted column sums of
-// X.  T [K, NT] is the thin operand, W [K, NW] the wide one; partial[split][t][w] (SWAP: [w][t], the thin operand is the product's
-// B) = sum over the split's rows of T[k][t] W[k][w].  One wave takes 64 columns of one split, a lane one column: coalesced 256-byte
-// row segments, 16 rows requested ahead of the chain that consumes them.
-// Summation order: per split ONE k-ascending fmaf chain from 0 — the order of the MFMA kernels above (k0 = even k from lanes 0-31,
-// k1 = odd k from lanes 32-63, rows past the split as exact zeros) with the same split lengths — then the splits in ascending order
-// by the split-K reduction below: the results are those of the MFMA route, bit for bit.
-template <int NT, bool SWAP>
-__global__ __launch_bounds__(kWave) void gemm_tn_thin_kernel(const float* __restrict__ T, int64_t ldt,
-                                                             const float* __restrict__ W, int64_t ldw,
-                                                             float* __restrict__ P, int NW, int64_t K, int64_t kchunk,
-                                                             int ntile) {
-  const int tile = blockIdx.x % ntile, split = blockIdx.x / ntile;
-  const int c = tile * kWave + threadIdx.x;
-  if (c >= NW) return;
-  const int64_t kbeg = (int64_t)split * kchunk;
-  int64_t kend = kbeg + kchunk;
-  if (kend > K) kend = K;
-  float acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) acc[t] = 0.f;
-  const float* w = W + c;
-#pragma unroll 16
-  for (int64_t k = kbeg; k < kend; ++k) {
-    const float wv = w[k * ldw];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = fmaf(T[k * ldt + t], wv, acc[t]);
-  }
-  float* Ps = P + (int64_t)split * NT * NW;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) Ps[SWAP ? (int64_t)c * NT + t : (int64_t)t * NW + c] = acc[t];
-}
-
-// C[m][n] = sum_s P[s][m][n]   (fixed order -> deterministic)
-__global__ __launch_bounds__(kBlk) void splitk_reduce_kernel(const float* __restrict__ P, float* __restrict__ C,
-                                                             int64_t ldc, int M, int N, int splits) {
-  const int64_t total = (int64_t)M * N;
-  for (int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlk) {
-    float s = 0.f;
-    for (int sp = 0; sp < splits; ++sp) s += P[(int64_t)sp * total + i];
-    C[(i / N) * ldc + (i % N)] = s;
-  }
-}
-
-// The same sums in the same order, four columns per lane and eight partial tiles requested before the first is added: the
-// scalar loop above asks for one 4-byte value per split and lane at a time (64 dependent round trips for 64 splits).
-__global__ __launch_bounds__(kBlk) void splitk_reduce4_kernel(const float4* __restrict__ P, float* __restrict__ C,
-                                                              int64_t ldc, int M, int N, int splits) {
-  const int64_t total4 = (int64_t)M * N / 4;
-  for (int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x; i < total4; i += (int64_t)gridDim.x * kBlk) {
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    int sp = 0;
-    for (; sp + 8 <= splits; sp += 8) {
-      float4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = P[(int64_t)(sp + u) * total4 + i];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        s.x += v[u].x;
-        s.y += v[u].y;
-        s.z += v[u].z;
-        s.w += v[u].w;
-      }
-    }
-    for (; sp < splits; ++sp) {
-      const float4 v = P[(int64_t)sp * total4 + i];
-      s.x += v.x;
-      s.y += v.y;
-      s.z += v.z;
-      s.w += v.w;
-    }
-    const int64_t e = i * 4;
-    *reinterpret_cast<float4*>(C + (e / N) * ldc + (e % N)) = s;
-  }
-}
-
-// ------------------------------------------------------------------------------------------ posenc
-struct PeWeights {
-  float w[32];  // by-value kernel argument: no H2D copy, graph-capturable
-};
-__global__ __launch_bounds__(kBlk) void posenc_kernel(const float* __restrict__ x, int64_t ldx,
-                                                      float* __restrict__ out, int64_t ldo, int64_t ldo_fill,
-                                                      int64_t P, int L, PeWeights w, float out_scale) {
-  const int nf = 1 + 2 * L;  // identity + (sin,cos) per band
-  const int64_t total = P * nf;
-  for (int64_t e = (int64_t)blockIdx.x * kBlk + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlk) {
-    const int64_t p = e / nf;
-    const int f = (int)(e % nf);
-    const float x0 = x[p * ldx], x1 = x[p * ldx + 1], x2 = x[p * ldx + 2];
-    float* o = out + p * ldo + 3 * f;
-    if (f == 0) {
-      o[0] = x0 * out_scale;
-      o[1] = x1 * out_scale;
-      o[2] = x2 * out_scale;
-      for (int64_t c = 3 * nf; c < ldo_fill; ++c) out[p * ldo + c] = 0.f;
-    } else {
-      const int band = (f - 1) >> 1;
-      const float freq = (float)(1 << band);  // 2**linspace(0, L-1, L): exact powers of two
-      const float wt = w.w[f - 1];
-      float v0, v1, v2;
-      if ((f - 1) & 1) {
-        v0 = cosf(x0 * freq); v1 = cosf(x1 * freq); v2 = cosf(x2 * freq);
-      } else {
-        v0 = sinf(x0 * freq); v1 = sinf(x1 * freq); v2 = sinf(x2 * freq);
-      }
-      o[0] = wt * v0 * out_scale;
-      o[1] = wt * v1 * out_scale;
-      o[2] = wt * v2 * out_scale;
-    }
-  }
-}
-
 // ---- optional per-launch HIP-event timing of the MFMA kernels (bench.py's roofline object) ----------------------
 // Events are recorded on the stream the kernel is launched on, immediately before and after the launch.
-struct LaunchRec {
-  hipEvent_t a, b;
-  int variant;
-  double flops, bytes;
-};
 struct Profiler {
   bool on = false;
   double min_flops = 0.0;          // launches below this are counted but not bracketed by events
-  double untimed[14][2] = {};      // [variant][launches, flops]
+  double untimed[route::kNumSlots][2] = {};      // [variant][launches, flops]
   std::vector<LaunchRec> recs;
   std::vector<hipEvent_t> pool;
-  double large[14][3] = {};        // of the last recmv_profile_end: launches / seconds / FLOP of the bracketed launches of >= 4 GFLOP
-  double timed_bytes[14] = {};     // of the last recmv_profile_end: algorithmic bytes (4 (MK + NK + MN)) of the bracketed launches, per variant
+  double large[route::kNumSlots][3] = {};        // of the last recmv_profile_end: launches / seconds / FLOP of the bracketed launches of >= 4 GFLOP
+  double timed_bytes[route::kNumSlots] = {};     // of the last recmv_profile_end: algorithmic bytes (4 (MK + NK + MN)) of the bracketed launches, per variant
   double busy_union_s = 0.0, busy_span_s = 0.0;   // of the last recmv_profile_end: union of the bracketed intervals, first start -> last end
   std::mutex mu;        // autograd's backward thread launches too
   hipEvent_t get() {
@@ -1687,78 +1208,87 @@ struct Profiler {
 };
 Profiler g_prof;
 
-struct ScopedLaunchTimer {
-  LaunchRec r;
-  hipStream_t s;
-  bool active;
-  ScopedLaunchTimer(int variant, double M, double N, double K, hipStream_t stream) : s(stream), active(g_prof.on) {
-    if (!active) return;
-    const double flops = 2.0 * M * N * K;
-    r.bytes = 4.0 * (M * K + N * K + M * N);
-    if (flops < g_prof.min_flops) {
-      std::lock_guard<std::mutex> lk(g_prof.mu);
-      g_prof.untimed[variant][0] += 1.0;
-      g_prof.untimed[variant][1] += flops;
-      active = false;
-      return;
-    }
-    r.variant = variant;
-    r.flops = flops;
-    r.a = g_prof.get();
-    r.b = g_prof.get();
-    if (!r.a || !r.b) {
-      active = false;
-      return;
-    }
-    (void)hipEventRecord(r.a, s);
-  }
-  ~ScopedLaunchTimer() {
-    if (!active) return;
-    (void)hipEventRecord(r.b, s);
-    std::lock_guard<std::mutex> lk(g_prof.mu);
-    g_prof.recs.push_back(r);
-  }
+constexpr int kNtLds = (2 * BM * LDK + 2 * BN * LDK) * 4;   // 73728 B (T=2); half of it for T=1
+constexpr int kNarrowLds = 2 * (64 + 32) * LDK * 4;         // 27648 B
+
+// One NT product as the entry points hand it to dispatch_nt, which fills in the alignment flags.
+struct NtCall {
+  const float* A;
+  int64_t lda;
+  const float* B;
+  int64_t ldb;
+  const float* bias;
+  float* C;
+  int64_t ldc, M, N, K;
+  int act;
+  float act_param, out_scale;
+  AMul am;
+  hipStream_t stream;
+  bool a_vec, b_vec, c_vec;
 };
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-constexpr int kNtLds = (2 * BM * LDK + 2 * BN * LDK) * 4;   // 73728 B (T=2); half of it for T=1
-constexpr int kTnLds = (4 * BK * LDM) * 4;                  // 67584 B
-
-// RECMV_GEMM_SKINNY=0 (read at every launch, so one process can time both): the routes before the skinny and the SCAL
-// kernels — the tool of profiles/r07_fallback_shapes_ab.txt.  RECMV_GEMM_OCC=0 switches them off as well.
-bool skinny_routes() {
-  const char* e = getenv("RECMV_GEMM_SKINNY");
-  return !(e && e[0] == '0');
-}
-
-bool tn_occ() {     // RECMV_GEMM_OCC=0: the two-workgroups-per-CU kernels (A/B)
-  static const bool v = [] { const char* e = getenv("RECMV_GEMM_OCC"); return !(e && e[0] == '0'); }();
-  return v;
-}
-
-int tn_splits(int64_t M, int64_t N, int64_t K) {
-  const int64_t tiles = ceil_div(M, BM) * ceil_div(N, BN);
-  int64_t want = ceil_div((int64_t)kNumCU * 4, tiles);        // ~4 workgroups per CU overall
-  const int64_t maxs = ceil_div(K, (int64_t)BK * 4);          // at least 4 K-tiles per split
-  if (want > maxs) want = maxs;
-  if (want > 128) want = 128;
-  if (want < 1) want = 1;
-  return (int)want;
-}
-
 }  // namespace
+
+ScopedLaunchTimer::ScopedLaunchTimer(int variant, double M, double N, double K, hipStream_t stream) : s(stream), active(g_prof.on) {
+  if (!active) return;
+  const double flops = 2.0 * M * N * K;
+  r.bytes = 4.0 * (M * K + N * K + M * N);
+  if (flops < g_prof.min_flops) {
+    std::lock_guard<std::mutex> lk(g_prof.mu);
+    g_prof.untimed[variant][0] += 1.0;
+    g_prof.untimed[variant][1] += flops;
+    active = false;
+    return;
+  }
+  r.variant = variant;
+  r.flops = flops;
+  r.a = g_prof.get();
+  r.b = g_prof.get();
+  if (!r.a || !r.b) {
+    active = false;
+    return;
+  }
+  (void)hipEventRecord(r.a, s);
+}
+ScopedLaunchTimer::~ScopedLaunchTimer() {
+  if (!active) return;
+  (void)hipEventRecord(r.b, s);
+  std::lock_guard<std::mutex> lk(g_prof.mu);
+  g_prof.recs.push_back(r);
+}
+
+void log_shape(const char* route, const char* parent, const LoggedShape& s) {
+  static const bool on = [] { const char* e = getenv("RECMV_GEMM_SHAPES"); return e && e[0] == '1'; }();
+  if (!on || !route::logged(s.M, s.N, s.K)) return;
+  static std::mutex mu;
+  static std::unordered_map<std::string, int> seen;
+  char key[256];
+  snprintf(key, sizeof key, "%s (before: %s) M=%lld N=%lld K=%lld lda=%lld ldb=%lld A%%16=%d B%%16=%d amul=%d emul=%d seg=%d", route, parent,
+           (long long)s.M, (long long)s.N, (long long)s.K, (long long)s.lda, (long long)s.ldb, (int)(reinterpret_cast<uintptr_t>(s.A) & 15),
+           (int)(reinterpret_cast<uintptr_t>(s.B) & 15), (int)s.amul, (int)s.emul, (int)s.seg);
+  std::lock_guard<std::mutex> lk(mu);
+  if (seen[key]++ == 0) fprintf(stderr, "[recmv shapes] %s\n", key);
+}
+
 }  // namespace recmv
 
 using namespace recmv;
+using route::NtKernel;
+using route::NtPlan;
 
 int g_b3_families = 7;   // mode 1 only: bit 0 the 128 x 128 NT kernels, bit 1 the 64 x 64 / 64 x 32 NT kernels, bit 2 the TN (dW) kernel
 int g_gemm_mode = 0;     // 0: f32 MFMA (exact f32 products), 1: bf16x6 (3-way bf16 split, six bf16 MFMA products)
 
+route::GemmSwitches recmv::gemm_switches() {
+  static const bool occ = [] { const char* e = getenv("RECMV_GEMM_OCC"); return !(e && e[0] == '0'); }();   // =0: the two-per-CU kernels (A/B)
+  const char* e = getenv("RECMV_GEMM_SKINNY");
+  return {g_gemm_mode, g_b3_families, occ, !(e && e[0] == '0')};
+}
+
+// ---- launchers: one per kernel template.  The profile slot comes with the plan: a launch of a kernel added after the 14 slots were
+// fixed is recorded under the slot of the kernel that took the launch before, so the per-step FLOP totals stay comparable.
 template <int T, bool FAST, bool AMUL, bool BF3>
-static int launch_nt(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C,
-                     int64_t ldc, int64_t M, int64_t N, int64_t K, int act, float act_param, float out_scale,
-                     bool a_vec, bool b_vec, bool c_vec, const AMul& am, hipStream_t stream) {
+static int launch_nt(const NtCall& c, const NtPlan& p) {
   constexpr int lds = kNtLds / (T == 2 ? 1 : 2);
   static bool attr_set = false;
   if (!attr_set) {
@@ -1766,87 +1296,58 @@ static int launch_nt(const float* A, int64_t lda, const float* B, int64_t ldb, c
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     attr_set = true;
   }
-  const int nbm = (int)ceil_div(M, 64 * T), nbn = (int)ceil_div(N, 64 * T);
-  ScopedLaunchTimer timer((T - 1) + 2 * (FAST ? 1 : 0) + 4 * (AMUL ? 1 : 0), (double)M, (double)N, (double)K, stream);
-  hipLaunchKernelGGL((gemm_nt_kernel<T, FAST, AMUL, BF3>), dim3((unsigned)((int64_t)nbm * nbn)), dim3(kBlk), lds, stream, A,
-                     lda, B, ldb, bias, C, ldc, (int)M, (int)N, (int)K, act, act_param, out_scale, nbm, nbn, a_vec,
-                     b_vec, c_vec, am);
+  const int nbm = (int)ceil_div(c.M, 64 * T), nbn = (int)ceil_div(c.N, 64 * T);
+  ScopedLaunchTimer timer(p.slot, (double)c.M, (double)c.N, (double)c.K, c.stream);
+  hipLaunchKernelGGL((gemm_nt_kernel<T, FAST, AMUL, BF3>), dim3((unsigned)((int64_t)nbm * nbn)), dim3(kBlk), lds, c.stream, c.A,
+                     c.lda, c.B, c.ldb, c.bias, c.C, c.ldc, (int)c.M, (int)c.N, (int)c.K, c.act, c.act_param, c.out_scale, nbm, nbn,
+                     p.a_vec, p.b_vec, c.c_vec, c.am);
   return check_launch("gemm_nt");
 }
 
-// Profile slots: a launch of a kernel added after the 14 slots were fixed is recorded under the slot of the kernel that took the launch
-// before (SCAL and the skinny NT kernels: gemm_nt_kernel<2, false, AMUL> = 1 + 4 AMUL where the old route was that kernel), so the
-// per-step FLOP totals stay comparable.
-template <bool AMUL, int BKT, bool SINGLE, int MI, int NI, bool SCAL = false>
-static int launch_nt_occ(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C,
-                         int64_t ldc, int64_t M, int64_t N, int64_t K, int act, float act_param, float out_scale,
-                         bool c_vec, const AMul& am, hipStream_t stream, bool a_vec = true, bool b_vec = true) {
-  constexpr int lds_ops = (SINGLE ? 1 : 2) * 64 * (MI + NI) * (BKT + 4) * 4, lds_c = 32 * MI * (64 * NI + 4) * 4;
+template <bool FAST, bool AMUL, bool BF3>
+static int launch_nt_narrow(const NtCall& c, const NtPlan& p) {
+  const int nbm = (int)ceil_div(c.M, 64), nbn = (int)ceil_div(c.N, 32);
+  ScopedLaunchTimer timer(p.slot, (double)c.M, (double)c.N, (double)c.K, c.stream);
+  hipLaunchKernelGGL((gemm_nt_narrow_kernel<FAST, AMUL, BF3>), dim3((unsigned)((int64_t)nbm * nbn)), dim3(kBlk), kNarrowLds, c.stream,
+                     c.A, c.lda, c.B, c.ldb, c.bias, c.C, c.ldc, (int)c.M, (int)c.N, (int)c.K, c.act, c.act_param, c.out_scale, nbm, nbn,
+                     p.a_vec, p.b_vec, c.c_vec, c.am);
+  return check_launch("gemm_nt(narrow)");
+}
+
+// MI x NI tiles of 64 x 64 per workgroup, K-tile 16; SCAL: staging loads that need only dword alignment
+template <bool AMUL, int MI, int NI, bool SCAL>
+static int launch_nt_occ(const NtCall& c, const NtPlan& p) {
+  constexpr int lds_ops = 64 * (MI + NI) * (16 + 4) * 4, lds_c = 32 * MI * (64 * NI + 4) * 4;
   constexpr int lds = lds_ops > lds_c ? lds_ops : lds_c;
-  const int nbm = (int)ceil_div(M, 64 * MI), nbn = (int)ceil_div(N, 64 * NI);
-  ScopedLaunchTimer timer(SCAL ? (AMUL ? 5 : 1) : (AMUL ? 11 : (MI == 2 ? 9 : 10)), (double)M, (double)N, (double)K, stream);
-  hipLaunchKernelGGL((gemm_nt_occ_kernel<AMUL, BKT, SINGLE, MI, NI, SCAL>), dim3((unsigned)((int64_t)nbm * nbn)), dim3(kBlk), lds,
-                     stream, A, lda, B, ldb, bias, C, ldc, (int)M, (int)N, (int)K, act, act_param, out_scale, nbm, nbn, c_vec,
-                     am, a_vec, b_vec);
+  const int nbm = (int)ceil_div(c.M, 64 * MI), nbn = (int)ceil_div(c.N, 64 * NI);
+  ScopedLaunchTimer timer(p.slot, (double)c.M, (double)c.N, (double)c.K, c.stream);
+  hipLaunchKernelGGL((gemm_nt_occ_kernel<AMUL, 16, true, MI, NI, SCAL>), dim3((unsigned)((int64_t)nbm * nbn)), dim3(kBlk), lds,
+                     c.stream, c.A, c.lda, c.B, c.ldb, c.bias, c.C, c.ldc, (int)c.M, (int)c.N, (int)c.K, c.act, c.act_param,
+                     c.out_scale, nbm, nbn, c.c_vec, c.am, p.a_vec, p.b_vec);
   return check_launch("gemm_nt(occ)");
 }
 
-// The profile slot of the kernel the parent routes give a launch (see dispatch_nt).
-static int nt_old_slot(int64_t M, int64_t N, bool fast, bool amul) {
-  const int64_t big_blocks = ceil_div(M, BM) * ceil_div(N, BN);
-  if (big_blocks >= 2 * kNumCU) {
-    if (!fast) return amul ? 5 : 1;
-    return amul ? 11 : (big_blocks >= 3600 ? 9 : 10);
-  }
-  if (ceil_div(M, 64) * ceil_div(N, 64) < (5 * kNumCU) / 2) return fast && !amul ? 12 : 13;
-  return 2 * (fast ? 1 : 0) + 4 * (amul ? 1 : 0);
-}
-
 template <int NN>
-static int launch_nt_thin_n(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C,
-                            int64_t ldc, int64_t M, int64_t K, int act, float act_param, float out_scale, bool vec,
-                            const AMul& am, int slot, hipStream_t stream) {
-  ScopedLaunchTimer timer(slot, (double)M, (double)NN, (double)K, stream);
-  const dim3 grid((unsigned)ceil_div(M, kThinRows));
-  // the summation order of the MFMA kernel that the tile choice of dispatch_nt gives a launch of this many rows: below 2.5 tiles of
-  // 64 x 64 per CU that is the 64 x 32 kernel, whose waves split every K-tile in two halves
-  const bool halves = ceil_div(M, 64) < (5 * kNumCU) / 2;
-  if (vec)
-    hipLaunchKernelGGL((gemm_nt_thin_n_kernel<NN, true>), grid, dim3(kThinRows), 0, stream, A, lda, B, ldb, bias, C, ldc, (int)M,
-                       (int)K, act, act_param, out_scale, halves, am);
+static int launch_nt_thin_n(const NtCall& c, const NtPlan& p) {
+  ScopedLaunchTimer timer(p.slot, (double)c.M, (double)NN, (double)c.K, c.stream);
+  const dim3 grid((unsigned)ceil_div(c.M, kThinRows));
+  if (p.a_vec && c.K % 4 == 0)
+    hipLaunchKernelGGL((gemm_nt_thin_n_kernel<NN, true>), grid, dim3(kThinRows), 0, c.stream, c.A, c.lda, c.B, c.ldb, c.bias, c.C,
+                       c.ldc, (int)c.M, (int)c.K, c.act, c.act_param, c.out_scale, p.halves, c.am);
   else
-    hipLaunchKernelGGL((gemm_nt_thin_n_kernel<NN, false>), grid, dim3(kThinRows), 0, stream, A, lda, B, ldb, bias, C, ldc, (int)M,
-                       (int)K, act, act_param, out_scale, halves, am);
+    hipLaunchKernelGGL((gemm_nt_thin_n_kernel<NN, false>), grid, dim3(kThinRows), 0, c.stream, c.A, c.lda, c.B, c.ldb, c.bias, c.C,
+                       c.ldc, (int)c.M, (int)c.K, c.act, c.act_param, c.out_scale, p.halves, c.am);
   return check_launch("gemm_nt(thin n)");
 }
 
 template <int KK, bool AMUL>
-static int launch_nt_thin_k(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C,
-                            int64_t ldc, int64_t M, int64_t N, int act, float act_param, float out_scale, bool c_vec,
-                            const AMul& am, int slot, hipStream_t stream) {
-  ScopedLaunchTimer timer(slot, (double)M, (double)N, (double)KK, stream);
+static int launch_nt_thin_k(const NtCall& c, const NtPlan& p) {
+  ScopedLaunchTimer timer(p.slot, (double)c.M, (double)c.N, (double)KK, c.stream);
   int cw_log2 = 0;
-  while (cw_log2 < 8 && (4ll << cw_log2) < N) ++cw_log2;      // threads across a row: the float4 strips of a row, at most 256
-  hipLaunchKernelGGL((gemm_nt_thin_k_kernel<KK, AMUL>), dim3((unsigned)ceil_div(M, kThinKRows)), dim3(kBlk), 0, stream, A, lda, B,
-                     ldb, bias, C, ldc, (int)M, (int)N, act, act_param, out_scale, cw_log2, c_vec, am);
+  while (cw_log2 < 8 && (4ll << cw_log2) < c.N) ++cw_log2;      // threads across a row: the float4 strips of a row, at most 256
+  hipLaunchKernelGGL((gemm_nt_thin_k_kernel<KK, AMUL>), dim3((unsigned)ceil_div(c.M, kThinKRows)), dim3(kBlk), 0, c.stream, c.A, c.lda,
+                     c.B, c.ldb, c.bias, c.C, c.ldc, (int)c.M, (int)c.N, c.act, c.act_param, c.out_scale, cw_log2, c.c_vec, c.am);
   return check_launch("gemm_nt(thin k)");
-}
-
-// RECMV_GEMM_SHAPES=1: every distinct (route, route before the skinny / SCAL kernels, shape, leading dimensions, alignment)
-// of a product of more than 1e8 multiply-adds that those kernels take or that still runs on a two-per-CU kernel is printed once to stderr — how the table of profiles/r07_fallback_shapes.txt was taken.
-static void log_shape(const char* route, const char* parent, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, const void* A, const void* B,
-                      bool amul, bool emul, bool seg) {
-  static const bool on = [] { const char* e = getenv("RECMV_GEMM_SHAPES"); return e && e[0] == '1'; }();
-  if (!on || (double)M * (double)N * (double)K < 1e8) return;
-  static std::mutex mu;
-  static std::unordered_map<std::string, int> seen;
-  char key[256];
-  snprintf(key, sizeof key, "%s (before: %s) M=%lld N=%lld K=%lld lda=%lld ldb=%lld A%%16=%d B%%16=%d amul=%d emul=%d seg=%d", route, parent,
-           (long long)M,
-           (long long)N, (long long)K, (long long)lda, (long long)ldb, (int)(reinterpret_cast<uintptr_t>(A) & 15),
-           (int)(reinterpret_cast<uintptr_t>(B) & 15), (int)amul, (int)emul, (int)seg);
-  std::lock_guard<std::mutex> lk(mu);
-  if (seen[key]++ == 0) fprintf(stderr, "[recmv shapes] %s\n", key);
 }
 
 // Weight matrices whose bf16 planes exist (recmv_b3_split), by the address the products get them under.
@@ -1856,18 +1357,16 @@ struct B3Entry {
 };
 static std::mutex g_b3_mu;
 static std::unordered_map<const float*, B3Entry> g_b3;
-static bool b3_lookup(const float* B, int64_t N, int64_t K, int64_t ldb, B3Entry* out) {
+static bool b3_lookup(const float* B, const NtCall& c, B3Entry* out) {
   std::lock_guard<std::mutex> lock(g_b3_mu);
   auto it = g_b3.find(B);
-  if (it == g_b3.end() || it->second.K != K || it->second.ldb != ldb || it->second.N < N) return false;
+  if (it == g_b3.end() || it->second.K != c.K || it->second.ldb != c.ldb || it->second.N < c.N) return false;
   *out = it->second;
   return true;
 }
 
 template <int T, bool AMUL, bool PRE>
-static int launch_nt_b3_as(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C, int64_t ldc,
-                           int64_t M, int64_t N, int64_t K, int act, float act_param, float out_scale, bool c_vec, const AMul& am,
-                           const B3Pre& pre, hipStream_t stream) {
+static int launch_nt_b3_as(const NtCall& c, const NtPlan& p, const B3Pre& pre) {
   constexpr int lds_ops = 6 * 64 * T * 64, lds_c = 64 * T * (64 * T + 4) * 4;
   constexpr int lds = lds_ops > lds_c ? lds_ops : lds_c;
   static bool attr_set = false;
@@ -1876,126 +1375,71 @@ static int launch_nt_b3_as(const float* A, int64_t lda, const float* B, int64_t 
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     attr_set = true;
   }
-  const int nbm = (int)ceil_div(M, 64 * T), nbn = (int)ceil_div(N, 64 * T);
-  ScopedLaunchTimer timer((T - 1) + 2 + 4 * (AMUL ? 1 : 0), (double)M, (double)N, (double)K, stream);
-  hipLaunchKernelGGL((gemm_nt_b3_kernel<T, AMUL, PRE>), dim3((unsigned)((int64_t)nbm * nbn)), dim3(kBlk), lds, stream, A, lda,
-                     B, ldb, bias, C, ldc, (int)M, (int)N, (int)K, act, act_param, out_scale, nbm, nbn, c_vec, am, pre);
+  const int nbm = (int)ceil_div(c.M, 64 * T), nbn = (int)ceil_div(c.N, 64 * T);
+  ScopedLaunchTimer timer(p.slot, (double)c.M, (double)c.N, (double)c.K, c.stream);
+  hipLaunchKernelGGL((gemm_nt_b3_kernel<T, AMUL, PRE>), dim3((unsigned)((int64_t)nbm * nbn)), dim3(kBlk), lds, c.stream, c.A, c.lda,
+                     c.B, c.ldb, c.bias, c.C, c.ldc, (int)c.M, (int)c.N, (int)c.K, c.act, c.act_param, c.out_scale, nbm, nbn, c.c_vec,
+                     c.am, pre);
   return check_launch("gemm_nt(b3)");
 }
 
 template <int T, bool AMUL>
-static int launch_nt_b3(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C,
-                        int64_t ldc, int64_t M, int64_t N, int64_t K, int act, float act_param, float out_scale,
-                        bool c_vec, const AMul& am, hipStream_t stream) {
+static int launch_nt_b3(const NtCall& c, const NtPlan& p) {
   B3Entry e, e2;
-  if (b3_lookup(B, N, K, ldb, &e) && (!am.B2 || (b3_lookup(am.B2, N, K, ldb, &e2) && e2.Kp == e.Kp))) {
-    B3Pre pre = {e.planes, am.B2 ? e2.planes : nullptr, e.N * e.Kp * 2, am.B2 ? e2.N * e2.Kp * 2 : 0, (int)e.Kp};
-    return launch_nt_b3_as<T, AMUL, true>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, c_vec, am, pre, stream);
+  if (b3_lookup(c.B, c, &e) && (!c.am.B2 || (b3_lookup(c.am.B2, c, &e2) && e2.Kp == e.Kp))) {
+    B3Pre pre = {e.planes, c.am.B2 ? e2.planes : nullptr, e.N * e.Kp * 2, c.am.B2 ? e2.N * e2.Kp * 2 : 0, (int)e.Kp};
+    return launch_nt_b3_as<T, AMUL, true>(c, p, pre);
   }
   B3Pre none = {nullptr, nullptr, 0, 0, 0};
-  return launch_nt_b3_as<T, AMUL, false>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, c_vec, am, none, stream);
+  return launch_nt_b3_as<T, AMUL, false>(c, p, none);
 }
 
-constexpr int kNarrowLds = 2 * (64 + 32) * LDK * 4;   // 27648 B
-
-template <bool FAST, bool AMUL, bool BF3>
-static int launch_nt_narrow(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C,
-                            int64_t ldc, int64_t M, int64_t N, int64_t K, int act, float act_param, float out_scale,
-                            bool a_vec, bool b_vec, bool c_vec, const AMul& am, hipStream_t stream) {
-  const int nbm = (int)ceil_div(M, 64), nbn = (int)ceil_div(N, 32);
-  ScopedLaunchTimer timer(FAST && !AMUL ? 12 : 13, (double)M, (double)N, (double)K, stream);
-  hipLaunchKernelGGL((gemm_nt_narrow_kernel<FAST, AMUL, BF3>), dim3((unsigned)((int64_t)nbm * nbn)), dim3(kBlk),
-                     kNarrowLds, stream, A, lda, B, ldb, bias, C, ldc, (int)M, (int)N, (int)K, act, act_param, out_scale,
-                     nbm, nbn, a_vec, b_vec, c_vec, am);
-  return check_launch("gemm_nt(narrow)");
+// the FAST / BF3 instantiation the plan names
+template <int T, bool AMUL>
+static int launch_nt_tile(const NtCall& c, const NtPlan& p) {
+  if (p.fast) return p.bf3 ? launch_nt<T, true, AMUL, true>(c, p) : launch_nt<T, true, AMUL, false>(c, p);
+  return p.bf3 ? launch_nt<T, false, AMUL, true>(c, p) : launch_nt<T, false, AMUL, false>(c, p);
 }
-
 template <bool AMUL>
-static int dispatch_nt(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C,
-                       int64_t ldc, int64_t M, int64_t N, int64_t K, int act, float act_param, float out_scale,
-                       const AMul& am, hipStream_t s) {
-  const bool a_vec = aligned16(A) && lda % 4 == 0 && (!AMUL || (aligned16(am.Y) && am.ldy % 4 == 0));
-  const bool b_vec = aligned16(B) && ldb % 4 == 0 && (!am.B2 || aligned16(am.B2));
-  const bool c_vec = aligned16(C) && ldc % 4 == 0;
-  const bool fast = a_vec && b_vec && K % 4 == 0 && K > 0;
-  // tile choice: 128x128 tiles unless they would leave the 256 CUs under-filled (< 2 workgroups per CU)
-  const int64_t big_blocks = ceil_div(M, BM) * ceil_div(N, BN);
-  // (which kernel families take the bf16x6 path in mode 1: recmv_set_b3_families, all of them by default)
-  const bool bf3_big = g_gemm_mode == 1 && (g_b3_families & 1), bf3_mid = g_gemm_mode == 1 && (g_b3_families & 2);
-  static const bool occ_env = [] { const char* e = getenv("RECMV_GEMM_OCC"); return !(e && e[0] == '0'); }();
-  const bool occ = occ_env, skinny = occ_env && skinny_routes();
-  const char* parent_route = big_blocks >= 2 * kNumCU ? (fast ? "nt_occ" : "nt_kernel<2,false>") : "below 512 large tiles";
-  // f32 mode, skinny shapes (the route is chosen by N and K alone; every launch keeps the bits its MFMA route gave it): the
-  // rank-K update for K <= 4, the per-row chains for N <= 4.  RECMV_GEMM_OCC=0 keeps the MFMA routes for the A/B.
-  if (g_gemm_mode == 0 && skinny && K >= 1 && K <= 4) {
-    const int slot = nt_old_slot(M, N, fast, AMUL);
-    log_shape("thin_k", parent_route, M, N, K, lda, ldb, A, B, AMUL, !AMUL && am.Y, am.B2 != nullptr);
-#define RECMV_TK(KK) \
-  case KK: return launch_nt_thin_k<KK, AMUL>(A, lda, B, ldb, bias, C, ldc, M, N, act, act_param, out_scale, c_vec, am, slot, s)
-    switch (K) {
-      RECMV_TK(1);
-      RECMV_TK(2);
-      RECMV_TK(3);
-      default: RECMV_TK(4);
-    }
-#undef RECMV_TK
+static int launch_nt_narrow_tile(const NtCall& c, const NtPlan& p) {
+  if (p.fast) return p.bf3 ? launch_nt_narrow<true, AMUL, true>(c, p) : launch_nt_narrow<true, AMUL, false>(c, p);
+  return p.bf3 ? launch_nt_narrow<false, AMUL, true>(c, p) : launch_nt_narrow<false, AMUL, false>(c, p);
+}
+
+// plan (gemm_route.h), log, launch
+template <bool AMUL>
+static int dispatch_nt(NtCall& c) {
+  c.a_vec = aligned16(c.A) && c.lda % 4 == 0 && (!AMUL || (aligned16(c.am.Y) && c.am.ldy % 4 == 0));
+  c.b_vec = aligned16(c.B) && c.ldb % 4 == 0 && (!c.am.B2 || aligned16(c.am.B2));
+  c.c_vec = aligned16(c.C) && c.ldc % 4 == 0;
+  const bool emul = !AMUL && c.am.Y, seg = c.am.B2 != nullptr;
+  const NtPlan p = route::plan_nt({c.M, c.N, c.K, c.a_vec, c.b_vec, c.c_vec, AMUL, emul, seg, c.lda >= c.K}, gemm_switches());
+  if (p.route[0]) log_shape(p.route, p.parent, {c.M, c.N, c.K, c.lda, c.ldb, c.A, c.B, AMUL, emul, seg});
+  switch (p.kernel) {
+    case NtKernel::ThinK:
+      switch (c.K) {
+        case 1: return launch_nt_thin_k<1, AMUL>(c, p);
+        case 2: return launch_nt_thin_k<2, AMUL>(c, p);
+        case 3: return launch_nt_thin_k<3, AMUL>(c, p);
+        default: return launch_nt_thin_k<4, AMUL>(c, p);
+      }
+    case NtKernel::ThinN:
+      switch (c.N) {
+        case 1: return launch_nt_thin_n<1>(c, p);
+        case 2: return launch_nt_thin_n<2>(c, p);
+        case 3: return launch_nt_thin_n<3>(c, p);
+        default: return launch_nt_thin_n<4>(c, p);
+      }
+    case NtKernel::B3: return launch_nt_b3<2, AMUL>(c, p);
+    case NtKernel::Occ128: return launch_nt_occ<AMUL, 2, 2, false>(c, p);
+    case NtKernel::Occ64x128: return launch_nt_occ<AMUL, 1, 2, false>(c, p);
+    case NtKernel::Occ128Scal: return launch_nt_occ<AMUL, 2, 2, true>(c, p);
+    case NtKernel::Occ64x128Scal: return launch_nt_occ<AMUL, 1, 2, true>(c, p);
+    case NtKernel::Tile128: return launch_nt_tile<2, AMUL>(c, p);
+    case NtKernel::Narrow: return launch_nt_narrow_tile<AMUL>(c, p);
+    case NtKernel::Tile64: break;
   }
-  if (g_gemm_mode == 0 && skinny && !AMUL && N <= 4) {
-    const int slot = nt_old_slot(M, N, fast, false);
-    const bool vec = a_vec && K % 4 == 0;
-    log_shape("thin_n", parent_route, M, N, K, lda, ldb, A, B, false, am.Y != nullptr, am.B2 != nullptr);
-#define RECMV_TN_(NN) \
-  case NN: return launch_nt_thin_n<NN>(A, lda, B, ldb, bias, C, ldc, M, K, act, act_param, out_scale, vec, am, slot, s)
-    switch (N) {
-      RECMV_TN_(1);
-      RECMV_TN_(2);
-      RECMV_TN_(3);
-      default: RECMV_TN_(4);
-    }
-#undef RECMV_TN_
-  }
-#define RECMV_NT(TT, FF)                                                                                         \
-  ((TT == 2 ? bf3_big : bf3_mid) ? launch_nt<TT, FF, AMUL, true>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, \
-                                                    a_vec, b_vec, c_vec, am, s)                                    \
-                    : launch_nt<TT, FF, AMUL, false>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param,        \
-                                                     out_scale, a_vec, b_vec, c_vec, am, s))
-  if (big_blocks >= 2 * kNumCU) {
-    if (bf3_big && fast) {
-      return launch_nt_b3<2, AMUL>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, c_vec, am, s);
-    }
-    // f32 mode, aligned operands: the high-occupancy kernels (gemm_nt_occ_kernel) — 128x128 tiles at four workgroups per CU
-    // for the largest launches, 64x128 tiles at five per CU below ~3600 large tiles (finer tail, measured crossover between
-    // 90 k and 150 k rows at N = 512: profiles/r03_gemm_occupancy_variants.txt).  RECMV_GEMM_OCC=0 keeps the two-per-CU
-    // kernel for the A/B.
-    if (fast && !bf3_big && occ) {
-      if (big_blocks >= 3600)
-        return launch_nt_occ<AMUL, 16, true, 2, 2>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, c_vec, am, s);
-      return launch_nt_occ<AMUL, 16, true, 1, 2>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, c_vec, am, s);
-    }
-    // unaligned operands or K % 4 != 0: the same kernels with staging loads that need only dword alignment (bit-identical to the
-    // aligned route on a zero-padded copy) instead of the two-per-CU kernel: 1.2-1.6x per launch (profiles/r07_fallback_shapes_ab.txt)
-    if (!fast && !bf3_big && skinny && K > 0) {
-      log_shape("occ_scal", parent_route, M, N, K, lda, ldb, A, B, AMUL, !AMUL && am.Y, am.B2 != nullptr);
-      if (big_blocks >= 3600)
-        return launch_nt_occ<AMUL, 16, true, 2, 2, true>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, c_vec, am, s, a_vec && lda >= K, b_vec);
-      return launch_nt_occ<AMUL, 16, true, 1, 2, true>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, c_vec, am, s, a_vec && lda >= K, b_vec);
-    }
-    if (!fast) log_shape("nt_kernel<2,false>", parent_route, M, N, K, lda, ldb, A, B, AMUL, !AMUL && am.Y, am.B2 != nullptr);
-    return fast ? RECMV_NT(2, true) : RECMV_NT(2, false);
-  }
-  // 64x64 tiles unless they would give the CUs fewer than ~2.5 workgroups each: then 64x32 tiles (twice as many)
-  const int64_t mid_blocks = ceil_div(M, 64) * ceil_div(N, 64);
-  if (mid_blocks < (5 * kNumCU) / 2) {
-#define RECMV_NTN(FF)                                                                                                  \
-  (bf3_mid ? launch_nt_narrow<FF, AMUL, true>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, \
-                                                       a_vec, b_vec, c_vec, am, s)                                     \
-                    : launch_nt_narrow<FF, AMUL, false>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param,          \
-                                                        out_scale, a_vec, b_vec, c_vec, am, s))
-    return fast ? RECMV_NTN(true) : RECMV_NTN(false);
-#undef RECMV_NTN
-  }
-  return fast ? RECMV_NT(1, true) : RECMV_NT(1, false);
-#undef RECMV_NT
+  return launch_nt_tile<1, AMUL>(c, p);
 }
 
 // Matrix mode of recmv_gemm_nt: 0 = f32-input MFMA (default; bit-for-bit an f32 fma chain), 1 = "bf16x6" (each f32
@@ -2049,17 +1493,30 @@ extern "C" int recmv_b3_forget(const float* B) {
   return RECMV_OK;
 }
 
+// The checks the five NT entry points share, in their order, under the entry point's name.  *run: there is something to launch
+// (an empty product passes with NULL operands).
+static int check_nt_args(const char* name, const NtCall& c, bool pointers, bool leading_dims, bool* run) {
+  *run = false;
+  RECMV_REQUIRE(c.M >= 0 && c.N >= 0 && c.K >= 0, "%s: negative size", name);
+  if (c.M == 0 || c.N == 0) return RECMV_OK;
+  RECMV_REQUIRE(pointers, "%s: NULL pointer", name);
+  RECMV_REQUIRE(leading_dims, "%s: leading dimension too small", name);
+  RECMV_REQUIRE(c.M < (1ll << 31) - BM && c.N < (1ll << 31) - BN && c.K < (1ll << 31) - BK, "%s: size overflow", name);
+  const int act = c.am.Y ? c.am.act : c.act;      // the caller's activation: the transform's where there is one, else the epilogue's
+  RECMV_REQUIRE(act >= RECMV_ACT_NONE && act <= RECMV_ACT_TANH, "%s: unknown activation %d", name, act);
+  *run = true;
+  return RECMV_OK;
+}
+
 extern "C" int recmv_gemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias,
                              float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int act,
                              float act_param, float out_scale, void* stream) {
-  RECMV_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm_nt: negative size");
-  if (M == 0 || N == 0) return RECMV_OK;
-  RECMV_REQUIRE(A && B && C, "gemm_nt: NULL pointer");
-  RECMV_REQUIRE(lda >= K && ldb >= K && ldc >= N, "gemm_nt: leading dimension too small");
-  RECMV_REQUIRE(M < (1ll << 31) - BM && N < (1ll << 31) - BN && K < (1ll << 31) - BK, "gemm_nt: size overflow");
-  RECMV_REQUIRE(act >= RECMV_ACT_NONE && act <= RECMV_ACT_TANH, "gemm_nt: unknown activation %d", act);
-  AMul am = {nullptr, 0, RECMV_ACT_NONE, 0.f, 1.f, 1.f};
-  return dispatch_nt<false>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, am, (hipStream_t)stream);
+  NtCall c = {A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, {nullptr, 0, RECMV_ACT_NONE, 0.f, 1.f, 1.f},
+              (hipStream_t)stream};
+  bool run;
+  const int rc = check_nt_args("gemm_nt", c, A && B && C, lda >= K && ldb >= K && ldc >= N, &run);
+  if (!run) return rc;
+  return dispatch_nt<false>(c);
 }
 
 // C[M,N] = (G (.) act'(y_scale * Y) * g_scale) . B^T : the activation-gradient step fused into the product.
@@ -2067,15 +1524,12 @@ extern "C" int recmv_gemm_nt(const float* A, int64_t lda, const float* B, int64_
 extern "C" int recmv_gemm_nt_actgrad(const float* G, int64_t ldg, const float* Y, int64_t ldy, const float* B,
                                      int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int act,
                                      float act_param, float y_scale, float g_scale, void* stream) {
-  RECMV_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm_nt_actgrad: negative size");
-  if (M == 0 || N == 0) return RECMV_OK;
-  RECMV_REQUIRE(G && Y && B && C, "gemm_nt_actgrad: NULL pointer");
-  RECMV_REQUIRE((ldg >= K || ldg == 0) && ldy >= K && ldb >= K && ldc >= N,
-                "gemm_nt_actgrad: leading dimension too small");
-  RECMV_REQUIRE(M < (1ll << 31) - BM && N < (1ll << 31) - BN && K < (1ll << 31) - BK, "gemm_nt_actgrad: size overflow");
-  RECMV_REQUIRE(act >= RECMV_ACT_NONE && act <= RECMV_ACT_TANH, "gemm_nt_actgrad: unknown activation %d", act);
-  AMul am = {Y, ldy, act, act_param, y_scale, g_scale};
-  return dispatch_nt<true>(G, ldg, B, ldb, nullptr, C, ldc, M, N, K, RECMV_ACT_NONE, 0.f, 1.f, am, (hipStream_t)stream);
+  NtCall c = {G, ldg, B, ldb, nullptr, C, ldc, M, N, K, RECMV_ACT_NONE, 0.f, 1.f, {Y, ldy, act, act_param, y_scale, g_scale},
+              (hipStream_t)stream};
+  bool run;
+  const int rc = check_nt_args("gemm_nt_actgrad", c, G && Y && B && C, (ldg >= K || ldg == 0) && ldy >= K && ldb >= K && ldc >= N, &run);
+  if (!run) return rc;
+  return dispatch_nt<true>(c);
 }
 
 // C[M,N] = (A . B^T) (.) act'(y_scale * Y) * scale : the activation-gradient step of the NEXT backward layer fused into the
@@ -2083,14 +1537,12 @@ extern "C" int recmv_gemm_nt_actgrad(const float* G, int64_t ldg, const float* Y
 extern "C" int recmv_gemm_nt_mulgrad(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
                                      int64_t M, int64_t N, int64_t K, const float* Y, int64_t ldy, int act,
                                      float act_param, float y_scale, float scale, void* stream) {
-  RECMV_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm_nt_mulgrad: negative size");
-  if (M == 0 || N == 0) return RECMV_OK;
-  RECMV_REQUIRE(A && B && C && Y, "gemm_nt_mulgrad: NULL pointer");
-  RECMV_REQUIRE(lda >= K && ldb >= K && ldc >= N && ldy >= N, "gemm_nt_mulgrad: leading dimension too small");
-  RECMV_REQUIRE(M < (1ll << 31) - BM && N < (1ll << 31) - BN && K < (1ll << 31) - BK, "gemm_nt_mulgrad: size overflow");
-  RECMV_REQUIRE(act >= RECMV_ACT_NONE && act <= RECMV_ACT_TANH, "gemm_nt_mulgrad: unknown activation %d", act);
-  AMul em = {Y, ldy, act, act_param, y_scale, scale};
-  return dispatch_nt<false>(A, lda, B, ldb, nullptr, C, ldc, M, N, K, RECMV_ACT_NONE, 0.f, 1.f, em, (hipStream_t)stream);
+  NtCall c = {A, lda, B, ldb, nullptr, C, ldc, M, N, K, RECMV_ACT_NONE, 0.f, 1.f, {Y, ldy, act, act_param, y_scale, scale},
+              (hipStream_t)stream};
+  bool run;
+  const int rc = check_nt_args("gemm_nt_mulgrad", c, A && B && C && Y, lda >= K && ldb >= K && ldc >= N && ldy >= N, &run);
+  if (!run) return rc;
+  return dispatch_nt<false>(c);
 }
 
 // The same products over a row block that holds the rows of TWO nets of one shape: rows [0, split_row) use B / bias, rows
@@ -2098,149 +1550,35 @@ extern "C" int recmv_gemm_nt_mulgrad(const float* A, int64_t lda, const float* B
 extern "C" int recmv_gemm_nt_seg(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias,
                                  const float* B2, const float* bias2, int64_t split_row, float* C, int64_t ldc, int64_t M,
                                  int64_t N, int64_t K, int act, float act_param, float out_scale, void* stream) {
-  RECMV_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm_nt_seg: negative size");
-  if (M == 0 || N == 0) return RECMV_OK;
-  RECMV_REQUIRE(A && B && C, "gemm_nt_seg: NULL pointer");
-  RECMV_REQUIRE(lda >= K && ldb >= K && ldc >= N, "gemm_nt_seg: leading dimension too small");
-  RECMV_REQUIRE(M < (1ll << 31) - BM && N < (1ll << 31) - BN && K < (1ll << 31) - BK, "gemm_nt_seg: size overflow");
-  RECMV_REQUIRE(act >= RECMV_ACT_NONE && act <= RECMV_ACT_TANH, "gemm_nt_seg: unknown activation %d", act);
+  NtCall c = {A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale,
+              {nullptr, 0, RECMV_ACT_NONE, 0.f, 1.f, 1.f, B2, bias2, (int)(split_row < M ? split_row : M)}, (hipStream_t)stream};
+  bool run;
+  const int rc = check_nt_args("gemm_nt_seg", c, A && B && C, lda >= K && ldb >= K && ldc >= N, &run);
+  if (!run) return rc;
   RECMV_REQUIRE(!B2 || (split_row >= 0 && split_row % BM == 0), "gemm_nt_seg: split_row must be a multiple of %d", BM);
   RECMV_REQUIRE(!B2 || !bias == !bias2, "gemm_nt_seg: both nets with or both without a bias");
-  AMul am = {nullptr, 0, RECMV_ACT_NONE, 0.f, 1.f, 1.f, B2, bias2, (int)(split_row < M ? split_row : M)};
-  return dispatch_nt<false>(A, lda, B, ldb, bias, C, ldc, M, N, K, act, act_param, out_scale, am, (hipStream_t)stream);
+  return dispatch_nt<false>(c);
 }
 
 extern "C" int recmv_gemm_nt_mulgrad_seg(const float* A, int64_t lda, const float* B, const float* B2, int64_t split_row,
                                          int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, const float* Y,
                                          int64_t ldy, int act, float act_param, float y_scale, float scale, void* stream) {
-  RECMV_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm_nt_mulgrad_seg: negative size");
-  if (M == 0 || N == 0) return RECMV_OK;
-  RECMV_REQUIRE(A && B && C && Y, "gemm_nt_mulgrad_seg: NULL pointer");
-  RECMV_REQUIRE(lda >= K && ldb >= K && ldc >= N && ldy >= N, "gemm_nt_mulgrad_seg: leading dimension too small");
-  RECMV_REQUIRE(M < (1ll << 31) - BM && N < (1ll << 31) - BN && K < (1ll << 31) - BK, "gemm_nt_mulgrad_seg: size overflow");
-  RECMV_REQUIRE(act >= RECMV_ACT_NONE && act <= RECMV_ACT_TANH, "gemm_nt_mulgrad_seg: unknown activation %d", act);
+  NtCall c = {A, lda, B, ldb, nullptr, C, ldc, M, N, K, RECMV_ACT_NONE, 0.f, 1.f,
+              {Y, ldy, act, act_param, y_scale, scale, B2, nullptr, (int)(split_row < M ? split_row : M)}, (hipStream_t)stream};
+  bool run;
+  const int rc = check_nt_args("gemm_nt_mulgrad_seg", c, A && B && C && Y, lda >= K && ldb >= K && ldc >= N && ldy >= N, &run);
+  if (!run) return rc;
   RECMV_REQUIRE(!B2 || (split_row >= 0 && split_row % BM == 0), "gemm_nt_mulgrad_seg: split_row must be a multiple of %d", BM);
-  AMul em = {Y, ldy, act, act_param, y_scale, scale, B2, nullptr, (int)(split_row < M ? split_row : M)};
-  return dispatch_nt<false>(A, lda, B, ldb, nullptr, C, ldc, M, N, K, RECMV_ACT_NONE, 0.f, 1.f, em, (hipStream_t)stream);
-}
-
-extern "C" int64_t recmv_gemm_tn_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  return (int64_t)tn_splits(M, N, K) * M * N * 4;
-}
-
-extern "C" int recmv_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
-                             int64_t M, int64_t N, int64_t K, void* workspace, int64_t workspace_bytes,
-                             void* stream) {
-  RECMV_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm_tn: negative size");
-  if (M == 0 || N == 0) return RECMV_OK;
-  RECMV_REQUIRE(M < (1 << 20) && N < (1 << 20), "gemm_tn: output too large");
-  hipStream_t s = (hipStream_t)stream;
-  if (K == 0) {                // an empty reduction (its operands carry NULL data pointers): C = 0
-    RECMV_REQUIRE(C && ldc >= N, "gemm_tn: bad output");
-    for (int64_t m = 0; m < M; ++m) RECMV_HIP_TRY(hipMemsetAsync(C + m * ldc, 0, N * 4, s));
-    return RECMV_OK;
-  }
-  RECMV_REQUIRE(A && B && C, "gemm_tn: NULL pointer");
-  RECMV_REQUIRE(lda >= M && ldb >= N && ldc >= N, "gemm_tn: leading dimension too small");
-  const int splits = tn_splits(M, N, K);
-  const int64_t need = (int64_t)splits * M * N * 4;
-  if (!workspace || workspace_bytes < need) {
-    set_error("gemm_tn: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
-    return RECMV_ERR_WORKSPACE;
-  }
-  static bool attr_set = false;
-  if (!attr_set) {
-    RECMV_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      kTnLds));
-    RECMV_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      kTnLds));
-    attr_set = true;
-  }
-  const int nbm = (int)ceil_div(M, BM), nbn = (int)ceil_div(N, BN);
-  int64_t kchunk = ceil_div(ceil_div(K, splits), BK) * BK;
-  const bool a_vec = aligned16(A) && lda % 4 == 0, b_vec = aligned16(B) && ldb % 4 == 0;
-  int rc;
-  {                          // the events bracket the product kernel alone (slot 8 = one kernel symbol); its reduction pass follows
-  ScopedLaunchTimer timer(8, (double)M, (double)N, (double)K, s);
-  const bool bf3_tn = g_gemm_mode == 1 && (g_b3_families & 4);
-  if (!bf3_tn && tn_occ() && skinny_routes() && (M <= 4 || N <= 4)) {
-    // a skinny output (the weight gradient of a 1- or 3-output layer): weighted column sums on the VALU, the partials and the split
-    // lengths of the MFMA kernel that took the launch before (the aligned high-occupancy kernel rounds them to 16 rows, the other to 32)
-    const bool swap = M > 4;                     // the thin operand is B
-    const float* T = swap ? B : A;
-    const float* W = swap ? A : B;
-    const int64_t ldt = swap ? ldb : lda, ldw = swap ? lda : ldb, NT = swap ? N : M, NW = swap ? M : N;
-    const bool was_occ = a_vec && b_vec && lda >= ((M + 3) & ~3ll) && ldb >= ((N + 3) & ~3ll) && M >= 4 && N >= 4;
-    kchunk = ceil_div(ceil_div(K, splits), was_occ ? 16 : BK) * (was_occ ? 16 : BK);
-    const int ntile = (int)ceil_div(NW, kWave);
-    const dim3 grid((unsigned)((int64_t)ntile * splits));
-    log_shape("tn_thin", was_occ ? "tn_occ" : "tn_kernel<false>", M, N, K, lda, ldb, A, B, false, false, false);
-#define RECMV_TT(NTT, SW) \
-  hipLaunchKernelGGL((gemm_tn_thin_kernel<NTT, SW>), grid, dim3(kWave), 0, s, T, ldt, W, ldw, (float*)workspace, (int)NW, K, kchunk, ntile)
-#define RECMV_TT2(NTT) \
-  case NTT: if (swap) RECMV_TT(NTT, true); else RECMV_TT(NTT, false); break
-    switch (NT) {
-      RECMV_TT2(1);
-      RECMV_TT2(2);
-      RECMV_TT2(3);
-      default: RECMV_TT2(4);
-    }
-#undef RECMV_TT2
-#undef RECMV_TT
-  } else if (!bf3_tn && tn_occ() && a_vec && b_vec && lda >= ((M + 3) & ~3ll) && ldb >= ((N + 3) & ~3ll) && M >= 4 && N >= 4) {
-    kchunk = ceil_div(ceil_div(K, splits), 16) * 16;
-    hipLaunchKernelGGL(gemm_tn_occ_kernel<16>, dim3((unsigned)(nbm * nbn * splits)), dim3(kBlk), 2 * 16 * LDM * 4, s, A, lda,
-                       B, ldb, (float*)workspace, (int)M, (int)N, K, nbm, nbn, kchunk);
-  } else if (!bf3_tn && tn_occ() && skinny_routes() && M > 4 && N > 4) {
-    // a leading dimension that is no multiple of 4 or an unaligned base: the same kernel with staging loads that need only dword
-    // alignment (1.03-1.2x per launch)
-    // (split lengths rounded to 32 rows like the kernel it replaces, not to 16: the launch keeps its bits)
-    log_shape("tn_occ_scal", "tn_kernel<false>", M, N, K, lda, ldb, A, B, false, false, false);
-    hipLaunchKernelGGL((gemm_tn_occ_kernel<16, true>), dim3((unsigned)(nbm * nbn * splits)), dim3(kBlk), 2 * 16 * LDM * 4, s, A, lda,
-                       B, ldb, (float*)workspace, (int)M, (int)N, K, nbm, nbn, kchunk);
-  } else if (bf3_tn)
-    hipLaunchKernelGGL(gemm_tn_kernel<true>, dim3((unsigned)(nbm * nbn * splits)), dim3(kBlk), kTnLds, s, A, lda, B,
-                       ldb, (float*)workspace, (int)M, (int)N, K, nbm, nbn, kchunk, a_vec, b_vec);
-  else {
-    log_shape("tn_kernel<false>", "tn_kernel<false>", M, N, K, lda, ldb, A, B, false, false, false);
-    hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3((unsigned)(nbm * nbn * splits)), dim3(kBlk), kTnLds, s, A, lda, B,
-                       ldb, (float*)workspace, (int)M, (int)N, K, nbm, nbn, kchunk, a_vec, b_vec);
-  }
-  rc = check_launch("gemm_tn");
-  }
-  if (rc) return rc;
-  if (N % 4 == 0 && ldc % 4 == 0 && aligned16(C) && aligned16(workspace))
-    hipLaunchKernelGGL(splitk_reduce4_kernel, dim3(stream_grid(M * N / 4, kBlk)), dim3(kBlk), 0, s,
-                       (const float4*)workspace, C, ldc, (int)M, (int)N, splits);
-  else
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(stream_grid(M * N, kBlk)), dim3(kBlk), 0, s,
-                       (const float*)workspace, C, ldc, (int)M, (int)N, splits);
-  return check_launch("gemm_tn/reduce");
-}
-
-extern "C" int recmv_posenc_forward(const float* x, int64_t ldx, float* out, int64_t ldo, int64_t ldo_fill,
-                                    int64_t P, int L, const float* weights_host, float out_scale,
-                                    void* stream) {
-  RECMV_REQUIRE(P >= 0 && L >= 0 && L <= 16, "posenc: bad size (P=%lld, L=%d)", (long long)P, L);
-  if (P == 0) return RECMV_OK;
-  RECMV_REQUIRE(x && out, "posenc: NULL pointer");
-  RECMV_REQUIRE(ldx >= 3 && ldo >= 3 + 6 * L && ldo_fill <= ldo, "posenc: leading dimension too small");
-  hipStream_t s = (hipStream_t)stream;
-  // the 2L annealing weights are python floats in the reference (utils/utils.py:40-46); ship them by value
-  PeWeights hw;
-  for (int i = 0; i < 32; ++i) hw.w[i] = (weights_host && i < 2 * L) ? weights_host[i] : 1.f;
-  hipLaunchKernelGGL(posenc_kernel, dim3(stream_grid(P * (1 + 2 * L), kBlk)), dim3(kBlk), 0, s, x, ldx, out, ldo,
-                     ldo_fill, P, L, hw, out_scale);
-  return check_launch("posenc");
+  return dispatch_nt<false>(c);
 }
 
 // Per-launch HIP-event timing of the MFMA kernels.  recmv_profile_begin() starts recording (events on the launch
 // stream around every gemm_nt / gemm_tn launch); recmv_profile_end() waits for the recorded events and returns, per
-// kernel variant v (0..7: gemm_nt_kernel<T, FAST, AMUL> with v = (T-1) + 2*FAST + 4*AMUL; 8: gemm_tn_occ_kernel / gemm_tn_kernel
+// slot v (route::Slot of gemm_route.h — 0..7: gemm_nt_kernel<T, FAST, AMUL> with v = (T-1) + 2*FAST + 4*AMUL; 8: gemm_tn_occ_kernel / gemm_tn_kernel
 // (the product alone, its split-K reduction pass is not bracketed); 9 / 10: gemm_nt_occ_kernel<false, ...> with 128x128 / 64x128 tiles, 11: gemm_nt_occ_kernel<true, ...>; 12 / 13: gemm_nt_narrow_kernel<true, false, .> / its other instantiations), out[5v] = timed launches, out[5v+1] = their summed duration in seconds, out[5v+2] = their
 // summed algorithmic FLOP (2 M N K), out[5v+3] / out[5v+4] = launches / FLOP of the launches below `min_flops`, which
 // are only counted (bracketing tens of thousands of ~20 us launches with events would perturb the run being timed).
+// A caller with room for fewer than 14 slots (at least 9) gets the later slots folded into those of the kernels they replaced (route::fold_slot).
 extern "C" int recmv_profile_begin(double min_flops) {
   g_prof.recs.clear();
   for (auto& u : g_prof.untimed) u[0] = u[1] = 0.0;
@@ -2254,8 +1592,7 @@ extern "C" int recmv_profile_begin(double min_flops) {
 extern "C" int recmv_profile_bytes(double* out, int n_variants) {
   RECMV_REQUIRE(out && n_variants >= 9, "profile_bytes: need room for 9 variants");
   for (int i = 0; i < n_variants; ++i) out[i] = 0.0;
-  auto slot = [&](int v) { return v < n_variants ? v : (v == 11 ? 7 : (v == 12 ? 2 : (v == 13 ? 6 : 3))); };
-  for (int v = 0; v < 14; ++v) out[slot(v)] += g_prof.timed_bytes[v];
+  for (int v = 0; v < route::kNumSlots; ++v) out[route::fold_slot(v, n_variants)] += g_prof.timed_bytes[v];
   return RECMV_OK;
 }
 
@@ -2264,9 +1601,8 @@ extern "C" int recmv_profile_bytes(double* out, int n_variants) {
 extern "C" int recmv_profile_large(double* out, int n_variants) {
   RECMV_REQUIRE(out && n_variants >= 9, "profile_large: need room for 9 variants");
   for (int i = 0; i < 3 * n_variants; ++i) out[i] = 0.0;
-  auto slot = [&](int v) { return v < n_variants ? v : (v == 11 ? 7 : (v == 12 ? 2 : (v == 13 ? 6 : 3))); };
-  for (int v = 0; v < 14; ++v)
-    for (int q = 0; q < 3; ++q) out[3 * slot(v) + q] += g_prof.large[v][q];
+  for (int v = 0; v < route::kNumSlots; ++v)
+    for (int q = 0; q < 3; ++q) out[3 * route::fold_slot(v, n_variants) + q] += g_prof.large[v][q];
   return RECMV_OK;
 }
 
@@ -2281,9 +1617,8 @@ extern "C" int recmv_profile_end(double* out, int n_variants) {
   g_prof.on = false;
   RECMV_REQUIRE(out && n_variants >= 9, "profile_end: need room for 9 variants");
   for (int i = 0; i < 5 * n_variants; ++i) out[i] = 0.0;
-  // slots 9..11 (the high-occupancy NT kernels) fold into the slots of the kernels they replace for a caller with 9 slots
-  auto slot = [&](int v) { return v < n_variants ? v : (v == 11 ? 7 : (v == 12 ? 2 : (v == 13 ? 6 : 3))); };
-  for (int v = 0; v < 14; ++v) {
+  auto slot = [&](int v) { return route::fold_slot(v, n_variants); };
+  for (int v = 0; v < route::kNumSlots; ++v) {
     out[5 * slot(v) + 3] += g_prof.untimed[v][0];
     out[5 * slot(v) + 4] += g_prof.untimed[v][1];
   }

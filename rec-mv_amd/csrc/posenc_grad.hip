@@ -77,6 +77,42 @@ inline void fill_w(PeW* pw, const float* weights_host, int L) {
   for (int i = 0; i < 32; ++i) pw->w[i] = (weights_host && i < 2 * L) ? weights_host[i] : 1.f;
 }
 
+// ---- the encoding itself
+struct PeWeights {
+  float w[32];  // by-value kernel argument: no H2D copy, graph-capturable
+};
+__global__ __launch_bounds__(kBlk) void posenc_kernel(const float* __restrict__ x, int64_t ldx,
+                                                      float* __restrict__ out, int64_t ldo, int64_t ldo_fill,
+                                                      int64_t P, int L, PeWeights w, float out_scale) {
+  const int nf = 1 + 2 * L;  // identity + (sin,cos) per band
+  const int64_t total = P * nf;
+  for (int64_t e = (int64_t)blockIdx.x * kBlk + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlk) {
+    const int64_t p = e / nf;
+    const int f = (int)(e % nf);
+    const float x0 = x[p * ldx], x1 = x[p * ldx + 1], x2 = x[p * ldx + 2];
+    float* o = out + p * ldo + 3 * f;
+    if (f == 0) {
+      o[0] = x0 * out_scale;
+      o[1] = x1 * out_scale;
+      o[2] = x2 * out_scale;
+      for (int64_t c = 3 * nf; c < ldo_fill; ++c) out[p * ldo + c] = 0.f;
+    } else {
+      const int band = (f - 1) >> 1;
+      const float freq = (float)(1 << band);  // 2**linspace(0, L-1, L): exact powers of two
+      const float wt = w.w[f - 1];
+      float v0, v1, v2;
+      if ((f - 1) & 1) {
+        v0 = cosf(x0 * freq); v1 = cosf(x1 * freq); v2 = cosf(x2 * freq);
+      } else {
+        v0 = sinf(x0 * freq); v1 = sinf(x1 * freq); v2 = sinf(x2 * freq);
+      }
+      o[0] = wt * v0 * out_scale;
+      o[1] = wt * v1 * out_scale;
+      o[2] = wt * v2 * out_scale;
+    }
+  }
+}
+
 }  // namespace
 }  // namespace recmv
 
@@ -105,4 +141,20 @@ extern "C" int recmv_posenc_jvp(const float* x, int64_t ldx, const float* t, int
   hipLaunchKernelGGL(pe_jvp_kernel, dim3(stream_grid(P * (1 + 2 * L), kBlk)), dim3(kBlk), 0, (hipStream_t)stream, x,
                      ldx, t, ldt, out, ldo, P, L, w);
   return check_launch("posenc_jvp");
+}
+
+extern "C" int recmv_posenc_forward(const float* x, int64_t ldx, float* out, int64_t ldo, int64_t ldo_fill,
+                                    int64_t P, int L, const float* weights_host, float out_scale,
+                                    void* stream) {
+  RECMV_REQUIRE(P >= 0 && L >= 0 && L <= 16, "posenc: bad size (P=%lld, L=%d)", (long long)P, L);
+  if (P == 0) return RECMV_OK;
+  RECMV_REQUIRE(x && out, "posenc: NULL pointer");
+  RECMV_REQUIRE(ldx >= 3 && ldo >= 3 + 6 * L && ldo_fill <= ldo, "posenc: leading dimension too small");
+  hipStream_t s = (hipStream_t)stream;
+  // the 2L annealing weights are python floats in the reference (utils/utils.py:40-46); ship them by value
+  PeWeights hw;
+  for (int i = 0; i < 32; ++i) hw.w[i] = (weights_host && i < 2 * L) ? weights_host[i] : 1.f;
+  hipLaunchKernelGGL(posenc_kernel, dim3(stream_grid(P * (1 + 2 * L), kBlk)), dim3(kBlk), 0, s, x, ldx, out, ldo,
+                     ldo_fill, P, L, hw, out_scale);
+  return check_launch("posenc");
 }

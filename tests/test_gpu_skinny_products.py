@@ -1,4 +1,5 @@
-"""The skinny and the unaligned routes of recmv_gemm_nt / recmv_gemm_tn (csrc/gemm_f32.hip), through the ctypes entry points.
+"""The skinny and the unaligned routes of recmv_gemm_nt / recmv_gemm_tn (csrc/gemm_f32.hip, csrc/gemm_tn.hip; which launch takes which
+kernel: the planner of csrc/gemm_route.h), through the ctypes entry points.
 
   NT, N <= 4 (last layers' forward)       gemm_nt_thin_n_kernel
   NT, K <= 4 (their input gradients)      gemm_nt_thin_k_kernel
@@ -13,7 +14,7 @@ of the same operands, and against themselves at another row count; the TN routes
 a padded copy (unaligned).
 
 The aligned MFMA reference of the N <= 4 cases: the same rows, N padded to 128 and K to a multiple of 4.  Which MFMA kernel that is
-depends on the row count (the tile choice of dispatch_nt), and the kernels do not all round alike: the 64 x 32 kernel of the small
+depends on the row count (the tile choice of plan_nt), and the kernels do not all round alike: the 64 x 32 kernel of the small
 launches (up to 40 896 rows here) sums the two halves of every 32-wide K-tile on separate chains, the 64 x 64 and the high-occupancy
 kernels of the larger launches on one.  The skinny kernel takes the order of the kernel its launch had before, so every launch keeps
 its bits: rows compare equal between launches of one regime (63 / 130 / 16 421 rows; 41 000 / 66 001 rows), which the cases below
@@ -22,11 +23,21 @@ The aligned MFMA reference of the K <= 4 cases pads K to 8 (K = 4 itself is a sk
 The skinny TN route keeps the order and the split lengths of the MFMA route, so it is also compared with that route on a copy padded
 to 8 output rows / columns, on top of a second run of itself (run-to-run reproducibility).  The unaligned TN route keeps the split length of the kernel
 it replaces (rounded to 32 rows; the aligned route rounds to 16): equal for the shape tested here (20 005 rows in 128 splits: 160).
+
+The last test replays the route census (tests/gemm_route_cases.py, tests/golden/gemm_routes.json): every case under the default routes
+and under RECMV_GEMM_SKINNY=0 must land in the profile slot and give the bits that the library gave before its routes were planned in
+gemm_route.h.
 """
 import ctypes as C
+import json
+import sys
+from pathlib import Path
 
 import pytest
 import torch
+
+sys.path[:0] = [str(Path(__file__).resolve().parent)]
+import gemm_route_cases as GC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -330,3 +341,25 @@ def test_linear_backward_skinny_layer(N, act):
     _check64(gx, gz @ W.double(), gz.abs() @ W.double().abs(), 1.0, "linear_backward gx N=%d" % N)
     _check64(gW, gz.t() @ x.double(), gz.abs().t() @ x.double().abs(), 1.0, "linear_backward gW N=%d" % N)
     _check64(gb, gz.sum(0), gz.abs().sum(0), 1.0, "linear_backward gb N=%d" % N)
+
+
+# ------------------------------------------------------------------------------------------------ the route census
+def test_routes_keep_the_slot_and_the_bits_of_the_census(monkeypatch):
+    """Every case of gemm_route_cases under the default routes and under RECMV_GEMM_SKINNY=0 (the library reads it at every launch):
+    the slot of a bracketing profile and the digest of the output's bits equal those recorded on an MI355X at the commit before the
+    route planner (tests/golden/gemm_routes.json).  RECMV_GEMM_OCC=0 is read once per process: test_gpu_kernels.py runs it in a child."""
+    census = json.loads((Path(__file__).resolve().parent / "golden" / "gemm_routes.json").read_text())["settings"]
+    wrong = []
+    for setting in ("default", "skinny0"):
+        monkeypatch.delenv("RECMV_GEMM_SKINNY", raising=False)
+        for k, v in GC.SETTINGS[setting].items():
+            monkeypatch.setenv(k, v)
+        assert sorted(census[setting]) == sorted(c["name"] for c in GC.CASES)
+        for c in GC.CASES:
+            want = census[setting][c["name"]]
+            slot, out = GC.profiled_slot(c, DEV)
+            got = GC.digest(out)
+            print("%s %s: slot %d digest %s" % (setting, c["name"], slot, got))
+            if slot != want["slot"] or got != want["digest"]:
+                wrong.append((setting, c["name"], slot, want["slot"], got, want["digest"]))
+    assert not wrong, wrong

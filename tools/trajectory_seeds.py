@@ -33,7 +33,10 @@ CONFIGS = [
     ("no fma contraction in lbs_fused.hip only", {"RECMV_LIB_PATH": os.path.join(LIBDIR, "librecmv_hip_nc_lbs.so")}),
     ("no fma contraction in elementwise.hip + linear_bwd.hip only", {"RECMV_LIB_PATH": os.path.join(LIBDIR, "librecmv_hip_nc_elt.so")}),
     ("no fma contraction in mlp_chain.hip + mlp_jet.hip + posenc_grad.hip only", {"RECMV_LIB_PATH": os.path.join(LIBDIR, "librecmv_hip_nc_mlp.so")}),
-    ("no fma contraction in gemm_f32.hip + mlp_rows.hip only (epilogues, encodings; the MFMA chains stay)",
+    # RECMV_BUILD_TAG=nc_gemm RECMV_NOCONTRACT_FILES=gemm_f32.hip,gemm_tn.hip,mlp_rows.hip,posenc_grad.hip python rec-mv_amd/build.py
+    # (the kernels gemm_f32.hip + mlp_rows.hip held when profiles/r06_trajectory_seeds.txt was taken: the TN products are in gemm_tn.hip
+    # now and the encoding, posenc_kernel, in posenc_grad.hip, whose two derivative kernels come along)
+    ("no fma contraction in gemm_f32.hip + gemm_tn.hip + mlp_rows.hip + posenc_grad.hip only (epilogues, encodings; the MFMA chains stay)",
      {"RECMV_LIB_PATH": os.path.join(LIBDIR, "librecmv_hip_nc_gemm.so")}),
     ("no fma contraction in def_regu.hip only", {"RECMV_LIB_PATH": os.path.join(LIBDIR, "librecmv_hip_nc_regu.so")}),
     ("no fma contraction in grid_sample3d.hip only", {"RECMV_LIB_PATH": os.path.join(LIBDIR, "librecmv_hip_nc_gs.so")}),
