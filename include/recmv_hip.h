@@ -31,7 +31,17 @@ extern "C" {
 #define RECMV_F32 0
 #define RECMV_F64 1
 
-/* ABI version, bumped on any signature change. */
+/* ABI version, bumped when an existing signature changes (recmv/_lib.py checks the number at load).
+ *   v11: the mesh-grid entry points take a recmv_mesh_grid descriptor in place of the grid's loose arguments
+ *        (recmv_mesh_grid_count / _fill, recmv_closest_point_grid, recmv_mesh_intersect_grid_count / _fill,
+ *        recmv_segment_mesh_grid).
+ *   v10: recmv_verts_normals, recmv_hard_phong_shade, recmv_hard_phong_params_floats added.  Added since without a bump (no
+ *        existing signature changed, and _lib.py rejects a library that lacks them): recmv_knn1, recmv_nricp_energy,
+ *        recmv_lap_align_solve, recmv_lap_smooth, recmv_closest_point, recmv_iso_relax, recmv_loop_subdivide,
+ *        recmv_point_mesh_nearest, recmv_collision_push, recmv_curve_tubes, recmv_curve_fit_step, the mesh-grid entry points,
+ *        recmv_mesh_intersect_brute, recmv_segment_mesh_brute and their workspace sizes.
+ *   v9: recmv_lbs_jet_* added.  v8: recmv_cam_* added.  v7: recmv_get_sampler_mode, recmv_set_jet_fill added.
+ *   v6: recmv_def_regu, recmv_b3_*, recmv_mlp_rows_*, recmv_mc_run_batch added.  v5: second weight set + split_row in recmv_mlp. */
 int recmv_abi_version(void);
 /* 1 when every kernel of the library was built without packed-f32 VALU instructions (RECMV_NO_PACKED_F32=1 at build time): the build
  * the optional bf16x6 matrix mode needs — beside its NT product kernels, waves executing v_pk_*_f32 were caught computing wrong values in
@@ -734,39 +744,46 @@ int recmv_curve_fit_step(const float* center, const float* dirs, const float* in
                          float* g_scale, float* g_nx_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Uniform grid over a triangle mesh and the exact closest point through it (csrc/mesh_grid.hip; added to ABI v10, no
- * existing signature changed).  Not in the reference: the search of the evaluation metrics (recmv/metrics.py, eval_fl.py).
- * Integer atomics only.  The grid is nx x ny x nz cubic cells of size cell_size with its corner at origin (three floats on
- * the HOST), chosen by the caller so that it covers the mesh; cell (x, y, z) has index (z ny + y) nx + x; at most 2^26
- * cells.  A coordinate outside the grid is clamped into its edge cells.  Argument errors (negative sizes, NULL pointers
- * with non-zero sizes, dims below 1, a cell size that is not positive and finite) are found before any HIP call.
- * recmv_mesh_grid_count: counts [cells] int32 = the faces of verts [V,3] f32 / faces [F,3] int64 whose axis-aligned box
- *   overlaps each cell (conservative; a face with an index outside [0, V) is binned nowhere), total [1] int64 (device,
- *   8-byte aligned) = their sum, the number of (cell, face) entries.  Both are zeroed by the call.
- * recmv_mesh_grid_fill: offsets [cells + 1] int32 = the exclusive scan of counts (offsets[cells] the total, which must be
- *   below 2^31), entries [capacity] int32 = the face ids of cell c at offsets[c] .. offsets[c + 1] (in an order that
- *   depends on scheduling; a slot at or beyond capacity is not written), tris [F,12] f32 (16-byte aligned) = every face as
- *   (a, b - a, c - a, 0, 0, 0).  Same grid arguments as the count call.  Workspace:
- *   recmv_mesh_grid_workspace_bytes(cells), 4-byte aligned.
- * recmv_closest_point_grid: recmv_closest_point's outputs for the query points p [P,3] f32 — face [P] int64 (-1: none),
- *   point [P,3] f32, dist2 [P] f32, ties to the lowest face id, bit for bit what recmv_closest_point gives on the mesh
- *   the grid was built from — by visiting the Chebyshev rings of cells around the query's cell until everything outside
- *   them is farther than the best found.  order: NULL, or a permutation [P] int64 of the queries (thread t handles
- *   query order[t]: sorted by cell, neighbouring lanes read the same cells); lanes: 1, 8 or 64 lanes of a wave per query.
- *   P = 0 is a no-op, F = 0 an argument error.
+ * Uniform grid over a triangle mesh and the exact closest point through it (csrc/mesh_grid.hip).  Not in the reference: the
+ * search of the evaluation metrics (recmv/metrics.py, eval_fl.py).  Integer atomics only.  One struct recmv_mesh_grid in HOST
+ * memory describes a grid to the entry points below and to the queries of the next two sections (ABI v11):
+ *   geometry: nx x ny x nz cubic cells of size cell_size with the corner at origin, chosen by the caller so that it covers
+ *     the mesh; cell (x, y, z) has index (z ny + y) nx + x; at most 2^26 cells; a coordinate outside is clamped to the edge.
+ *   tables (device): offsets [cells + 1] int32, entries [n_entries] int32 with n_entries < 2^31 — the face ids of cell c at
+ *     offsets[c] .. offsets[c + 1] — and tris [F,12] f32, 16-byte aligned: every face as (a, b - a, c - a, 0, 0, 0).
+ * Every entry point checks the geometry, n_entries and the tables it reads or writes before any HIP call, like its other
+ * arguments (negative sizes, NULL pointers with non-zero sizes); a NULL descriptor is an argument error.
+ * recmv_mesh_grid_count [reads the geometry]: counts [cells] int32 = the faces of verts [V,3] f32 / faces [F,3] int64 whose
+ *   axis-aligned box overlaps each cell (conservative; a face with an index outside [0, V) is binned nowhere), total [1] int64
+ *   (device, 8-byte aligned) = their sum, the number of (cell, face) entries.  Both are zeroed by the call.
+ * recmv_mesh_grid_fill [reads the geometry and n_entries, the CAPACITY of entries; writes through offsets, entries, tris]:
+ *   offsets = the exclusive scan of counts (offsets[cells] the total, which must be below 2^31), entries in an order that
+ *   depends on scheduling (a slot at or beyond the capacity is not written), tris.  The geometry of the count call.
+ *   Workspace: recmv_mesh_grid_workspace_bytes(cells), 4-byte aligned.
+ * recmv_closest_point_grid [reads the geometry and every table]: recmv_closest_point's outputs for the query points p [P,3]
+ *   f32 — face [P] int64 (-1: none), point [P,3] f32, dist2 [P] f32, ties to the lowest face id, bit for bit what
+ *   recmv_closest_point gives on the mesh of F faces the grid was built from — by visiting the Chebyshev rings of cells
+ *   around the query's cell until everything outside them is farther than the best found.  order: NULL, or a permutation [P]
+ *   int64 of the queries (thread t handles query order[t]: sorted by cell, neighbouring lanes read the same cells); lanes:
+ *   1, 8 or 64 lanes of a wave per query.  P = 0 is a no-op, F = 0 an argument error.
  * ---------------------------------------------------------------------------------------------- */
+typedef struct recmv_mesh_grid {
+  float origin[3];
+  float cell_size;
+  int64_t nx, ny, nz;
+  int32_t* offsets;
+  int32_t* entries;
+  int64_t n_entries;
+  float* tris;
+} recmv_mesh_grid;
+
 int64_t recmv_mesh_grid_workspace_bytes(int64_t cells);
-int recmv_mesh_grid_count(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* origin,
-                          float cell_size, int64_t nx, int64_t ny, int64_t nz, int32_t* counts, int64_t* total,
-                          void* stream);
-int recmv_mesh_grid_fill(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* origin,
-                         float cell_size, int64_t nx, int64_t ny, int64_t nz, const int32_t* counts, int32_t* offsets,
-                         int32_t* entries, int64_t capacity, float* tris, void* workspace, int64_t workspace_bytes,
-                         void* stream);
-int recmv_closest_point_grid(const float* p, int64_t P, const int64_t* order, const float* tris, int64_t F,
-                             const int32_t* offsets, const int32_t* entries, int64_t n_entries, const float* origin,
-                             float cell_size, int64_t nx, int64_t ny, int64_t nz, int32_t lanes, int64_t* face,
-                             float* point, float* dist2, void* stream);
+int recmv_mesh_grid_count(const float* verts, int64_t V, const int64_t* faces, int64_t F, const recmv_mesh_grid* grid,
+                          int32_t* counts, int64_t* total, void* stream);
+int recmv_mesh_grid_fill(const float* verts, int64_t V, const int64_t* faces, int64_t F, const recmv_mesh_grid* grid,
+                         const int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+int recmv_closest_point_grid(const float* p, int64_t P, const int64_t* order, int64_t F, const recmv_mesh_grid* grid,
+                             int32_t lanes, int64_t* face, float* point, float* dist2, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Which faces of two triangle meshes cross (csrc/mesh_intersect.hip, csrc/tri_tri.h; added to ABI v10, no existing
@@ -783,9 +800,9 @@ int recmv_closest_point_grid(const float* p, int64_t P, const int64_t* order, co
  *   slot below their face's end and below capacity (0 when the passes agree and capacity >= total) — they are not written.
  * recmv_mesh_intersect_brute: every pair of faces.  counts and total given, offsets NULL: the count pass; offsets given,
  *   counts NULL: the fill pass.
- * recmv_mesh_intersect_grid_count / _fill: through the grid built over B by recmv_mesh_grid_count / _fill (cell_offsets
- *   [cells + 1], entries [n_entries], the grid arguments of those calls): the same pairs as the brute force.  lanes: 1, 8 or
- *   64 lanes of a wave per face of A; it does not change the result.
+ * recmv_mesh_intersect_grid_count / _fill: through the grid built over B by recmv_mesh_grid_count / _fill (reads the
+ *   descriptor's geometry, offsets, entries and n_entries; not tris): the same pairs as the brute force.  lanes: 1, 8 or 64
+ *   lanes of a wave per face of A; it does not change the result.
  * Argument errors are found before any HIP call.  An empty A or B gives no pair (counts and total zeroed).
  * ---------------------------------------------------------------------------------------------- */
 int recmv_mesh_intersect_brute(const float* a_verts, int64_t VA, const int64_t* a_faces, int64_t FA, const float* b_verts,
@@ -794,15 +811,13 @@ int recmv_mesh_intersect_brute(const float* a_verts, int64_t VA, const int64_t* 
                                int32_t* cursor, int64_t* dropped, void* stream);
 int recmv_mesh_intersect_grid_count(const float* a_verts, int64_t VA, const int64_t* a_faces, int64_t FA,
                                     const float* b_verts, int64_t VB, const int64_t* b_faces, int64_t FB,
-                                    const int32_t* cell_offsets, const int32_t* entries, int64_t n_entries,
-                                    const float* origin, float cell_size, int64_t nx, int64_t ny, int64_t nz, int32_t lanes,
-                                    int32_t self_mode, int32_t skip_shared, int32_t* counts, int64_t* total, void* stream);
+                                    const recmv_mesh_grid* grid, int32_t lanes, int32_t self_mode, int32_t skip_shared,
+                                    int32_t* counts, int64_t* total, void* stream);
 int recmv_mesh_intersect_grid_fill(const float* a_verts, int64_t VA, const int64_t* a_faces, int64_t FA,
                                    const float* b_verts, int64_t VB, const int64_t* b_faces, int64_t FB,
-                                   const int32_t* cell_offsets, const int32_t* entries, int64_t n_entries,
-                                   const float* origin, float cell_size, int64_t nx, int64_t ny, int64_t nz, int32_t lanes,
-                                   int32_t self_mode, int32_t skip_shared, const int32_t* offsets, int32_t* pairs,
-                                   int64_t capacity, int32_t* cursor, int64_t* dropped, void* stream);
+                                   const recmv_mesh_grid* grid, int32_t lanes, int32_t self_mode, int32_t skip_shared,
+                                   const int32_t* offsets, int32_t* pairs, int64_t capacity, int32_t* cursor,
+                                   int64_t* dropped, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Segments against a triangle mesh (csrc/segment_mesh.hip, csrc/seg_tri.h; added to ABI v10, no existing signature
@@ -818,9 +833,9 @@ int recmv_mesh_intersect_grid_fill(const float* a_verts, int64_t VA, const int64
  * Outputs: face [S] int64 = the hit with the smallest t, ties to the lowest face id (-1: none), t [S] f32 (NaN: none),
  *   count [S] int32 = the number of faces hit.  No atomics.  S = 0 is a no-op; F = 0 hits nothing.
  * recmv_segment_mesh_brute: every face.
- * recmv_segment_mesh_grid: through the grid built over the mesh by recmv_mesh_grid_count / _fill (cell_offsets [cells + 1],
- *   entries [n_entries], the grid arguments of those calls): bit for bit the brute force's outputs.  lanes: 1, 8 or 64 lanes
- *   of a wave per segment; it does not change the result.  want_count = 1: the whole segment is walked and count written;
+ * recmv_segment_mesh_grid: through the grid built over the mesh by recmv_mesh_grid_count / _fill (reads the descriptor's
+ *   geometry, offsets, entries and n_entries; not tris): bit for bit the brute force's outputs.  lanes: 1, 8 or 64 lanes of a
+ *   wave per segment; it does not change the result.  want_count = 1: the whole segment is walked and count written;
  *   want_count = 0: the walk may stop behind the first hit, count is not written and may be NULL.
  * Argument errors (negative sizes, NULL pointers, lanes, dims below 1, a cell size that is not positive and finite,
  * want_count = 1 without count) are found before any HIP call.
@@ -828,9 +843,8 @@ int recmv_mesh_intersect_grid_fill(const float* a_verts, int64_t VA, const int64
 int recmv_segment_mesh_brute(const float* p, const float* q, int64_t S, const float* verts, int64_t V, const int64_t* faces,
                              int64_t F, int64_t* face, float* t, int32_t* count, void* stream);
 int recmv_segment_mesh_grid(const float* p, const float* q, int64_t S, const float* verts, int64_t V, const int64_t* faces,
-                            int64_t F, const int32_t* cell_offsets, const int32_t* entries, int64_t n_entries,
-                            const float* origin, float cell_size, int64_t nx, int64_t ny, int64_t nz, int32_t lanes,
-                            int32_t want_count, int64_t* face, float* t, int32_t* count, void* stream);
+                            int64_t F, const recmv_mesh_grid* grid, int32_t lanes, int32_t want_count, int64_t* face, float* t,
+                            int32_t* count, void* stream);
 
 #ifdef __cplusplus
 }

@@ -56,60 +56,3 @@ __device__ __forceinline__ bool load_tri(const float* __restrict__ v, const int6
   q.cx = v[3 * i2] - q.ax; q.cy = v[3 * i2 + 1] - q.ay; q.cz = v[3 * i2 + 2] - q.az;
   return true;
 }
-
-// ---- the uniform grid over a mesh: what its binning (mesh_grid.hip) and every query on it (mesh_grid.hip's closest point,
-// mesh_intersect.hip's triangle pairs) must compute alike.  Kept in this header, beside load_tri, because
-// tools/mesh_grid_host_check compiles mesh_grid.hip for the host with this header alone beside it. ----------------------------
-struct Grid {
-  float ox, oy, oz, h, inv_h;
-  int nx, ny, nz;
-};
-
-struct Range {
-  int x0, x1, y0, y1, z0, z1;
-};
-
-// A coordinate in cell units relative to the grid's origin: the ONE expression binning and query share.
-__device__ __forceinline__ float cell_coord(float x, float o, float inv_h) { return (x - o) * inv_h; }
-
-// The cell of a coordinate in cell units, clamped into [0, n) (NaN gives 0: fmaxf returns its other argument).
-__device__ __forceinline__ int cell_index(float u, int n) {
-  return (int)fminf(fmaxf(floorf(u), 0.f), (float)(n - 1));
-}
-
-// The cells face k's axis-aligned box overlaps (false: an index outside [0, V), the face is binned nowhere).  Used by the
-// count and the fill pass alike.
-__device__ __forceinline__ bool face_range(const float* __restrict__ v, const int64_t* __restrict__ f, int64_t V,
-                                           int64_t k, const Grid& g, Range& r) {
-  const int64_t i0 = f[3 * k], i1 = f[3 * k + 1], i2 = f[3 * k + 2];
-  if ((uint64_t)i0 >= (uint64_t)V || (uint64_t)i1 >= (uint64_t)V || (uint64_t)i2 >= (uint64_t)V) return false;
-  const float ax = v[3 * i0], ay = v[3 * i0 + 1], az = v[3 * i0 + 2];
-  const float bx = v[3 * i1], by = v[3 * i1 + 1], bz = v[3 * i1 + 2];
-  const float cx = v[3 * i2], cy = v[3 * i2 + 1], cz = v[3 * i2 + 2];
-  r.x0 = cell_index(cell_coord(fminf(fminf(ax, bx), cx), g.ox, g.inv_h), g.nx);
-  r.x1 = cell_index(cell_coord(fmaxf(fmaxf(ax, bx), cx), g.ox, g.inv_h), g.nx);
-  r.y0 = cell_index(cell_coord(fminf(fminf(ay, by), cy), g.oy, g.inv_h), g.ny);
-  r.y1 = cell_index(cell_coord(fmaxf(fmaxf(ay, by), cy), g.oy, g.inv_h), g.ny);
-  r.z0 = cell_index(cell_coord(fminf(fminf(az, bz), cz), g.oz, g.inv_h), g.nz);
-  r.z1 = cell_index(cell_coord(fmaxf(fmaxf(az, bz), cz), g.oz, g.inv_h), g.nz);
-  if (r.x1 < r.x0) r.x1 = r.x0;                            // (non-finite coordinates)
-  if (r.y1 < r.y0) r.y1 = r.y0;
-  if (r.z1 < r.z0) r.z1 = r.z0;
-  return true;
-}
-
-__device__ __forceinline__ int64_t range_cells(const Range& r) {
-  return (int64_t)(r.x1 - r.x0 + 1) * (r.y1 - r.y0 + 1) * (r.z1 - r.z0 + 1);
-}
-
-// The triangle table of a grid: face k as (a, b - a, c - a) — load_tri's values — in three float4, the last three floats 0.
-__device__ __forceinline__ void tri_table_store(float4* __restrict__ tris, int64_t k, const Tri& q) {
-  tris[3 * k] = make_float4(q.ax, q.ay, q.az, q.bx);
-  tris[3 * k + 1] = make_float4(q.by, q.bz, q.cx, q.cy);
-  tris[3 * k + 2] = make_float4(q.cz, 0.f, 0.f, 0.f);
-}
-
-__device__ __forceinline__ Tri tri_table_load(const float4* __restrict__ tris, int64_t k) {
-  const float4 t0 = tris[3 * k], t1 = tris[3 * k + 1], t2 = tris[3 * k + 2];
-  return Tri{t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x};
-}

@@ -28,7 +28,8 @@ namespace {
 
 #pragma clang fp contract(off)
 
-#include "closest_tri.h"                                   // Tri, closest_st, load_tri; Grid, Range, face_range, the table
+#include "closest_tri.h"                                   // Tri, closest_st, load_tri
+#include "grid_query.h"                                    // Grid, Range, face_range, the table; GridView, for_each_entry
 
 constexpr int kGridBlock = 256;
 constexpr int kBigFace = 256;                              // cells of a face's range above which its wave shares the work
@@ -44,21 +45,21 @@ __device__ __forceinline__ void for_each_cell(const Range& r, bool valid, int fa
   if (valid && !big) {
     for (int z = r.z0; z <= r.z1; ++z)
       for (int y = r.y0; y <= r.y1; ++y)
-        for (int x = r.x0; x <= r.x1; ++x) op((z * g.ny + y) * g.nx + x, face);
+        for (int x = r.x0; x <= r.x1; ++x) op(cell_id(g, x, y, z), face);
   }
   unsigned long long m = __ballot(big);
   const int lane = threadIdx.x % kWave;
   while (m) {
     const int src = __ffsll((long long)m) - 1;
     m &= m - 1;
-    const int x0 = __shfl(r.x0, src, kWave), y0 = __shfl(r.y0, src, kWave), z0 = __shfl(r.z0, src, kWave);
-    const int wx = __shfl(r.x1, src, kWave) - x0 + 1, wy = __shfl(r.y1, src, kWave) - y0 + 1;
-    const int wz = __shfl(r.z1, src, kWave) - z0 + 1;
+    const Range b{__shfl(r.x0, src, kWave), __shfl(r.x1, src, kWave), __shfl(r.y0, src, kWave),
+                  __shfl(r.y1, src, kWave), __shfl(r.z0, src, kWave), __shfl(r.z1, src, kWave)};
     const int fk = __shfl(face, src, kWave);
-    const int64_t n = (int64_t)wx * wy * wz;
+    const int64_t n = range_cells(b);
     for (int64_t c = lane; c < n; c += kWave) {
-      const int x = x0 + (int)(c % wx), y = y0 + (int)((c / wx) % wy), z = z0 + (int)(c / ((int64_t)wx * wy));
-      op((z * g.ny + y) * g.nx + x, fk);
+      int x, y, z;
+      range_cell(b, c, x, y, z);
+      op(cell_id(g, x, y, z), fk);
     }
   }
 }
@@ -245,9 +246,9 @@ __device__ __forceinline__ float axis_gap(float u, int i, int n) {
 template <int G>
 __global__ void __launch_bounds__(kGridBlock)
 closest_point_grid_kernel(const float* __restrict__ p, int64_t P, const int64_t* __restrict__ order,
-                          const float4* __restrict__ tris, int64_t F, const int32_t* __restrict__ offsets,
-                          const int32_t* __restrict__ entries, int64_t n_entries, Grid g, int64_t* __restrict__ face,
+                          const float4* __restrict__ tris, int64_t F, GridView view, int64_t* __restrict__ face,
                           float* __restrict__ point, float* __restrict__ dist2) {
+  const Grid& g = view.g;
   const int64_t slot = ((int64_t)blockIdx.x * kGridBlock + threadIdx.x) / G;
   const int sub = threadIdx.x % G;
   if (slot >= P) return;                                   // (a whole group at once: slot is the same in its lanes)
@@ -270,17 +271,11 @@ closest_point_grid_kernel(const float* __restrict__ p, int64_t P, const int64_t*
       shell_cell(k, r, cx, cy, cz, x, y, z);
       if ((unsigned)x >= (unsigned)g.nx || (unsigned)y >= (unsigned)g.ny || (unsigned)z >= (unsigned)g.nz) continue;
       if (lower_bound2(axis_gap(ux, x, g.nx), axis_gap(uy, y, g.ny), axis_gap(uz, z, g.nz), mu, m2, g.h) > best) continue;
-      const int cell = (z * g.ny + y) * g.nx + x;
-      int e0 = offsets[cell], e1 = offsets[cell + 1];
-      if (e0 < 0) e0 = 0;
-      if ((int64_t)e1 > n_entries) e1 = (int)n_entries;
-      for (int e = e0; e < e1; ++e) {
-        const int k2 = entries[e];
-        if ((uint64_t)k2 >= (uint64_t)F) continue;
+      for_each_entry(view, cell_id(g, x, y, z), F, [&](int k2) {
         const Tri q = tri_table_load(tris, k2);
         float s, t;
         take_min(closest_st(px, py, pz, q, s, t), k2, best, bidx);
-      }
+      });
     }
 #pragma unroll
     for (int off = G / 2; off > 0; off >>= 1) {            // the group's minimum, in every lane of it
@@ -324,67 +319,46 @@ closest_point_grid_kernel(const float* __restrict__ p, int64_t P, const int64_t*
 
 using namespace recmv;
 
-namespace {
-
-constexpr int64_t kMaxCells = 1ll << 26;
-
-// the grid's arguments, checked before any HIP call (0: fine)
-int grid_args(const char* what, const float* origin, float h, int64_t nx, int64_t ny, int64_t nz, Grid& g) {
-  RECMV_REQUIRE(origin, "%s: NULL origin", what);
-  RECMV_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1, "%s: dims=(%lld,%lld,%lld) must be at least 1", what, (long long)nx,
-                (long long)ny, (long long)nz);
-  RECMV_REQUIRE(h > 0.f && h < __builtin_inff(), "%s: cell size %g must be positive and finite", what, (double)h);
-  RECMV_REQUIRE(nx <= kMaxCells && ny <= kMaxCells && nz <= kMaxCells && nx * ny * nz <= kMaxCells,
-                "%s: at most 2^26 cells", what);
-  g = Grid{origin[0], origin[1], origin[2], h, 1.f / h, (int)nx, (int)ny, (int)nz};
-  return RECMV_OK;
-}
-
-}  // namespace
+#include "mesh_grid_host.h"                                // grid_view_args, lanes_ok, with_lanes
 
 extern "C" int64_t recmv_mesh_grid_workspace_bytes(int64_t cells) {
   return cells > 0 ? (cells + ceil_div(cells, kScanTile)) * (int64_t)sizeof(int32_t) : 0;
 }
 
-extern "C" int recmv_mesh_grid_count(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* origin,
-                                     float cell_size, int64_t nx, int64_t ny, int64_t nz, int32_t* counts,
-                                     int64_t* total, void* stream) {
+extern "C" int recmv_mesh_grid_count(const float* verts, int64_t V, const int64_t* faces, int64_t F,
+                                     const recmv_mesh_grid* grid, int32_t* counts, int64_t* total, void* stream) {
   RECMV_REQUIRE(V >= 0 && F >= 0, "mesh_grid_count: V=%lld, F=%lld must not be negative", (long long)V, (long long)F);
   RECMV_REQUIRE(F < (1ll << 31), "mesh_grid_count: at most 2^31 - 1 faces");
-  Grid g;
-  int rc = grid_args("mesh_grid_count", origin, cell_size, nx, ny, nz, g);
+  GridView view;
+  int rc = grid_view_args("mesh_grid_count", grid, kGridGeometry, view);
   if (rc != RECMV_OK) return rc;
   RECMV_REQUIRE(counts && total, "mesh_grid_count: NULL output pointer");
   RECMV_REQUIRE(F == 0 || (faces && (V == 0 || verts)), "mesh_grid_count: NULL mesh pointer");
   RECMV_REQUIRE(((uintptr_t)total & 7) == 0, "mesh_grid_count: total must be 8-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  RECMV_HIP_TRY(hipMemsetAsync(counts, 0, (size_t)(nx * ny * nz) * sizeof(int32_t), s));
+  RECMV_HIP_TRY(hipMemsetAsync(counts, 0, (size_t)(grid->nx * grid->ny * grid->nz) * sizeof(int32_t), s));
   RECMV_HIP_TRY(hipMemsetAsync(total, 0, sizeof(int64_t), s));
   if (F == 0) return RECMV_OK;
-  grid_count_kernel<<<stream_grid(F, kGridBlock), kGridBlock, 0, s>>>(verts, V, faces, F, g, counts,
+  grid_count_kernel<<<stream_grid(F, kGridBlock), kGridBlock, 0, s>>>(verts, V, faces, F, view.g, counts,
                                                                        (unsigned long long*)total);
   return check_launch("mesh_grid_count");
 }
 
-extern "C" int recmv_mesh_grid_fill(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* origin,
-                                    float cell_size, int64_t nx, int64_t ny, int64_t nz, const int32_t* counts,
-                                    int32_t* offsets, int32_t* entries, int64_t capacity, float* tris, void* workspace,
+extern "C" int recmv_mesh_grid_fill(const float* verts, int64_t V, const int64_t* faces, int64_t F,
+                                    const recmv_mesh_grid* grid, const int32_t* counts, void* workspace,
                                     int64_t workspace_bytes, void* stream) {
-  RECMV_REQUIRE(V >= 0 && F >= 0 && capacity >= 0, "mesh_grid_fill: V=%lld, F=%lld, capacity=%lld must not be negative",
-                (long long)V, (long long)F, (long long)capacity);
-  RECMV_REQUIRE(F < (1ll << 31) && capacity < (1ll << 31), "mesh_grid_fill: at most 2^31 - 1 faces and entries");
-  Grid g;
-  int rc = grid_args("mesh_grid_fill", origin, cell_size, nx, ny, nz, g);
+  RECMV_REQUIRE(V >= 0 && F >= 0, "mesh_grid_fill: V=%lld, F=%lld must not be negative", (long long)V, (long long)F);
+  RECMV_REQUIRE(F < (1ll << 31), "mesh_grid_fill: at most 2^31 - 1 faces");
+  GridView view;
+  int rc = grid_view_args("mesh_grid_fill", grid, kGridTables | (F ? kGridTris : 0), view);
   if (rc != RECMV_OK) return rc;
-  const int64_t cells = nx * ny * nz;
-  RECMV_REQUIRE(counts && offsets && workspace, "mesh_grid_fill: NULL pointer");
-  RECMV_REQUIRE(capacity == 0 || entries, "mesh_grid_fill: NULL entries");
-  RECMV_REQUIRE(F == 0 || (faces && tris && (V == 0 || verts)), "mesh_grid_fill: NULL mesh pointer");
+  const int64_t cells = grid->nx * grid->ny * grid->nz;
+  RECMV_REQUIRE(counts && workspace, "mesh_grid_fill: NULL pointer");
+  RECMV_REQUIRE(F == 0 || (faces && (V == 0 || verts)), "mesh_grid_fill: NULL mesh pointer");
   RECMV_REQUIRE(workspace_bytes >= recmv_mesh_grid_workspace_bytes(cells),
                 "mesh_grid_fill: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
                 (long long)recmv_mesh_grid_workspace_bytes(cells));
-  RECMV_REQUIRE(((uintptr_t)workspace & 3) == 0 && ((uintptr_t)tris & 15) == 0,
-                "mesh_grid_fill: workspace must be 4-byte and tris 16-byte aligned");
+  RECMV_REQUIRE(((uintptr_t)workspace & 3) == 0, "mesh_grid_fill: workspace must be 4-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   int32_t* cursor = (int32_t*)workspace;
   int32_t* sums = cursor + cells;
@@ -392,46 +366,37 @@ extern "C" int recmv_mesh_grid_fill(const float* verts, int64_t V, const int64_t
   scan_sums_kernel<<<(unsigned)nb, kGridBlock, 0, s>>>(counts, cells, sums);
   rc = check_launch("mesh_grid_scan_sums");
   if (rc != RECMV_OK) return rc;
-  scan_of_sums_kernel<<<1, kGridBlock, 0, s>>>(sums, nb, offsets + cells);
+  scan_of_sums_kernel<<<1, kGridBlock, 0, s>>>(sums, nb, grid->offsets + cells);
   rc = check_launch("mesh_grid_scan_of_sums");
   if (rc != RECMV_OK) return rc;
-  scan_apply_kernel<<<(unsigned)nb, kGridBlock, 0, s>>>(counts, cells, sums, offsets, cursor);
+  scan_apply_kernel<<<(unsigned)nb, kGridBlock, 0, s>>>(counts, cells, sums, grid->offsets, cursor);
   rc = check_launch("mesh_grid_scan_apply");
   if (rc != RECMV_OK || F == 0) return rc;
-  grid_fill_kernel<<<stream_grid(F, kGridBlock), kGridBlock, 0, s>>>(verts, V, faces, F, g, offsets, cursor, entries,
-                                                                      capacity, (float4*)tris);
+  grid_fill_kernel<<<stream_grid(F, kGridBlock), kGridBlock, 0, s>>>(verts, V, faces, F, view.g, grid->offsets, cursor,
+                                                                      grid->entries, grid->n_entries, (float4*)grid->tris);
   return check_launch("mesh_grid_fill");
 }
 
-extern "C" int recmv_closest_point_grid(const float* p, int64_t P, const int64_t* order, const float* tris, int64_t F,
-                                        const int32_t* offsets, const int32_t* entries, int64_t n_entries,
-                                        const float* origin, float cell_size, int64_t nx, int64_t ny, int64_t nz,
-                                        int32_t lanes, int64_t* face, float* point, float* dist2, void* stream) {
-  RECMV_REQUIRE(P >= 0 && n_entries >= 0, "closest_point_grid: P=%lld, entries=%lld must not be negative", (long long)P,
-                (long long)n_entries);
-  RECMV_REQUIRE(F > 0, "closest_point_grid: F=%lld: the surface must not be empty", (long long)F);
-  RECMV_REQUIRE(F < (1ll << 31) && n_entries < (1ll << 31) && P < (1ll << 40),
-                "closest_point_grid: at most 2^31 - 1 faces and entries");
-  RECMV_REQUIRE(lanes == 1 || lanes == 8 || lanes == 64, "closest_point_grid: lanes=%d must be 1, 8 or 64", (int)lanes);
-  Grid g;
-  int rc = grid_args("closest_point_grid", origin, cell_size, nx, ny, nz, g);
+extern "C" int recmv_closest_point_grid(const float* p, int64_t P, const int64_t* order, int64_t F,
+                                        const recmv_mesh_grid* grid, int32_t lanes, int64_t* face, float* point,
+                                        float* dist2, void* stream) {
+  const char* what = "closest_point_grid";
+  RECMV_REQUIRE(P >= 0 && P < (1ll << 40), "%s: P=%lld must be in [0, 2^40)", what, (long long)P);
+  RECMV_REQUIRE(F > 0, "%s: F=%lld: the surface must not be empty", what, (long long)F);
+  RECMV_REQUIRE(F < (1ll << 31), "%s: at most 2^31 - 1 faces", what);
+  int rc = lanes_ok(what, lanes);
   if (rc != RECMV_OK) return rc;
-  if (P == 0) return RECMV_OK;
-  RECMV_REQUIRE(p && tris && offsets && face && point && dist2, "closest_point_grid: NULL pointer");
-  RECMV_REQUIRE(n_entries == 0 || entries, "closest_point_grid: NULL entries");
-  RECMV_REQUIRE(((uintptr_t)tris & 15) == 0, "closest_point_grid: tris must be 16-byte aligned");
+  GridView view;
+  rc = grid_view_args(what, grid, P ? kGridTables | kGridTris : kGridGeometry, view);
+  if (rc != RECMV_OK || P == 0) return rc;
+  RECMV_REQUIRE(p && face && point && dist2, "%s: NULL pointer", what);
   const int64_t nb = ceil_div(P * lanes, kGridBlock);
-  RECMV_REQUIRE(nb < (1ll << 31), "closest_point_grid: too many query points");
+  RECMV_REQUIRE(nb < (1ll << 31), "%s: too many query points", what);
   hipStream_t s = (hipStream_t)stream;
-  const float4* t4 = (const float4*)tris;
-  if (lanes == 1)
-    closest_point_grid_kernel<1><<<(unsigned)nb, kGridBlock, 0, s>>>(p, P, order, t4, F, offsets, entries, n_entries, g,
-                                                                     face, point, dist2);
-  else if (lanes == 8)
-    closest_point_grid_kernel<8><<<(unsigned)nb, kGridBlock, 0, s>>>(p, P, order, t4, F, offsets, entries, n_entries, g,
-                                                                     face, point, dist2);
-  else
-    closest_point_grid_kernel<64><<<(unsigned)nb, kGridBlock, 0, s>>>(p, P, order, t4, F, offsets, entries, n_entries, g,
-                                                                      face, point, dist2);
-  return check_launch("closest_point_grid");
+  const float4* t4 = (const float4*)grid->tris;
+  with_lanes(lanes, [&](auto G) {
+    closest_point_grid_kernel<decltype(G)::value><<<(unsigned)nb, kGridBlock, 0, s>>>(p, P, order, t4, F, view, face, point,
+                                                                                     dist2);
+  });
+  return check_launch(what);
 }

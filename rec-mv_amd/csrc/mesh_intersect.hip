@@ -29,7 +29,7 @@ namespace {
 
 #pragma clang fp contract(off)
 
-#include "closest_tri.h"                                   // Grid, Range, face_range, range_cells
+#include "grid_query.h"                                    // Grid, Range, face_range, range_cell; GridView, for_each_entry
 #include "tri_tri.h"                                       // Pts, load_pts, tri_boxes_meet, tri_tri_cross
 
 constexpr int kBlock = 256;
@@ -105,9 +105,9 @@ template <int G>
 __global__ void __launch_bounds__(kBlock)
 intersect_grid_kernel(const float* __restrict__ va, int64_t VA, const int64_t* __restrict__ fa, int64_t FA,
                       const float* __restrict__ vb, int64_t VB, const int64_t* __restrict__ fb, int64_t FB,
-                      const int32_t* __restrict__ cell_offsets, const int32_t* __restrict__ entries, int64_t n_entries,
-                      Grid g, int self_mode, int skip_shared, int32_t* __restrict__ counts,
+                      GridView view, int self_mode, int skip_shared, int32_t* __restrict__ counts,
                       unsigned long long* __restrict__ total, Sink sink) {
+  const Grid& g = view.g;
   const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
   const int sub = threadIdx.x % G;
   if (i >= FA) return;                                     // (a whole group at once: i is the same in its lanes)
@@ -116,27 +116,21 @@ intersect_grid_kernel(const float* __restrict__ va, int64_t VA, const int64_t* _
   Range r{0, 0, 0, 0, 0, 0};
   int32_t mine = 0;
   if (load_pts(va, fa, VA, i, ta, a0, a1, a2) && face_range(va, fa, VA, i, g, r)) {
-    const int wx = r.x1 - r.x0 + 1, wy = r.y1 - r.y0 + 1;
     const int64_t n = range_cells(r);                      // at most the grid's cell count: the range is clamped into it
     for (int64_t c = sub; c < n; c += G) {
-      const int x = r.x0 + (int)(c % wx), y = r.y0 + (int)((c / wx) % wy), z = r.z0 + (int)(c / ((int64_t)wx * wy));
-      const int cell = (z * g.ny + y) * g.nx + x;
-      int e0 = cell_offsets[cell], e1 = cell_offsets[cell + 1];
-      if (e0 < 0) e0 = 0;
-      if ((int64_t)e1 > n_entries) e1 = (int)n_entries;
-      for (int e = e0; e < e1; ++e) {
-        const int64_t j = entries[e];
-        if ((uint64_t)j >= (uint64_t)FB) continue;
-        if (self_mode && j <= i) continue;
+      int x, y, z;
+      range_cell(r, c, x, y, z);
+      for_each_entry(view, cell_id(g, x, y, z), FB, [&](int64_t j) {
+        if (self_mode && j <= i) return;
         Range rj;
-        if (!face_range(vb, fb, VB, j, g, rj)) continue;
+        if (!face_range(vb, fb, VB, j, g, rj)) return;
         // the one cell of the pair: per axis the larger of the two lower cell indices
-        if (x != max(r.x0, rj.x0) || y != max(r.y0, rj.y0) || z != max(r.z0, rj.z0)) continue;
+        if (x != max(r.x0, rj.x0) || y != max(r.y0, rj.y0) || z != max(r.z0, rj.z0)) return;
         if (pair_crosses(ta, a0, a1, a2, i, vb, fb, VB, j, self_mode != 0, skip_shared != 0)) {
           ++mine;
           emit(sink, i, j);
         }
-      }
+      });
     }
   }
 #pragma unroll
@@ -152,9 +146,9 @@ intersect_grid_kernel(const float* __restrict__ va, int64_t VA, const int64_t* _
 
 using namespace recmv;
 
-namespace {
+#include "mesh_grid_host.h"                                // grid_view_args, lanes_ok, with_lanes
 
-constexpr int64_t kMaxCells = 1ll << 26;                   // mesh_grid.hip's limit
+namespace {
 
 // the two meshes and the flags, checked before any HIP call (0: fine)
 int mesh_args(const char* what, const float* a_verts, int64_t VA, const int64_t* a_faces, int64_t FA, const float* b_verts,
@@ -170,17 +164,6 @@ int mesh_args(const char* what, const float* a_verts, int64_t VA, const int64_t*
                 "%s: self_mode needs the same mesh as A and B", what);
   RECMV_REQUIRE(FA == 0 || (a_faces && (VA == 0 || a_verts)), "%s: NULL pointer of mesh A", what);
   RECMV_REQUIRE(FB == 0 || (b_faces && (VB == 0 || b_verts)), "%s: NULL pointer of mesh B", what);
-  return RECMV_OK;
-}
-
-int grid_args(const char* what, const float* origin, float h, int64_t nx, int64_t ny, int64_t nz, Grid& g) {
-  RECMV_REQUIRE(origin, "%s: NULL origin", what);
-  RECMV_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1, "%s: dims=(%lld,%lld,%lld) must be at least 1", what, (long long)nx,
-                (long long)ny, (long long)nz);
-  RECMV_REQUIRE(h > 0.f && h < __builtin_inff(), "%s: cell size %g must be positive and finite", what, (double)h);
-  RECMV_REQUIRE(nx <= kMaxCells && ny <= kMaxCells && nz <= kMaxCells && nx * ny * nz <= kMaxCells,
-                "%s: at most 2^26 cells", what);
-  g = Grid{origin[0], origin[1], origin[2], h, 1.f / h, (int)nx, (int)ny, (int)nz};
   return RECMV_OK;
 }
 
@@ -210,17 +193,15 @@ int prepare(const Sink& s, int64_t FA, int32_t* counts, int64_t* total, hipStrea
 }
 
 int grid_pass(const char* what, const float* a_verts, int64_t VA, const int64_t* a_faces, int64_t FA, const float* b_verts,
-              int64_t VB, const int64_t* b_faces, int64_t FB, const int32_t* cell_offsets, const int32_t* entries,
-              int64_t n_entries, const float* origin, float cell_size, int64_t nx, int64_t ny, int64_t nz, int32_t lanes,
-              int32_t self_mode, int32_t skip_shared, int32_t* counts, int64_t* total, const int32_t* offsets,
-              int32_t* pairs, int64_t capacity, int32_t* cursor, int64_t* dropped, void* stream) {
+              int64_t VB, const int64_t* b_faces, int64_t FB, const recmv_mesh_grid* grid, int32_t lanes, int32_t self_mode,
+              int32_t skip_shared, int32_t* counts, int64_t* total, const int32_t* offsets, int32_t* pairs, int64_t capacity,
+              int32_t* cursor, int64_t* dropped, void* stream) {
   int rc = mesh_args(what, a_verts, VA, a_faces, FA, b_verts, VB, b_faces, FB, self_mode, skip_shared);
   if (rc != RECMV_OK) return rc;
-  RECMV_REQUIRE(n_entries >= 0 && n_entries < (1ll << 31), "%s: entries=%lld must be in [0, 2^31)", what,
-                (long long)n_entries);
-  RECMV_REQUIRE(lanes == 1 || lanes == 8 || lanes == 64, "%s: lanes=%d must be 1, 8 or 64", what, (int)lanes);
-  Grid g;
-  rc = grid_args(what, origin, cell_size, nx, ny, nz, g);
+  rc = lanes_ok(what, lanes);
+  if (rc != RECMV_OK) return rc;
+  GridView view;
+  rc = grid_view_args(what, grid, FA && FB ? kGridTables : kGridGeometry, view);
   if (rc != RECMV_OK) return rc;
   Sink s;
   rc = sink_args(what, offsets, pairs, capacity, cursor, dropped, s);
@@ -228,25 +209,15 @@ int grid_pass(const char* what, const float* a_verts, int64_t VA, const int64_t*
   RECMV_REQUIRE(s.offsets || (total && (counts || FA == 0)), "%s: NULL output pointer", what);
   RECMV_REQUIRE(!s.offsets || (!counts && !total), "%s: the fill pass writes no counts", what);
   RECMV_REQUIRE(!total || ((uintptr_t)total & 7) == 0, "%s: total must be 8-byte aligned", what);
-  RECMV_REQUIRE(FA == 0 || FB == 0 || (cell_offsets && (n_entries == 0 || entries)), "%s: NULL pointer of the grid", what);
   const int64_t nb = ceil_div(FA * lanes, kBlock);
   RECMV_REQUIRE(nb < (1ll << 31), "%s: too many faces", what);
   hipStream_t st = (hipStream_t)stream;
   rc = prepare(s, FA, counts, total, st);
   if (rc != RECMV_OK || FA == 0 || FB == 0) return rc;     // an empty mesh crosses nothing
-  unsigned long long* tot = (unsigned long long*)total;
-  if (lanes == 1)
-    intersect_grid_kernel<1><<<(unsigned)nb, kBlock, 0, st>>>(a_verts, VA, a_faces, FA, b_verts, VB, b_faces, FB,
-                                                              cell_offsets, entries, n_entries, g, self_mode, skip_shared,
-                                                              counts, tot, s);
-  else if (lanes == 8)
-    intersect_grid_kernel<8><<<(unsigned)nb, kBlock, 0, st>>>(a_verts, VA, a_faces, FA, b_verts, VB, b_faces, FB,
-                                                              cell_offsets, entries, n_entries, g, self_mode, skip_shared,
-                                                              counts, tot, s);
-  else
-    intersect_grid_kernel<64><<<(unsigned)nb, kBlock, 0, st>>>(a_verts, VA, a_faces, FA, b_verts, VB, b_faces, FB,
-                                                               cell_offsets, entries, n_entries, g, self_mode, skip_shared,
-                                                               counts, tot, s);
+  with_lanes(lanes, [&](auto G) {
+    intersect_grid_kernel<decltype(G)::value><<<(unsigned)nb, kBlock, 0, st>>>(
+        a_verts, VA, a_faces, FA, b_verts, VB, b_faces, FB, view, self_mode, skip_shared, counts, (unsigned long long*)total, s);
+  });
   return check_launch(what);
 }
 
@@ -277,25 +248,19 @@ extern "C" int recmv_mesh_intersect_brute(const float* a_verts, int64_t VA, cons
 
 extern "C" int recmv_mesh_intersect_grid_count(const float* a_verts, int64_t VA, const int64_t* a_faces, int64_t FA,
                                                const float* b_verts, int64_t VB, const int64_t* b_faces, int64_t FB,
-                                               const int32_t* cell_offsets, const int32_t* entries, int64_t n_entries,
-                                               const float* origin, float cell_size, int64_t nx, int64_t ny, int64_t nz,
-                                               int32_t lanes, int32_t self_mode, int32_t skip_shared, int32_t* counts,
-                                               int64_t* total, void* stream) {
+                                               const recmv_mesh_grid* grid, int32_t lanes, int32_t self_mode,
+                                               int32_t skip_shared, int32_t* counts, int64_t* total, void* stream) {
   RECMV_REQUIRE(total && (counts || FA == 0), "mesh_intersect_grid_count: NULL output pointer");
-  return grid_pass("mesh_intersect_grid_count", a_verts, VA, a_faces, FA, b_verts, VB, b_faces, FB, cell_offsets, entries,
-                   n_entries, origin, cell_size, nx, ny, nz, lanes, self_mode, skip_shared, counts, total, nullptr, nullptr,
-                   0, nullptr, nullptr, stream);
+  return grid_pass("mesh_intersect_grid_count", a_verts, VA, a_faces, FA, b_verts, VB, b_faces, FB, grid, lanes, self_mode,
+                   skip_shared, counts, total, nullptr, nullptr, 0, nullptr, nullptr, stream);
 }
 
 extern "C" int recmv_mesh_intersect_grid_fill(const float* a_verts, int64_t VA, const int64_t* a_faces, int64_t FA,
                                               const float* b_verts, int64_t VB, const int64_t* b_faces, int64_t FB,
-                                              const int32_t* cell_offsets, const int32_t* entries, int64_t n_entries,
-                                              const float* origin, float cell_size, int64_t nx, int64_t ny, int64_t nz,
-                                              int32_t lanes, int32_t self_mode, int32_t skip_shared, const int32_t* offsets,
-                                              int32_t* pairs, int64_t capacity, int32_t* cursor, int64_t* dropped,
-                                              void* stream) {
+                                              const recmv_mesh_grid* grid, int32_t lanes, int32_t self_mode,
+                                              int32_t skip_shared, const int32_t* offsets, int32_t* pairs, int64_t capacity,
+                                              int32_t* cursor, int64_t* dropped, void* stream) {
   RECMV_REQUIRE(offsets, "mesh_intersect_grid_fill: NULL offsets");
-  return grid_pass("mesh_intersect_grid_fill", a_verts, VA, a_faces, FA, b_verts, VB, b_faces, FB, cell_offsets, entries,
-                   n_entries, origin, cell_size, nx, ny, nz, lanes, self_mode, skip_shared, nullptr, nullptr, offsets, pairs,
-                   capacity, cursor, dropped, stream);
+  return grid_pass("mesh_intersect_grid_fill", a_verts, VA, a_faces, FA, b_verts, VB, b_faces, FB, grid, lanes, self_mode,
+                   skip_shared, nullptr, nullptr, offsets, pairs, capacity, cursor, dropped, stream);
 }

@@ -64,7 +64,7 @@ namespace {
 
 #pragma clang fp contract(off)
 
-#include "closest_tri.h"                                   // Grid, Range, cell_coord, cell_index, face_range
+#include "grid_query.h"                                    // Grid, Range, cell_coord, cell_index, face_range; GridView, for_each_entry
 #include "tri_tri.h"                                       // Pts, load_pts, orient3, opposite, edge_inside
 #include "seg_tri.h"                                       // Seg, seg_make, seg_face_hit, seg_take_min
 
@@ -160,9 +160,9 @@ __device__ __forceinline__ bool slab_behind(const Walk& w, int k, float best) {
 template <int G>
 __global__ void __launch_bounds__(kBlock)
 segment_grid_kernel(const float* __restrict__ p, const float* __restrict__ q, int64_t S, const float* __restrict__ verts,
-                    int64_t V, const int64_t* __restrict__ faces, int64_t F, const int32_t* __restrict__ cell_offsets,
-                    const int32_t* __restrict__ entries, int64_t n_entries, Grid g, int want_count,
+                    int64_t V, const int64_t* __restrict__ faces, int64_t F, GridView view, int want_count,
                     int64_t* __restrict__ face_out, float* __restrict__ t_out, int32_t* __restrict__ count_out) {
+  const Grid& g = view.g;
   const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
   const int sub = threadIdx.x % G;
   if (i >= S) return;                                      // (a whole group at once: i is the same in its lanes)
@@ -182,22 +182,16 @@ segment_grid_kernel(const float* __restrict__ p, const float* __restrict__ q, in
       for (int64_t c = sub; c < cells; c += G) {
         const int a = a0 + (int)(c % wa), b = b0 + (int)(c / wa);
         const int x = w.M == 0 ? k : a, z = w.M == 2 ? k : b, y = w.M == 0 ? a : (w.M == 1 ? k : b);
-        const int cell = (z * g.ny + y) * g.nx + x;
-        int e0 = cell_offsets[cell], e1 = cell_offsets[cell + 1];
-        if (e0 < 0) e0 = 0;
-        if ((int64_t)e1 > n_entries) e1 = (int)n_entries;
-        for (int e = e0; e < e1; ++e) {
-          const int64_t j = entries[e];
-          if ((uint64_t)j >= (uint64_t)F) continue;
+        for_each_entry(view, cell_id(g, x, y, z), F, [&](int64_t j) {
           Range r;
-          if (!face_range(verts, faces, V, j, g, r)) continue;
-          if (!first_meeting(w, k, a, b, a0, b0, r)) continue;
+          if (!face_range(verts, faces, V, j, g, r)) return;
+          if (!first_meeting(w, k, a, b, a0, b0, r)) return;
           float tt;
           if (seg_face_hit(s, verts, faces, V, j, tt)) {
             ++mine;
             seg_take_min(tt, (int)j, best, bidx);
           }
-        }
+        });
       }
       if (!want_count) {
 #pragma unroll
@@ -273,9 +267,9 @@ segment_brute_kernel(const float* __restrict__ p, const float* __restrict__ q, i
 
 using namespace recmv;
 
-namespace {
+#include "mesh_grid_host.h"                                // grid_view_args, lanes_ok, with_lanes
 
-constexpr int64_t kMaxCells = 1ll << 26;                   // mesh_grid.hip's limit
+namespace {
 
 // the segments, the mesh and the outputs, checked before any HIP call (0: fine)
 int common_args(const char* what, const float* p, const float* q, int64_t S, const float* verts, int64_t V,
@@ -310,40 +304,26 @@ extern "C" int recmv_segment_mesh_brute(const float* p, const float* q, int64_t 
 }
 
 extern "C" int recmv_segment_mesh_grid(const float* p, const float* q, int64_t S, const float* verts, int64_t V,
-                                       const int64_t* faces, int64_t F, const int32_t* cell_offsets, const int32_t* entries,
-                                       int64_t n_entries, const float* origin, float cell_size, int64_t nx, int64_t ny,
-                                       int64_t nz, int32_t lanes, int32_t want_count, int64_t* face, float* t, int32_t* count,
-                                       void* stream) {
+                                       const int64_t* faces, int64_t F, const recmv_mesh_grid* grid, int32_t lanes,
+                                       int32_t want_count, int64_t* face, float* t, int32_t* count, void* stream) {
   const char* what = "segment_mesh_grid";
   int rc = common_args(what, p, q, S, verts, V, faces, F, face, t);
   if (rc != RECMV_OK) return rc;
   RECMV_REQUIRE(want_count == 0 || want_count == 1, "%s: want_count=%d must be 0 or 1", what, (int)want_count);
   RECMV_REQUIRE(!want_count || S == 0 || count, "%s: want_count=1 needs count (NULL)", what);
-  RECMV_REQUIRE(n_entries >= 0 && n_entries < (1ll << 31), "%s: entries=%lld must be in [0, 2^31)", what,
-                (long long)n_entries);
-  RECMV_REQUIRE(lanes == 1 || lanes == 8 || lanes == 64, "%s: lanes=%d must be 1, 8 or 64", what, (int)lanes);
-  RECMV_REQUIRE(origin, "%s: NULL origin", what);
-  RECMV_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1, "%s: dims=(%lld,%lld,%lld) must be at least 1", what, (long long)nx,
-                (long long)ny, (long long)nz);
-  RECMV_REQUIRE(cell_size > 0.f && cell_size < __builtin_inff(), "%s: cell size %g must be positive and finite", what,
-                (double)cell_size);
-  RECMV_REQUIRE(nx <= kMaxCells && ny <= kMaxCells && nz <= kMaxCells && nx * ny * nz <= kMaxCells, "%s: at most 2^26 cells",
-                what);
-  RECMV_REQUIRE(S == 0 || F == 0 || (cell_offsets && (n_entries == 0 || entries)), "%s: NULL pointer of the grid", what);
+  rc = lanes_ok(what, lanes);
+  if (rc != RECMV_OK) return rc;
+  GridView view;
+  rc = grid_view_args(what, grid, S && F ? kGridTables : kGridGeometry, view);
+  if (rc != RECMV_OK) return rc;
   const int64_t nb = ceil_div(S * lanes, kBlock);
   RECMV_REQUIRE(nb < (1ll << 31), "%s: too many segments", what);
   if (S == 0) return RECMV_OK;
   hipStream_t st = (hipStream_t)stream;
   if (F == 0) return launch_brute(what, p, q, S, verts, V, faces, F, face, t, want_count ? count : nullptr, st);   // hits nothing
-  const Grid g{origin[0], origin[1], origin[2], cell_size, 1.f / cell_size, (int)nx, (int)ny, (int)nz};
-  if (lanes == 1)
-    segment_grid_kernel<1><<<(unsigned)nb, kBlock, 0, st>>>(p, q, S, verts, V, faces, F, cell_offsets, entries, n_entries, g,
-                                                            want_count, face, t, count);
-  else if (lanes == 8)
-    segment_grid_kernel<8><<<(unsigned)nb, kBlock, 0, st>>>(p, q, S, verts, V, faces, F, cell_offsets, entries, n_entries, g,
-                                                            want_count, face, t, count);
-  else
-    segment_grid_kernel<64><<<(unsigned)nb, kBlock, 0, st>>>(p, q, S, verts, V, faces, F, cell_offsets, entries, n_entries,
-                                                             g, want_count, face, t, count);
+  with_lanes(lanes, [&](auto G) {
+    segment_grid_kernel<decltype(G)::value><<<(unsigned)nb, kBlock, 0, st>>>(p, q, S, verts, V, faces, F, view, want_count, face,
+                                                                            t, count);
+  });
   return check_launch(what);
 }

@@ -16,7 +16,7 @@ _PKG = Path(__file__).resolve().parent.parent          # rec-mv_amd/
 LIB_PATH = Path(os.environ["RECMV_LIB_PATH"]) if os.environ.get("RECMV_LIB_PATH") else _PKG / "lib" / "librecmv_hip.so"   # (override: A/B builds of tools/)
 
 RECMV_OK = 0
-ABI_VERSION = 10         # include/recmv_hip.h; bumped when a signature changes (recmv_segment_mesh_brute, recmv_segment_mesh_grid, recmv_mesh_intersect_brute, recmv_mesh_intersect_grid_count, recmv_mesh_intersect_grid_fill, recmv_mesh_grid_count, recmv_mesh_grid_fill, recmv_closest_point_grid, recmv_curve_tubes, recmv_curve_fit_step, recmv_point_mesh_nearest, recmv_collision_push, recmv_closest_point, recmv_iso_relax, recmv_loop_subdivide, recmv_lap_align_solve, recmv_lap_smooth, recmv_knn1, recmv_nricp_energy and their workspace sizes were added at v10 without a bump: no existing signature changed, and _declare rejects a library that lacks them; v10: recmv_verts_normals, recmv_hard_phong_shade, recmv_hard_phong_params_floats added; v9: recmv_lbs_jet_* added; v8: recmv_cam_* added; v7: recmv_get_sampler_mode, recmv_set_jet_fill added; v5: second weight set + split_row in recmv_mlp; v6: recmv_def_regu, recmv_b3_*, recmv_mlp_rows_*, recmv_mc_run_batch added)
+ABI_VERSION = 11         # include/recmv_hip.h has the history
 F32, F64 = 0, 1
 ACT_NONE, ACT_RELU, ACT_SOFTPLUS, ACT_TANH = 0, 1, 2, 3
 
@@ -37,6 +37,12 @@ class Mlp(C.Structure):
                 ("bias", C.c_void_p * MLP_MAX_LAYERS), ("pe_weights", C.c_float * 32),
                 ("W2", C.c_void_p * MLP_MAX_LAYERS), ("Wt2", C.c_void_p * MLP_MAX_LAYERS),
                 ("bias2", C.c_void_p * MLP_MAX_LAYERS), ("split_row", C.c_int64)]
+
+
+class MeshGridDesc(C.Structure):
+    """recmv_mesh_grid of include/recmv_hip.h."""
+    _fields_ = [("origin", C.c_float * 3), ("cell_size", C.c_float), ("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64),
+                ("offsets", C.c_void_p), ("entries", C.c_void_p), ("n_entries", C.c_int64), ("tris", C.c_void_p)]
 
 
 class LbsGrid(C.Structure):
@@ -69,7 +75,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
 
 def _declare(lib):
     vp, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
-    T5 = C.POINTER(Tensor5)
+    T5, MG = C.POINTER(Tensor5), C.POINTER(MeshGridDesc)
     sigs = {
         "recmv_abi_version": (C.c_int, []),
         "recmv_no_packed_f32": (C.c_int, []),
@@ -187,20 +193,16 @@ def _declare(lib):
         "recmv_curve_tubes": (C.c_int, [vp, vp, f32, i64, i64, i64, vp, vp, vp]),
         "recmv_curve_fit_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, f32, f32, vp, vp, vp, vp]),
         "recmv_mesh_grid_workspace_bytes": (i64, [i64]),
-        "recmv_mesh_grid_count": (C.c_int, [vp, i64, vp, i64, C.POINTER(f32), f32, i64, i64, i64, vp, vp, vp]),
-        "recmv_mesh_grid_fill": (C.c_int, [vp, i64, vp, i64, C.POINTER(f32), f32, i64, i64, i64, vp, vp, vp, i64, vp, vp,
-                                           i64, vp]),
-        "recmv_closest_point_grid": (C.c_int, [vp, i64, vp, vp, i64, vp, vp, i64, C.POINTER(f32), f32, i64, i64, i64, i32,
-                                               vp, vp, vp, vp]),
+        "recmv_mesh_grid_count": (C.c_int, [vp, i64, vp, i64, MG, vp, vp, vp]),
+        "recmv_mesh_grid_fill": (C.c_int, [vp, i64, vp, i64, MG, vp, vp, i64, vp]),
+        "recmv_closest_point_grid": (C.c_int, [vp, i64, vp, i64, MG, i32, vp, vp, vp, vp]),
         "recmv_mesh_intersect_brute": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, i64, vp, vp,
                                                  vp]),
-        "recmv_mesh_intersect_grid_count": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, C.POINTER(f32), f32,
-                                                      i64, i64, i64, i32, i32, i32, vp, vp, vp]),
-        "recmv_mesh_intersect_grid_fill": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, C.POINTER(f32), f32,
-                                                     i64, i64, i64, i32, i32, i32, vp, vp, i64, vp, vp, vp]),
+        "recmv_mesh_intersect_grid_count": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, MG, i32, i32, i32, vp, vp, vp]),
+        "recmv_mesh_intersect_grid_fill": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, MG, i32, i32, i32, vp, vp, i64, vp, vp,
+                                                     vp]),
         "recmv_segment_mesh_brute": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
-        "recmv_segment_mesh_grid": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, vp, i64, C.POINTER(f32), f32, i64, i64, i64,
-                                              i32, i32, vp, vp, vp, vp]),
+        "recmv_segment_mesh_grid": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, MG, i32, i32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)       # AttributeError if the symbol is missing: fail loudly

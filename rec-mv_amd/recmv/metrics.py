@@ -131,15 +131,18 @@ class MeshGrid:
         else:
             h, dims = choose_grid(lo, hi, faces.shape[0], faces_per_cell)
         lib = L.lib()
-        V, F = self.verts.shape[0], self.faces.shape[0]
-        self.origin = (C.c_float * 3)(*lo)
+        self._mesh = mesh = (L.ptr(self.verts), self.verts.shape[0], L.ptr(self.faces), self.faces.shape[0])
+        self.desc = desc = L.MeshGridDesc()                 # recmv_mesh_grid: points into offsets, entries and tris below
+        self.origin = desc.origin
+        desc.origin[:] = lo
         while True:
+            desc.cell_size, (desc.nx, desc.ny, desc.nz) = h, dims
             cells = dims[0] * dims[1] * dims[2]
             counts = L.scratch((cells,), torch.int32, dev)
             total = L.scratch((1,), torch.int64, dev)
             with L.device_guard(dev):
-                L.check(lib.recmv_mesh_grid_count(L.ptr(self.verts), V, L.ptr(self.faces), F, self.origin, h, *dims,
-                                                  L.ptr(counts), L.ptr(total), L.stream_ptr(dev)), "mesh_grid_count")
+                L.check(lib.recmv_mesh_grid_count(*mesh, C.byref(desc), L.ptr(counts), L.ptr(total), L.stream_ptr(dev)),
+                        "mesh_grid_count")
             n = int(total.item())
             if n <= MAX_ENTRIES:
                 break
@@ -149,13 +152,14 @@ class MeshGrid:
         self.cell_size, self.dims, self.n_entries = h, dims, n
         self.offsets = L.scratch((cells + 1,), torch.int32, dev)
         self.entries = L.scratch((max(n, 1),), torch.int32, dev)
-        self.tris = L.scratch((F, 12), torch.float32, dev)
+        self.tris = L.scratch((self.faces.shape[0], 12), torch.float32, dev)
+        desc.offsets, desc.entries, desc.tris = self.offsets.data_ptr(), self.entries.data_ptr(), self.tris.data_ptr()
+        desc.n_entries = n
         nbytes = int(lib.recmv_mesh_grid_workspace_bytes(cells))
         ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
         with L.device_guard(dev):
-            L.check(lib.recmv_mesh_grid_fill(L.ptr(self.verts), V, L.ptr(self.faces), F, self.origin, h, *dims,
-                                             L.ptr(counts), L.ptr(self.offsets), L.ptr(self.entries), n, L.ptr(self.tris),
-                                             L.ptr(ws), nbytes, L.stream_ptr(dev)), "mesh_grid_fill")
+            L.check(lib.recmv_mesh_grid_fill(*mesh, C.byref(desc), L.ptr(counts), L.ptr(ws), nbytes, L.stream_ptr(dev)),
+                    "mesh_grid_fill")
         self.counts = counts
 
     def cell_of(self, p):
@@ -184,10 +188,9 @@ class MeshGrid:
         lanes = QUERY_LANES if lanes is None else int(lanes)
         order = torch.sort(self.cell_of(p))[1].contiguous() if (QUERY_SORTED if sort is None else sort) else None
         with L.device_guard(dev):
-            L.check(L.lib().recmv_closest_point_grid(L.ptr(p), P, L.ptr(order), L.ptr(self.tris), self.faces.shape[0],
-                                                     L.ptr(self.offsets), L.ptr(self.entries), self.n_entries, self.origin,
-                                                     self.cell_size, *self.dims, lanes, L.ptr(face), L.ptr(point),
-                                                     L.ptr(dist2), L.stream_ptr(dev)), "closest_point_grid")
+            L.check(L.lib().recmv_closest_point_grid(L.ptr(p), P, L.ptr(order), self.faces.shape[0], C.byref(self.desc),
+                                                     lanes, L.ptr(face), L.ptr(point), L.ptr(dist2), L.stream_ptr(dev)),
+                    "closest_point_grid")
         return face, point, dist2
 
     def segment_hits(self, p, q, count=False, lanes=None):
@@ -205,10 +208,8 @@ class MeshGrid:
             raise ValueError("lanes must be 1, 8 or 64 (got %r)" % (lanes,))
         if S:
             with L.device_guard(dev):
-                L.check(L.lib().recmv_segment_mesh_grid(L.ptr(p), L.ptr(q), S, L.ptr(self.verts), self.verts.shape[0],
-                                                        L.ptr(self.faces), self.faces.shape[0], L.ptr(self.offsets),
-                                                        L.ptr(self.entries), self.n_entries, self.origin, self.cell_size,
-                                                        *self.dims, lanes, int(bool(count)), L.ptr(face), L.ptr(t), L.ptr(cnt),
+                L.check(L.lib().recmv_segment_mesh_grid(L.ptr(p), L.ptr(q), S, *self._mesh, C.byref(self.desc), lanes,
+                                                        int(bool(count)), L.ptr(face), L.ptr(t), L.ptr(cnt),
                                                         L.stream_ptr(dev)), "segment_mesh_grid")
         return _segment_result(p, q, face, t, cnt)
 
@@ -216,10 +217,8 @@ class MeshGrid:
         lanes = INTERSECT_LANES if lanes is None else int(lanes)
         dev = self.verts.device
         FA = faces.shape[0]
-        grid = (L.ptr(self.offsets), L.ptr(self.entries), self.n_entries, self.origin, self.cell_size, *self.dims, lanes,
-                int(self_mode), int(self_mode))
-        mesh = (L.ptr(verts), verts.shape[0], L.ptr(faces), FA, L.ptr(self.verts), self.verts.shape[0], L.ptr(self.faces),
-                self.faces.shape[0])
+        grid = (C.byref(self.desc), lanes, int(self_mode), int(self_mode))
+        mesh = (L.ptr(verts), verts.shape[0], L.ptr(faces), FA, *self._mesh)
         lib = L.lib()
 
         def count(counts, total):

@@ -247,7 +247,7 @@ def test_temporal_smoothness_is_the_mean_second_difference():
 def test_collision_entry_points_check_their_arguments_without_a_gpu():
     from recmv import _lib, collide
     lib = _lib.lib()
-    assert lib.recmv_abi_version() == 10 and _lib.ABI_VERSION == 10
+    assert lib.recmv_abi_version() == 11 and _lib.ABI_VERSION == 11
     assert {"recmv_point_mesh_nearest", "recmv_point_mesh_nearest_workspace_bytes",
             "recmv_collision_push"} <= set(_lib.exported_symbols())
     n, p = None, C.c_void_p(16)

@@ -189,7 +189,7 @@ def test_fill_with_too_small_a_capacity_stays_inside_its_buffer(bodies):
     cursor = torch.empty(FA, dtype=torch.int32, device=DEV)
     dropped = torch.full((1,), -1, dtype=torch.int64, device=DEV)
     mesh = (L.ptr(av), av.shape[0], L.ptr(af), FA, L.ptr(bv), bv.shape[0], L.ptr(bf), bf.shape[0])
-    grid = (L.ptr(g.offsets), L.ptr(g.entries), g.n_entries, g.origin, g.cell_size, *g.dims)
+    grid = (C.byref(g.desc),)
     out = (L.ptr(offsets), C.c_void_p(buf.data_ptr() + 4 * guard), cap, L.ptr(cursor), L.ptr(dropped))
     for lanes in LANES:
         buf.fill_(-7)

@@ -146,7 +146,7 @@ def test_vertex_normal_restatement_sums_in_corner_order():
 def test_new_abi_functions_check_arguments_without_a_gpu():
     from recmv import _lib
     lib = _lib.lib()
-    assert lib.recmv_abi_version() == 10 == _lib.ABI_VERSION
+    assert lib.recmv_abi_version() == 11 == _lib.ABI_VERSION
     assert lib.recmv_verts_normals(None, None, None, None, 1, -1, 4, None, None) == _lib.C.c_int(-1).value
     assert b"verts_normals: bad sizes" in lib.recmv_last_error()
     assert lib.recmv_verts_normals(None, None, None, None, 0, 10, 4, None, None) == 0          # empty batch: no-op

@@ -217,7 +217,7 @@ def test_isotropic_remesh_keeps_the_creases_of_a_cube():
 def test_new_abi_entry_points_reject_bad_arguments():
     from recmv import _lib as L
     lib = L.lib()
-    assert lib.recmv_abi_version() == L.ABI_VERSION == 10
+    assert lib.recmv_abi_version() == L.ABI_VERSION == 11
     assert {"recmv_closest_point", "recmv_closest_point_workspace_bytes", "recmv_iso_relax",
             "recmv_loop_subdivide"} <= set(L.exported_symbols())
     n = C.c_void_p(0)

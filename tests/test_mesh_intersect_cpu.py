@@ -116,8 +116,8 @@ def test_symbols_are_declared_and_exported():
 
 def test_argument_errors_do_not_need_a_gpu():
     from recmv import _lib
+    from test_mesh_metrics_cpu import grid_desc
     lib = _lib.lib()
-    o = (C.c_float * 3)(0., 0., 0.)
     one = C.c_void_p(16)                                   # a non-NULL pointer that is never followed
     two = C.c_void_p(32)
     err = lib.recmv_last_error
@@ -134,23 +134,23 @@ def test_argument_errors_do_not_need_a_gpu():
     assert brute(out=(None, None), fill=(one, None, 4, one, one)) == -1 and b"NULL" in err()
     assert brute(fill=(one, one, 4, one, one)) == -1 and b"no counts" in err()
 
-    def count(*, a=(one, 3, one, 1), b=(two, 3, two, 1), grid=(one, one, 7), dims=(2, 2, 2), h=1., origin=o, lanes=1,
-              flags=(0, 0), out=(one, one)):
-        return lib.recmv_mesh_intersect_grid_count(*a, *b, *grid, origin, h, *dims, lanes, *flags, *out, None)
+    def count(*, a=(one, 3, one, 1), b=(two, 3, two, 1), null=False, lanes=1, flags=(0, 0), out=(one, one), **grid):
+        g = None if null else C.byref(grid_desc(**grid))
+        return lib.recmv_mesh_intersect_grid_count(*a, *b, g, lanes, *flags, *out, None)
     assert count(b=(two, 3, two, -2)) == -1 and b"FB=-2" in err()
     assert count(dims=(2, 0, 2)) == -1 and b"dims=(2,0,2)" in err()
     assert count(h=0.) == -1 and b"cell size" in err()
     assert count(h=float("nan")) == -1
-    assert count(origin=None) == -1 and b"origin" in err()
+    assert count(null=True) == -1 and b"grid" in err()
     assert count(lanes=3) == -1 and b"lanes" in err()
-    assert count(grid=(one, one, -1)) == -1 and b"entries=-1" in err()
-    assert count(grid=(None, one, 7)) == -1 and b"NULL" in err()
+    assert count(n_entries=-1) == -1 and b"entries=-1" in err()
+    assert count(offsets=None) == -1 and b"NULL" in err()
     assert count(out=(one, None)) == -1 and b"NULL" in err()
     assert count(flags=(0, 1)) == -1 and b"skip_shared" in err()
     assert count(dims=(1 << 20, 1 << 20, 1)) == -1 and b"cells" in err()
 
     def fill(*, a=(one, 3, one, 1), lanes=8, flags=(0, 0), tail=(one, one, 4, one, one)):
-        return lib.recmv_mesh_intersect_grid_fill(*a, two, 3, two, 1, one, one, 7, o, 1., 2, 2, 2, lanes, *flags, *tail, None)
+        return lib.recmv_mesh_intersect_grid_fill(*a, two, 3, two, 1, C.byref(grid_desc()), lanes, *flags, *tail, None)
     assert fill(tail=(None, one, 4, one, one)) == -1 and b"offsets" in err()
     assert fill(tail=(one, one, 1 << 31, one, one)) == -1 and b"capacity" in err()
     assert fill(tail=(one, one, 4, None, one)) == -1 and b"NULL" in err()
@@ -205,7 +205,7 @@ def test_host_build_of_the_grid_kernel_equals_the_pair_loop(tmp_path):
         pytest.skip("ROCm's clang++ not present")
     csrc = REPO / "rec-mv_amd" / "csrc"
     for f in (REPO / "tools" / "mesh_grid_host_check" / "common.h", REPO / "tools" / "mesh_intersect_host_check" / "main.cpp",
-              csrc / "closest_tri.h", csrc / "tri_tri.h"):
+              csrc / "closest_tri.h", csrc / "grid_query.h", csrc / "tri_tri.h"):
         shutil.copy(f, tmp_path)
     for src, dst in (("mesh_grid.hip", "grid.inc"), ("mesh_intersect.hip", "intersect.inc")):
         hip = (csrc / src).read_text()

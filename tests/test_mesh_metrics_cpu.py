@@ -65,72 +65,136 @@ def test_reference_search_equals_the_brute_force():
     assert np.array_equal(face, face0) and np.array_equal(d2, d20)
 
 
+ONE = C.c_void_p(16)                                       # a non-NULL pointer that is never followed
+
+
+def grid_desc(origin=(0., 0., 0.), h=1., dims=(2, 2, 2), offsets=16, entries=16, n_entries=7, tris=16):
+    """A recmv_mesh_grid whose pointers are never followed (the argument checks come before any HIP call)."""
+    from recmv import _lib
+    d = _lib.MeshGridDesc()
+    d.origin[:] = origin
+    d.cell_size, (d.nx, d.ny, d.nz) = h, dims
+    d.offsets, d.entries, d.n_entries, d.tris = offsets, entries, n_entries, tris
+    return d
+
+
 def test_argument_errors_of_the_grid_entry_points_do_not_need_a_gpu():
     """Negative sizes, NULL pointers with non-zero sizes, dims below 1 and a non-positive cell size are found before any HIP
     call and reported through recmv_last_error."""
     from recmv import _lib
     lib = _lib.lib()
-    o = (C.c_float * 3)(0., 0., 0.)
-    one = C.c_void_p(16)                                   # a non-NULL pointer that is never followed
+    one = ONE
     assert lib.recmv_mesh_grid_workspace_bytes(0) == 0 and lib.recmv_mesh_grid_workspace_bytes(1025) == (1025 + 2) * 4
-    # count
-    assert lib.recmv_mesh_grid_count(None, -1, None, 0, o, 1., 1, 1, 1, one, one, None) == -1
+
+    def count(*, mesh=(one, 3, one, 1), out=(one, one), null=False, **grid):
+        return lib.recmv_mesh_grid_count(*mesh, None if null else C.byref(grid_desc(**{'dims': (1, 1, 1), **grid})), *out, None)
+    assert count(mesh=(None, -1, None, 0)) == -1
     assert b"V=-1" in lib.recmv_last_error()
-    assert lib.recmv_mesh_grid_count(one, 3, one, 1, o, 1., 0, 1, 1, one, one, None) == -1
+    assert count(dims=(0, 1, 1)) == -1
     assert b"dims=(0,1,1)" in lib.recmv_last_error()
-    assert lib.recmv_mesh_grid_count(one, 3, one, 1, o, 0., 1, 1, 1, one, one, None) == -1
+    assert count(h=0.) == -1
     assert b"cell size" in lib.recmv_last_error()
-    assert lib.recmv_mesh_grid_count(one, 3, one, 1, o, float("nan"), 1, 1, 1, one, one, None) == -1
-    assert lib.recmv_mesh_grid_count(one, 3, one, 1, None, 1., 1, 1, 1, one, one, None) == -1
-    assert b"origin" in lib.recmv_last_error()
-    assert lib.recmv_mesh_grid_count(one, 3, one, 1, o, 1., 1, 1, 1, None, one, None) == -1
+    assert count(h=float("nan")) == -1
+    assert count(null=True) == -1
+    assert b"grid" in lib.recmv_last_error()
+    assert count(out=(None, one)) == -1
     assert b"NULL" in lib.recmv_last_error()
-    assert lib.recmv_mesh_grid_count(one, 3, None, 1, o, 1., 1, 1, 1, one, one, None) == -1
+    assert count(mesh=(one, 3, None, 1)) == -1
     assert b"NULL" in lib.recmv_last_error()
-    assert lib.recmv_mesh_grid_count(one, 3, one, 1, o, 1., 1 << 20, 1 << 20, 1, one, one, None) == -1
+    assert count(dims=(1 << 20, 1 << 20, 1)) == -1
     assert b"cells" in lib.recmv_last_error()
-    # fill
-    assert lib.recmv_mesh_grid_fill(one, 3, one, 1, o, 1., 1, 1, 1, one, one, one, -1, one, one, 64, None) == -1
-    assert b"capacity=-1" in lib.recmv_last_error()
-    assert lib.recmv_mesh_grid_fill(one, 3, one, 1, o, 1., 1, 1, -2, one, one, one, 1, one, one, 64, None) == -1
+
+    def fill(*, ws=64, **grid):
+        d = grid_desc(**{'dims': (1, 1, 1), 'n_entries': 1, **grid})
+        return lib.recmv_mesh_grid_fill(one, 3, one, 1, C.byref(d), one, one, ws, None)
+    assert fill(n_entries=-1) == -1                        # the capacity of entries
+    assert b"entries=-1" in lib.recmv_last_error()
+    assert fill(dims=(1, 1, -2)) == -1
     assert b"dims" in lib.recmv_last_error()
-    assert lib.recmv_mesh_grid_fill(one, 3, one, 1, o, -1., 1, 1, 1, one, one, one, 1, one, one, 64, None) == -1
+    assert fill(h=-1.) == -1
     assert b"cell size" in lib.recmv_last_error()
-    assert lib.recmv_mesh_grid_fill(one, 3, one, 1, o, 1., 1, 1, 1, one, one, None, 1, one, one, 64, None) == -1
+    assert fill(entries=None) == -1
     assert b"NULL" in lib.recmv_last_error()
-    assert lib.recmv_mesh_grid_fill(one, 3, one, 1, o, 1., 1, 1, 1, one, one, one, 1, one, one, 4, None) == -1
+    assert fill(ws=4) == -1
     assert b"workspace" in lib.recmv_last_error()
-    # query
-    args = (one, one, 5, one, one, 7, o, 1., 2, 2, 2, 1, one, one, one, None)
-    assert lib.recmv_closest_point_grid(one, 0, *args) == 0                      # P = 0 is a no-op
-    assert lib.recmv_closest_point_grid(one, -1, *args) == -1
+
+    def query(*, p=one, P=4, F=5, lanes=1, **grid):
+        return lib.recmv_closest_point_grid(p, P, one, F, C.byref(grid_desc(**grid)), lanes, one, one, one, None)
+    assert query(P=0) == 0                                 # P = 0 is a no-op
+    assert query(P=-1) == -1
     assert b"P=-1" in lib.recmv_last_error()
-    assert lib.recmv_closest_point_grid(one, 4, one, one, 0, one, one, 7, o, 1., 2, 2, 2, 1, one, one, one, None) == -1
+    assert query(F=0) == -1
     assert b"must not be empty" in lib.recmv_last_error()
-    assert lib.recmv_closest_point_grid(one, 4, one, one, 5, one, one, 7, o, 1., 2, 0, 2, 1, one, one, one, None) == -1
+    assert query(dims=(2, 0, 2)) == -1
     assert b"dims" in lib.recmv_last_error()
-    assert lib.recmv_closest_point_grid(one, 4, one, one, 5, one, one, 7, o, 0., 2, 2, 2, 1, one, one, one, None) == -1
+    assert query(h=0.) == -1
     assert b"cell size" in lib.recmv_last_error()
-    assert lib.recmv_closest_point_grid(one, 4, one, one, 5, one, one, 7, o, 1., 2, 2, 2, 3, one, one, one, None) == -1
+    assert query(lanes=3) == -1
     assert b"lanes" in lib.recmv_last_error()
-    assert lib.recmv_closest_point_grid(None, 4, one, one, 5, one, one, 7, o, 1., 2, 2, 2, 1, one, one, one, None) == -1
+    assert query(p=None) == -1
     assert b"NULL" in lib.recmv_last_error()
-    assert lib.recmv_closest_point_grid(one, 4, one, one, 5, one, None, 7, o, 1., 2, 2, 2, 1, one, one, one, None) == -1
+    assert query(entries=None) == -1
     assert b"NULL" in lib.recmv_last_error()
+
+
+# every entry point that takes a recmv_mesh_grid: (call(lib, descriptor or None), whether it reads or writes the tables)
+_MESH = (ONE, 3, ONE, 1)
+_MESH_B = (C.c_void_p(32), 3, C.c_void_p(32), 1)
+GRID_ENTRY_POINTS = {
+    "mesh_grid_count": (lambda lib, g: lib.recmv_mesh_grid_count(*_MESH, g, ONE, ONE, None), False),
+    "mesh_grid_fill": (lambda lib, g: lib.recmv_mesh_grid_fill(*_MESH, g, ONE, ONE, 1 << 20, None), True),
+    "closest_point_grid": (lambda lib, g: lib.recmv_closest_point_grid(ONE, 4, ONE, 5, g, 1, ONE, ONE, ONE, None), True),
+    "mesh_intersect_grid_count": (
+        lambda lib, g: lib.recmv_mesh_intersect_grid_count(*_MESH, *_MESH_B, g, 1, 0, 0, ONE, ONE, None), True),
+    "mesh_intersect_grid_fill": (
+        lambda lib, g: lib.recmv_mesh_intersect_grid_fill(*_MESH, *_MESH_B, g, 8, 0, 0, ONE, ONE, 4, ONE, ONE, None), True),
+    "segment_mesh_grid": (lambda lib, g: lib.recmv_segment_mesh_grid(ONE, ONE, 4, *_MESH, g, 1, 0, ONE, ONE, None, None), True),
+}
+MALFORMED_GRIDS = {
+    "NULL descriptor": None,
+    "ny = 0": dict(dims=(2, 0, 2)),
+    "cell size 0": dict(h=0.),
+    "cell size NaN": dict(h=float("nan")),
+    "cell size inf": dict(h=float("inf")),
+    "2^20 x 2^20 x 1 cells": dict(dims=(1 << 20, 1 << 20, 1)),
+    "n_entries = -1": dict(n_entries=-1),
+    "NULL offsets": dict(offsets=None),
+}
+
+
+@pytest.mark.parametrize("name", sorted(GRID_ENTRY_POINTS))
+def test_one_validator_rejects_a_malformed_descriptor_alike_in_every_entry_point(name):
+    """Every malformed descriptor is an argument error in every entry point that takes one, found before any HIP call, and the
+    message is the same text apart from the entry point's name (compared with recmv_closest_point_grid's, which reads every
+    field): the descriptor is checked in one place.  NULL offsets only where the tables are read or written."""
+    from recmv import _lib
+    lib = _lib.lib()
+
+    def text(entry, grid):
+        call, _ = GRID_ENTRY_POINTS[entry]
+        rc = call(lib, None if grid is None else C.byref(grid_desc(**grid)))
+        msg = lib.recmv_last_error().decode()
+        assert rc == -1 and msg.startswith(entry + ": "), (entry, rc, msg)          # RECMV_ERR_ARG
+        return msg[len(entry) + 2:]
+    for case, grid in MALFORMED_GRIDS.items():
+        if case == "NULL offsets" and not GRID_ENTRY_POINTS[name][1]:
+            continue
+        assert text(name, grid) == text("closest_point_grid", grid), case
 
 
 def test_host_build_of_the_grid_kernels_returns_the_brute_force_bits(tmp_path):
     """tools/mesh_grid_host_check: csrc/mesh_grid.hip's count, fill and one-lane query kernels compiled for the CPU against a
-    brute force with the same closest_tri.h, bit for bit, on seven meshes and grids."""
+    brute force with the same closest_tri.h and grid_query.h, bit for bit, on seven meshes and grids."""
     import shutil
     import subprocess
     clang = "/opt/rocm/lib/llvm/bin/clang++"
     if not Path(clang).exists():
         pytest.skip("ROCm's clang++ not present")
     src = REPO / "tools" / "mesh_grid_host_check"
-    for f in (src / "common.h", src / "main.cpp", REPO / "rec-mv_amd" / "csrc" / "closest_tri.h"):
+    csrc = REPO / "rec-mv_amd" / "csrc"
+    for f in (src / "common.h", src / "main.cpp", csrc / "closest_tri.h", csrc / "grid_query.h"):
         shutil.copy(f, tmp_path)
-    hip = (REPO / "rec-mv_amd" / "csrc" / "mesh_grid.hip").read_text()
+    hip = (csrc / "mesh_grid.hip").read_text()
     cut = hip.index("\nusing namespace recmv;")
     (tmp_path / "kernels.inc").write_text(hip[:cut + 1])
     subprocess.run([clang, "-std=c++17", "-O2", "-ffp-contract=off", "-I.", "main.cpp", "-o", "check"], cwd=tmp_path, check=True)

@@ -152,13 +152,13 @@ def test_symbols_are_declared_and_exported():
     lib = _lib.lib()
     for n in ("recmv_segment_mesh_brute", "recmv_segment_mesh_grid"):
         assert n in declared and hasattr(lib, n)
-    assert lib.recmv_abi_version() == _lib.ABI_VERSION == 10
+    assert lib.recmv_abi_version() == _lib.ABI_VERSION == 11
 
 
 def test_argument_errors_do_not_need_a_gpu():
     from recmv import _lib
+    from test_mesh_metrics_cpu import grid_desc
     lib = _lib.lib()
-    o = (C.c_float * 3)(0., 0., 0.)
     one = C.c_void_p(16)                                   # a non-NULL pointer that is never followed
     err = lib.recmv_last_error
 
@@ -177,9 +177,9 @@ def test_argument_errors_do_not_need_a_gpu():
     assert brute(mesh=(one, 3, one, 1 << 31)) == -1 and b"faces" in err()
     assert brute(seg=(None, None, 0), out=(None, None, None)) == 0                 # S = 0: a no-op
 
-    def grid(*, seg=(one, one, 4), mesh=(one, 3, one, 1), cells=(one, one, 7), dims=(2, 2, 2), h=1., origin=o, lanes=1,
-             want=0, out=(one, one, None)):
-        return lib.recmv_segment_mesh_grid(*seg, *mesh, *cells, origin, h, *dims, lanes, want, *out, None)
+    def grid(*, seg=(one, one, 4), mesh=(one, 3, one, 1), null=False, lanes=1, want=0, out=(one, one, None), **desc):
+        g = None if null else C.byref(grid_desc(**desc))
+        return lib.recmv_segment_mesh_grid(*seg, *mesh, g, lanes, want, *out, None)
     assert grid(seg=(one, one, -5)) == -1 and b"S=-5" in err()
     assert grid(mesh=(one, 3, one, -2)) == -1 and b"F=-2" in err()
     assert grid(seg=(None, one, 4)) == -1 and b"NULL segment" in err()
@@ -191,12 +191,12 @@ def test_argument_errors_do_not_need_a_gpu():
     assert grid(h=0.) == -1 and b"cell size" in err()
     assert grid(h=float("nan")) == -1 and b"cell size" in err()
     assert grid(h=float("inf")) == -1 and b"cell size" in err()
-    assert grid(origin=None) == -1 and b"origin" in err()
+    assert grid(null=True) == -1 and b"grid" in err()
     assert grid(dims=(2, 0, 2)) == -1 and b"dims=(2,0,2)" in err()
     assert grid(dims=(1 << 20, 1 << 20, 1)) == -1 and b"cells" in err()
-    assert grid(cells=(one, one, -1)) == -1 and b"entries=-1" in err()
-    assert grid(cells=(None, one, 7)) == -1 and b"NULL pointer of the grid" in err()
-    assert grid(cells=(one, None, 7)) == -1 and b"NULL pointer of the grid" in err()
+    assert grid(n_entries=-1) == -1 and b"entries=-1" in err()
+    assert grid(offsets=None) == -1 and b"NULL pointer of the grid" in err()
+    assert grid(entries=None) == -1 and b"NULL pointer of the grid" in err()
     assert grid(seg=(None, None, 0), out=(None, None, None)) == 0
 
 
@@ -271,7 +271,7 @@ def test_host_build_of_the_grid_kernel_equals_the_brute_loop(tmp_path):
         pytest.skip("ROCm's clang++ not present")
     csrc = REPO / "rec-mv_amd" / "csrc"
     for f in (REPO / "tools" / "mesh_grid_host_check" / "common.h", REPO / "tools" / "segment_mesh_host_check" / "main.cpp",
-              csrc / "closest_tri.h", csrc / "tri_tri.h", csrc / "seg_tri.h"):
+              csrc / "closest_tri.h", csrc / "grid_query.h", csrc / "tri_tri.h", csrc / "seg_tri.h"):
         shutil.copy(f, tmp_path)
     for src, dst in (("mesh_grid.hip", "grid.inc"), ("segment_mesh.hip", "segment.inc")):
         hip = (csrc / src).read_text()

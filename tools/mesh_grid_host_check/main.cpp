@@ -45,7 +45,7 @@ static int run(const char* name, const Mesh& m, std::vector<float> p, int nx, in
   int bad = 0;
   for (int64_t s = 0; s < P; ++s) {
     blockIdx.x = (unsigned)(s / 256); threadIdx.x = (unsigned)(s % 256);
-    closest_point_grid_kernel<1>(p.data(), P, nullptr, tris.data(), F, offsets.data(), entries.data(), sum, g, face.data(), point.data(), dist2.data());
+    closest_point_grid_kernel<1>(p.data(), P, nullptr, tris.data(), F, GridView{g, offsets.data(), entries.data(), sum}, face.data(), point.data(), dist2.data());
     int64_t bf; float bd; float bp[3] = {0, 0, 0};
     brute(m, &p[3 * s], bf, bd, bp);
     bool ok = bf == face[s] && memcmp(&bd, &dist2[s], 4) == 0 && (bf < 0 || memcmp(bp, &point[3 * s], 12) == 0);

@@ -89,8 +89,8 @@ static int run(const char* name, const Mesh& a, const Mesh& b, bool self, int nx
   rc |= two_passes(name, FA, [&](int32_t* cnt, unsigned long long* tot, Sink s) {
     for (int64_t i = 0; i < FA; ++i) {
       blockIdx.x = (unsigned)(i / 256); threadIdx.x = (unsigned)(i % 256);
-      intersect_grid_kernel<1>(a.v.data(), VA, a.f.data(), FA, b.v.data(), VB, b.f.data(), FB, offsets.data(), entries.data(),
-                               sum, g, self, self, cnt, tot, s);
+      intersect_grid_kernel<1>(a.v.data(), VA, a.f.data(), FA, b.v.data(), VB, b.f.data(), FB,
+                               GridView{g, offsets.data(), entries.data(), sum}, self, self, cnt, tot, s);
     }
   }, pg);
   bool same = pb == pg;

@@ -152,8 +152,8 @@ static int compare(const char* name, const Mesh& m, int nx, int ny, int nz, floa
     std::vector<int32_t> count(S, -9);
     for (int64_t i = 0; i < S; ++i) {
       blockIdx.x = (unsigned)(i / 256); threadIdx.x = (unsigned)(i % 256);
-      segment_grid_kernel<1>(p.data(), q.data(), S, m.v.data(), V, m.f.data(), F, offsets.data(), entries.data(), sum, g, mode,
-                             face.data(), t.data(), mode ? count.data() : nullptr);
+      segment_grid_kernel<1>(p.data(), q.data(), S, m.v.data(), V, m.f.data(), F, GridView{g, offsets.data(), entries.data(), sum},
+                             mode, face.data(), t.data(), mode ? count.data() : nullptr);
       const Seg s = seg_make(p[3 * i], p[3 * i + 1], p[3 * i + 2], q[3 * i], q[3 * i + 1], q[3 * i + 2]);
       float best = __builtin_inff(); int bidx = -1; int32_t n = 0;
       if (s.ok) for (int64_t j = 0; j < F; ++j) {
