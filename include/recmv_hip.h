@@ -34,7 +34,7 @@ extern "C" {
 /* ABI version, bumped when an existing signature changes (recmv/_lib.py checks the number at load).
  *   v11: the mesh-grid entry points take a recmv_mesh_grid descriptor in place of the grid's loose arguments
  *        (recmv_mesh_grid_count / _fill, recmv_closest_point_grid, recmv_mesh_intersect_grid_count / _fill,
- *        recmv_segment_mesh_grid).
+ *        recmv_segment_mesh_grid).  Added since without a bump: recmv_icp_accumulate and its workspace size.
  *   v10: recmv_verts_normals, recmv_hard_phong_shade, recmv_hard_phong_params_floats added.  Added since without a bump (no
  *        existing signature changed, and _lib.py rejects a library that lacks them): recmv_knn1, recmv_nricp_energy,
  *        recmv_lap_align_solve, recmv_lap_smooth, recmv_closest_point, recmv_iso_relax, recmv_loop_subdivide,
@@ -845,6 +845,40 @@ int recmv_segment_mesh_brute(const float* p, const float* q, int64_t S, const fl
 int recmv_segment_mesh_grid(const float* p, const float* q, int64_t S, const float* verts, int64_t V, const int64_t* faces,
                             int64_t F, const recmv_mesh_grid* grid, int32_t lanes, int32_t want_count, int64_t* face, float* t,
                             int32_t* count, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The sums of one ICP iteration (csrc/icp.hip; added to ABI v11, no existing signature changed).  The reference's
+ * engineer/optimizer/icp_optimzier.py fits a rotation and a translation to nearest neighbours in torch; recmv/align.py
+ * iterates a rigid or similarity fit of a mesh to a mesh and takes its normal equations from here.  No float atomics.
+ * Inputs: x [P,3] f32, the source points under the current transform; q [P,3] f32, face [P] int64 and dist2 [P] f32 exactly
+ *   as recmv_closest_point or recmv_closest_point_grid returned them for x on the mesh verts [V,3] f32 / faces [F,3] int64
+ *   (q is taken as given, not recomputed); border [F] uint8 on the device or NULL; max_dist2 [1] f32 on the device or NULL;
+ *   centre [3] float64 in HOST memory; with_plane 0 or 1.
+ * Pair i is ACCEPTED iff all of: 0 <= face[i] < F and the face's three indices lie in [0, V); x_i, q_i and dist2[i] are
+ *   finite; max_dist2 is NULL or dist2[i] <= *max_dist2 (equality accepted, a NaN threshold accepts nothing); border is NULL or
+ *   the closest point does not lie on the border: csrc/closest_tri.h's point-triangle test of x_i against the face, as the
+ *   search ran it, ends in an edge or vertex region, and the pair is rejected when that region's bit of border[face] is set —
+ *   bit 0 / 1 / 2: edge ab / ac / bc is a border edge, bit 3 / 4 / 5: vertex a / b / c is a border vertex; and with
+ *   with_plane = 1 the face normal (b - a) x (c - a) has a finite length that is not zero.
+ * Output: sums [RECMV_ICP_SUMS] float64 on the device, over the accepted pairs, with c = centre, u = (double)x - c,
+ *   w = (double)q - c, m the unit face normal formed in double from the f32 vertex coordinates, g = u x m,
+ *   J = (g0, g1, g2, m0, m1, m2, u.m) and r = (u - w).m:
+ *     [0] the count; [1..3] sum u; [4..6] sum w; [7 + 3a + b] sum u_a w_b; [16] sum |u|^2; [17] sum |w|^2; [18] sum |u - w|^2;
+ *     [19..46] the upper triangle (row-major, j <= k) of sum J J^T; [47..53] sum J r; [54] sum r^2; [55] 0 (reserved).
+ *   Entries 19 .. 55 are exact zeros with with_plane = 0.  Every successful call writes all of sums; P = 0 writes zeros.
+ * Reproducible: threads take the pairs in a fixed pattern, waves meet in a fixed shuffle tree, a block's waves in wave order,
+ *   and a second one-block launch adds the blocks' slabs in block order; the number of blocks depends on P alone, so the same
+ *   input gives the same bits on every run and every card.
+ * Workspace: recmv_icp_accumulate_workspace_bytes(P) (0 for P = 0), 8-byte aligned; too small or misaligned is
+ *   RECMV_ERR_WORKSPACE.  Argument errors (negative sizes, NULL pointers with P > 0, V = 0 or F = 0 with P > 0, NULL centre or
+ *   sums, with_plane outside {0, 1}) are found before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+#define RECMV_ICP_SUMS 56
+int64_t recmv_icp_accumulate_workspace_bytes(int64_t P);
+int recmv_icp_accumulate(const float* x, const float* q, const int64_t* face, const float* dist2, int64_t P,
+                         const float* verts, int64_t V, const int64_t* faces, int64_t F, const uint8_t* border,
+                         const float* max_dist2, const double* centre, int32_t with_plane, double* sums, void* workspace,
+                         int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

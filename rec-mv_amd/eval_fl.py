@@ -3,7 +3,15 @@ reference has no evaluation command (its tools/comparison_results.py stops after
 
 `--pred` and `--gt` are two `.obj` files or two directories of them; directories are paired by file stem, files without a
 partner are listed in the output and skipped, and no pair at all is an error.  The two meshes of a pair are taken to be in one
-frame: no alignment is attempted (`--scale` multiplies the prediction, for captures in another unit).  Per pair
+frame unless `--align` is given (`--scale` multiplies the prediction, for captures in another unit).  `--align rigid` or
+`--align similarity` first fits the prediction to the ground truth by ICP (recmv.align.icp, after `--scale` and before
+everything else): a reconstruction from one monocular video is known only up to a similarity, so without it the distances
+measure the frame offset, not the shape.  `--align-metric plane|point` chooses the residual, `--align-trim f` keeps the
+share f of the pairs with the smallest distances, `--align-iters n` caps the steps, `--align-from first` estimates the
+transform on the first pair by stem and applies it to every pair (the honest setting for a sequence with one global scale;
+`each`, the default, fits every pair on its own), and `--align-out DIR` writes the aligned predictions as `.obj`.  The
+output then holds `align` (the settings) and `alignment` (per stem: scale, R, t, iterations, converged, rms_before, rms_after,
+pairs); with `--align none` it is what it was without these flags.  Per pair
 recmv.metrics.surface_distance (accuracy, completeness, Chamfer, normal consistency, precision / recall / F-score at
 `--thresholds`, definitions in INTEGRATION.md §5), then the means over the pairs.  When the prediction directory is a sequence
 of one topology the output also holds infer_fl_animation.py's temporal smoothness figure of it.  `--intersections` adds per
@@ -15,6 +23,8 @@ distance of one of them to its surface (`body_inside_vertices`, `body_max_depth`
 
     python rec-mv_amd/eval_fl.py --gpu-ids 0 --pred <obj|dir> --gt <obj|dir> [--samples N] [--seed S] [--thresholds t ...]
         [--scale s] [--method auto|grid|brute] [--intersections [--body <obj|dir> [--penetration]]] [--out metrics.json]
+        [--align none|rigid|similarity [--align-metric plane|point] [--align-trim f] [--align-iters n]
+         [--align-from each|first] [--align-out DIR]]
 """
 import argparse
 import json
@@ -42,6 +52,14 @@ def build_parser():
     parser.add_argument('--penetration', action='store_true',
                         help='with --intersections --body: also the vertices of the prediction inside the body and their largest depth')
     parser.add_argument('--out', default=None, help='metrics JSON (default: printed only)')
+    parser.add_argument('--align', default='none', choices=['none', 'rigid', 'similarity'],
+                        help='fit the prediction to the ground truth by ICP before the metrics')
+    parser.add_argument('--align-metric', default='plane', choices=['plane', 'point'])
+    parser.add_argument('--align-trim', default=1.0, type=float, help='share of the pairs with the smallest distances that takes part')
+    parser.add_argument('--align-iters', default=50, type=int, help='at most this many ICP steps')
+    parser.add_argument('--align-from', default='each', choices=['each', 'first'],
+                        help='first: the transform of the first pair by stem is applied to every pair')
+    parser.add_argument('--align-out', default=None, help='directory for the aligned predictions (.obj)')
     return parser
 
 
@@ -86,18 +104,41 @@ def main(argv=None):
             parser.error("no such mesh: %s" % args.body)
         if bodies is not None and not all(stem in bodies for stem, _, _ in pairs):
             parser.error("--body %s has no mesh for: %s" % (args.body, ', '.join(s for s, _, _ in pairs if s not in bodies)))
+    if args.align == 'none' and args.align_out:
+        parser.error("--align-out needs --align rigid or --align similarity")
+    if not (0. < args.align_trim <= 1.):
+        parser.error("--align-trim must be in (0, 1]")
+    if args.align_iters < 0:
+        parser.error("--align-iters must not be negative")
     import torch
     from infer_fl_animation import temporal_smoothness
-    from recmv import metrics
-    from recmv.utils import read_obj
+    from recmv import align, metrics
+    from recmv.utils import read_obj, write_obj
 
     device = torch.device('cuda:%d' % args.gpu_ids[0])
     thresholds = tuple(args.thresholds) if args.thresholds else metrics.DEFAULT_THRESHOLDS
-    per_pair, sequence = {}, []
+    per_pair, sequence, alignment, shared = {}, [], {}, None
     for stem, pf, gf in pairs:
         pv, pfaces = read_obj(pf)
         gv, gfaces = read_obj(gf)
         pv = pv * args.scale
+        if args.align != 'none':
+            fit = shared
+            if fit is None:
+                fit = align.icp(pv.to(device), pfaces.to(device), gv.to(device), gfaces.to(device), mode=args.align,
+                                metric=args.align_metric, seed=args.seed,
+                                iters=args.align_iters, trim=args.align_trim, method=args.method)
+                if args.align_from == 'first':
+                    shared = fit
+            alignment[stem] = {k: fit[k] for k in ('scale', 'R', 't', 'iterations', 'converged', 'rms_before', 'rms_after',
+                                                   'pairs')}
+            pv = align.apply(fit, pv)
+            print('%s: aligned (%s, %s): scale %.6g, rms %.6g -> %.6g in %d steps%s' % (
+                stem, args.align, args.align_metric, fit['scale'], fit['rms_before'], fit['rms_after'], fit['iterations'],
+                '' if args.align_from == 'each' or stem == pairs[0][0] else ' of ' + pairs[0][0]))
+            if args.align_out:
+                os.makedirs(args.align_out, exist_ok=True)
+                write_obj(osp.join(args.align_out, stem + '.obj'), pv, pfaces)
         sequence.append((pv, pfaces))
         per_pair[stem] = metrics.surface_distance(pv.to(device), pfaces.to(device), gv.to(device), gfaces.to(device),
                                                   samples=args.samples, seed=args.seed, thresholds=thresholds,
@@ -125,6 +166,10 @@ def main(argv=None):
     mean = {k: sum(m[k] for m in per_pair.values()) / len(per_pair) for k in keys}
     res = {'pairs': per_pair, 'mean': mean, 'samples': args.samples, 'seed': args.seed, 'method': args.method,
            'thresholds': list(thresholds), 'scale': args.scale, 'unmatched_pred': only_pred, 'unmatched_gt': only_gt}
+    if args.align != 'none':                               # (not into pairs[stem]: `mean` sums every key there)
+        res['align'] = {'mode': args.align, 'metric': args.align_metric, 'trim': args.align_trim, 'iters': args.align_iters,
+                        'from': args.align_from}
+        res['alignment'] = alignment
     v0, f0 = sequence[0]
     if osp.isdir(args.pred) and all(v.shape == v0.shape and torch.equal(f, f0) for v, f in sequence):
         res['temporal_smoothness'] = temporal_smoothness(torch.stack([v for v, _ in sequence]).numpy())

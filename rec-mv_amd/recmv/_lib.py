@@ -203,6 +203,9 @@ def _declare(lib):
                                                      vp]),
         "recmv_segment_mesh_brute": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
         "recmv_segment_mesh_grid": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, MG, i32, i32, vp, vp, vp, vp]),
+        "recmv_icp_accumulate_workspace_bytes": (i64, [i64]),
+        "recmv_icp_accumulate": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, C.POINTER(C.c_double), i32, vp, vp, i64,
+                                           vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)       # AttributeError if the symbol is missing: fail loudly

@@ -14,7 +14,8 @@ whose tools/comparison_results.py stops after loading a mesh.
                     share of the mesh — through the grid or by the brute force (recmv_mesh_intersect_brute)
   sample_surface    loop.sample_fan_mesh's area-weighted surface samples, with the picked faces
   surface_distance  accuracy / completeness / Chamfer / normal consistency / precision, recall and F-score at thresholds
-                    between two meshes taken to be in one frame (no alignment), from surface samples in both directions
+                    between two meshes taken to be in one frame (recmv.align.icp brings them into one; eval_fl.py --align),
+                    from surface samples in both directions
 
 Definitions (d the unsquared distance sqrt(dist2) of a sample to the other SURFACE, in the meshes' length unit; every
 reduction in float64 on the device, one read-back):
@@ -447,9 +448,10 @@ def use_grid(method, n_points, n_faces):
     return method == 'grid' or (method == 'auto' and n_points * n_faces >= AUTO_GRID_MIN_TESTS)
 
 
-def _nearest(p, verts, faces, method):
+def _nearest(p, verts, faces, method, grid=None):
+    """(face, point, squared distance) of p on the mesh; `grid`: a MeshGrid of the mesh built before (recmv.align iterates)."""
     if use_grid(method, p.shape[0], faces.shape[0]):
-        return MeshGrid(verts, faces).closest_point(p)
+        return (grid if grid is not None else MeshGrid(verts, faces)).closest_point(p)
     from .iso_remesh import closest_point
     return closest_point(p, verts, faces)
 
