@@ -34,7 +34,8 @@ extern "C" {
 /* ABI version, bumped when an existing signature changes (recmv/_lib.py checks the number at load).
  *   v11: the mesh-grid entry points take a recmv_mesh_grid descriptor in place of the grid's loose arguments
  *        (recmv_mesh_grid_count / _fill, recmv_closest_point_grid, recmv_mesh_intersect_grid_count / _fill,
- *        recmv_segment_mesh_grid).  Added since without a bump: recmv_icp_accumulate and its workspace size.
+ *        recmv_segment_mesh_grid).  Added since without a bump: recmv_icp_accumulate and its workspace size;
+ *        recmv_graph_components, recmv_mesh_face_stats, recmv_segment_sums with its chunk and workspace sizes.
  *   v10: recmv_verts_normals, recmv_hard_phong_shade, recmv_hard_phong_params_floats added.  Added since without a bump (no
  *        existing signature changed, and _lib.py rejects a library that lacks them): recmv_knn1, recmv_nricp_energy,
  *        recmv_lap_align_solve, recmv_lap_smooth, recmv_closest_point, recmv_iso_relax, recmv_loop_subdivide,
@@ -879,6 +880,42 @@ int recmv_icp_accumulate(const float* x, const float* q, const int64_t* face, co
                          const float* verts, int64_t V, const int64_t* faces, int64_t F, const uint8_t* border,
                          const float* max_dist2, const double* centre, int32_t with_plane, double* sums, void* workspace,
                          int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * What a mesh is made of (csrc/mesh_topology.hip; added to ABI v11, no existing signature changed).  Not in the reference.
+ * The kernels of recmv/topology.py: connected components, per-face figures, reproducible per-segment sums.  Integer atomics
+ * only.  Argument errors (negative sizes, K, C, NULL pointers with work to do, a workspace too small) are found before any
+ * HIP call; an empty input is a no-op that returns RECMV_OK.
+ * recmv_graph_components: a graph of n nodes and links [M,K] int64, K = 2 or 3; a row joins its K nodes.  A row with an index
+ *   outside [0, n) or a repeated index is INVALID: it joins nothing.  label [n] int32 ends as the smallest node index of every
+ *   node's component (a node no valid row touches is its own component) — a unique fixpoint, independent of scheduling.
+ *   The call runs `rounds` (0 .. 64) rounds of hook + compress; rounds_done = 0 starts a run (label, parent and state are
+ *   initialised, and the first round counts the invalid rows), rounds_done > 0 continues the run that has had that many
+ *   rounds on the same arrays.  parent [n] int32: workspace of the run.  state [4] int32 on the device: [0] the number (from 1) of
+ *   the last round that hooked anything — the labels are final as soon as state[0] is below the number of rounds run, and
+ *   2 ceil(log2 n) + 2 rounds always suffice (csrc/mesh_topology.hip has the argument); [1] the invalid rows; [2], [3] zero.
+ *   n = 0 or M = 0: nothing is written (every node is its own component).
+ * recmv_mesh_face_stats: per face of verts [V,3] f32 / faces [F,3] int64, computed in float64: area [F] = 0.5 |(b - a) x (c - a)|,
+ *   min_angle [F] = the smallest of the corner angles atan2(|u x w|, u . w) in radians, edge_ratio [F] = longest / shortest edge
+ *   (inf when the shortest is 0).  An invalid face (as above, n = V): area 0, NaN, NaN.  A valid face with a corner that is not
+ *   finite: NaN, NaN, NaN.  counts [2] int32 on the device: the invalid faces, the valid faces with such a corner.
+ * recmv_segment_sums: values [N,C] float64 (C in 1 .. 8) whose rows are sorted by segment, offsets [S + 1] int64 (segment s is
+ *   rows offsets[s] .. offsets[s + 1] - 1): sum, vmin, vmax [S,C] float64 (0, +inf, -inf for an empty segment; a NaN poisons the
+ *   sum and never is a minimum or maximum).  The same bits on every run: a segment is cut into chunks of
+ *   recmv_segment_sums_chunk() rows at fixed places, one wave adds a chunk (lane l the rows l, l + 64, ... in order, then a
+ *   fixed shuffle tree), and a second launch adds a segment's chunk results the same way.  chunk_offsets [S + 1] int64:
+ *   chunk_offsets[s] = the sum over s' < s of ceil(rows of s' / chunk).  Workspace: recmv_segment_sums_workspace_bytes(N, S, C),
+ *   8-byte aligned.  Ranges read from offsets and chunk_offsets are clamped to the arrays.
+ * ---------------------------------------------------------------------------------------------- */
+int recmv_graph_components(int64_t n, const int64_t* links, int64_t M, int32_t K, int32_t rounds_done, int32_t rounds,
+                           int32_t* label, int32_t* parent, int32_t* state, void* stream);
+int recmv_mesh_face_stats(const float* verts, int64_t V, const int64_t* faces, int64_t F, double* area, double* min_angle,
+                          double* edge_ratio, int32_t* counts, void* stream);
+int64_t recmv_segment_sums_chunk(void);
+int64_t recmv_segment_sums_workspace_bytes(int64_t N, int64_t S, int32_t C);
+int recmv_segment_sums(const double* values, int64_t N, int32_t C, const int64_t* offsets, int64_t S,
+                       const int64_t* chunk_offsets, double* sum, double* vmin, double* vmax, void* workspace,
+                       int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,105 @@
+"""clean_fl.py — what exported meshes are made of, and the same meshes without their floaters: an addition, the reference has
+no such command (recmv.topology has the definitions).
+
+`--in` is one `.obj` file or a directory of them.  Every mesh is described (recmv.topology.report: pieces, boundary loops, Euler
+characteristic, watertightness, triangle quality, the largest pieces with their genus), cleaned
+(recmv.topology.keep_components: a piece stays when it passes every rule given — `--largest N`: among the N largest by area,
+`--min-area-frac X`: at least X times the largest piece's area, `--min-faces N`: at least N faces; invalid faces and vertices
+that no kept face uses always go; `--connectivity edge` joins faces only across shared edges), described again and written to
+`--out` under its own name.  `--out`/topology.json holds per file the report `before`, the report `after` and what was
+`dropped`.  With `--report-only` nothing is cleaned or written but topology.json (with `before` alone; printed when there is no
+`--out`): on a registered run it is the check that `registry_<garment>.obj` is one piece with the expected number of boundary
+loops — an upper garment with four feature lines has four.
+
+    python rec-mv_amd/clean_fl.py --gpu-ids 0 --in <obj|dir> --out <dir> [--largest N] [--min-area-frac X] [--min-faces N]
+        [--connectivity vertex|edge] [--report-only]
+"""
+import argparse
+import json
+import os
+import os.path as osp
+import sys
+
+sys.path.insert(0, osp.dirname(osp.abspath(__file__)))
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description='topology report of meshes and removal of their small detached pieces')
+    parser.add_argument('--gpu-ids', nargs='+', type=int, default=[0], metavar='IDs', help='gpu ids (the first is used)')
+    parser.add_argument('--in', dest='inp', required=True, help='mesh (.obj) or a directory of them')
+    parser.add_argument('--out', default=None, help='directory for the cleaned meshes and topology.json')
+    parser.add_argument('--largest', default=None, type=int, help='keep at most this many pieces, the largest by area')
+    parser.add_argument('--min-area-frac', default=None, type=float,
+                        help='keep the pieces with at least this share of the largest piece\'s area')
+    parser.add_argument('--min-faces', default=None, type=int, help='keep the pieces with at least this many faces')
+    parser.add_argument('--connectivity', default='vertex', choices=['vertex', 'edge'],
+                        help='what joins two faces into one piece: a shared vertex, or only a shared edge')
+    parser.add_argument('--report-only', action='store_true', help='describe the meshes, clean and write none')
+    return parser
+
+
+def mesh_files(path):
+    """[(name, file)] of the `.obj` files of a directory sorted by name, or of the one file."""
+    if osp.isdir(path):
+        return [(n, osp.join(path, n)) for n in sorted(os.listdir(path)) if n.lower().endswith('.obj')]
+    if osp.isfile(path):
+        return [(osp.basename(path), path)]
+    raise ValueError("no such mesh or directory: %s" % path)
+
+
+def main(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.min_area_frac is not None and not (0. <= args.min_area_frac <= 1.):
+        parser.error("--min-area-frac must be in [0, 1]")
+    if args.largest is not None and args.largest < 1:
+        parser.error("--largest must be at least 1")
+    if args.min_faces is not None and args.min_faces < 0:
+        parser.error("--min-faces must not be negative")
+    if not args.report_only and not args.out:
+        parser.error("--out is needed unless --report-only is given")
+    try:
+        files = mesh_files(args.inp)
+    except ValueError as e:
+        parser.error(str(e))
+    if not files:
+        parser.error("no .obj file in %s" % args.inp)
+    import torch
+    from recmv import topology
+    from recmv.utils import read_obj, write_obj
+
+    device = torch.device('cuda:%d' % args.gpu_ids[0])
+    res = {}
+    for name, path in files:
+        v, f = read_obj(path)
+        v, f = v.to(device), f.to(device)
+        entry = {'before': topology.report(v, f)}
+        b = entry['before']
+        print('%s: %d faces, %d pieces (%d by edges), %d boundary loops, euler characteristic %d, watertight %s' % (
+            name, b['faces'], b['components_vertex'], b['components_edge'], b['boundary_loops'], b['euler_characteristic'],
+            b['watertight']))
+        if not args.report_only:
+            kv, kf, info = topology.keep_components(v, f, largest=args.largest, min_area_frac=args.min_area_frac,
+                                                    min_faces=args.min_faces, connectivity=args.connectivity)
+            entry['after'] = topology.report(kv, kf)
+            entry['dropped'] = {'components': info['dropped_components'], 'faces': info['dropped_faces'],
+                                'area': info['dropped_area'], 'invalid_faces': info['invalid_faces'],
+                                'vertices': int(v.shape[0] - kv.shape[0])}
+            os.makedirs(args.out, exist_ok=True)
+            write_obj(osp.join(args.out, name), kv, kf)
+            print('%s: dropped %d of %d pieces (%d faces, %d vertices)' % (name, info['dropped_components'], info['components'],
+                                                                          info['dropped_faces'], entry['dropped']['vertices']))
+        res[name] = entry
+    out = {'files': res, 'connectivity': args.connectivity, 'largest': args.largest, 'min_area_frac': args.min_area_frac,
+           'min_faces': args.min_faces, 'report_only': args.report_only}
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+        with open(osp.join(args.out, 'topology.json'), 'w') as fh:
+            json.dump(out, fh, indent=1, sort_keys=True)
+    else:
+        print(json.dumps(out, indent=1, sort_keys=True))
+    return out
+
+
+if __name__ == '__main__':
+    main()

@@ -20,11 +20,16 @@ pair the faces of the prediction that take part in a crossing of the prediction 
 a directory paired by stem, like `--gt`) the prediction's faces that cross that body (`body_intersecting_faces`,
 `body_intersection_ratio`), and with `--penetration` besides the prediction's vertices inside that body and the largest
 distance of one of them to its surface (`body_inside_vertices`, `body_max_depth`); definitions in INTEGRATION.md §5.
+`--drop-floaters FRAC` removes from the prediction, before alignment and metrics, every piece whose area is below FRAC times
+its largest piece's (recmv.topology.keep_components; one floater decides `accuracy_max` and drags the precision down) and
+records what went under `floaters` in the pair's entry; `--topology` adds `topology_pred` and `topology_gt`
+(recmv.topology.report: pieces, boundary loops, Euler characteristic, watertightness, triangle quality) to it.  `mean` is
+taken over the numeric entries.
 
     python rec-mv_amd/eval_fl.py --gpu-ids 0 --pred <obj|dir> --gt <obj|dir> [--samples N] [--seed S] [--thresholds t ...]
         [--scale s] [--method auto|grid|brute] [--intersections [--body <obj|dir> [--penetration]]] [--out metrics.json]
         [--align none|rigid|similarity [--align-metric plane|point] [--align-trim f] [--align-iters n]
-         [--align-from each|first] [--align-out DIR]]
+         [--align-from each|first] [--align-out DIR]] [--drop-floaters FRAC] [--topology]
 """
 import argparse
 import json
@@ -60,6 +65,10 @@ def build_parser():
     parser.add_argument('--align-from', default='each', choices=['each', 'first'],
                         help='first: the transform of the first pair by stem is applied to every pair')
     parser.add_argument('--align-out', default=None, help='directory for the aligned predictions (.obj)')
+    parser.add_argument('--topology', action='store_true',
+                        help='add the topology report of the prediction and of the ground truth to every pair')
+    parser.add_argument('--drop-floaters', default=None, type=float, metavar='FRAC',
+                        help='drop the pieces of the prediction with less than FRAC of its largest piece\'s area, before everything else')
     return parser
 
 
@@ -110,18 +119,29 @@ def main(argv=None):
         parser.error("--align-trim must be in (0, 1]")
     if args.align_iters < 0:
         parser.error("--align-iters must not be negative")
+    if args.drop_floaters is not None and not (0. <= args.drop_floaters <= 1.):
+        parser.error("--drop-floaters must be in [0, 1]")
     import torch
     from infer_fl_animation import temporal_smoothness
-    from recmv import align, metrics
+    from recmv import align, metrics, topology
     from recmv.utils import read_obj, write_obj
 
     device = torch.device('cuda:%d' % args.gpu_ids[0])
     thresholds = tuple(args.thresholds) if args.thresholds else metrics.DEFAULT_THRESHOLDS
-    per_pair, sequence, alignment, shared = {}, [], {}, None
+    per_pair, sequence, alignment, shared, floaters = {}, [], {}, None, {}
     for stem, pf, gf in pairs:
         pv, pfaces = read_obj(pf)
         gv, gfaces = read_obj(gf)
         pv = pv * args.scale
+        if args.drop_floaters is not None:
+            kv, kf, kept = topology.keep_components(pv.to(device), pfaces.to(device), min_area_frac=args.drop_floaters)
+            floaters[stem] = {'min_area_frac': args.drop_floaters, 'components': kept['components'],
+                              'dropped_components': kept['dropped_components'], 'dropped_faces': kept['dropped_faces'],
+                              'dropped_area': kept['dropped_area'], 'invalid_faces': kept['invalid_faces'],
+                              'vertices': int(kv.shape[0]), 'faces': int(kf.shape[0])}
+            pv, pfaces = kv.cpu(), kf.cpu()
+            print('%s: dropped %d of %d pieces (%d faces)' % (stem, kept['dropped_components'], kept['components'],
+                                                              kept['dropped_faces']))
         if args.align != 'none':
             fit = shared
             if fit is None:
@@ -159,10 +179,15 @@ def main(argv=None):
                 if args.penetration:
                     pen = metrics.penetration(pv.to(device), bv.to(device), bfaces.to(device), method=args.method)
                     per_pair[stem].update({'body_inside_vertices': pen['count'], 'body_max_depth': pen['max_depth']})
+        if stem in floaters:
+            per_pair[stem]['floaters'] = floaters[stem]
+        if args.topology:
+            per_pair[stem]['topology_pred'] = topology.report(pv.to(device), pfaces.to(device))
+            per_pair[stem]['topology_gt'] = topology.report(gv.to(device), gfaces.to(device))
         print('%s: chamfer_l1 %.6g, accuracy %.6g, completeness %.6g, normal consistency %.4f' % (
             stem, per_pair[stem]['chamfer_l1'], per_pair[stem]['accuracy'], per_pair[stem]['completeness'],
             per_pair[stem]['normal_consistency']))
-    keys = list(next(iter(per_pair.values())))
+    keys = [k for k, x in next(iter(per_pair.values())).items() if not isinstance(x, dict)]
     mean = {k: sum(m[k] for m in per_pair.values()) / len(per_pair) for k in keys}
     res = {'pairs': per_pair, 'mean': mean, 'samples': args.samples, 'seed': args.seed, 'method': args.method,
            'thresholds': list(thresholds), 'scale': args.scale, 'unmatched_pred': only_pred, 'unmatched_gt': only_gt}

@@ -206,6 +206,11 @@ def _declare(lib):
         "recmv_icp_accumulate_workspace_bytes": (i64, [i64]),
         "recmv_icp_accumulate": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, C.POINTER(C.c_double), i32, vp, vp, i64,
                                            vp]),
+        "recmv_graph_components": (C.c_int, [i64, vp, i64, i32, i32, i32, vp, vp, vp, vp]),
+        "recmv_mesh_face_stats": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+        "recmv_segment_sums_chunk": (i64, []),
+        "recmv_segment_sums_workspace_bytes": (i64, [i64, i64, i32]),
+        "recmv_segment_sums": (C.c_int, [vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)       # AttributeError if the symbol is missing: fail loudly
