@@ -28,6 +28,7 @@ import torch
 
 from . import _lib as L
 from . import metrics
+from .connectivity import EdgeTable
 
 N_SUMS = 56                     # RECMV_ICP_SUMS of include/recmv_hip.h
 MODES = ('rigid', 'similarity')
@@ -42,20 +43,9 @@ def border_flags(faces, n_verts):
     """uint8 [F] for faces [F,3] int64 (CPU or CUDA): bit 0 / 1 / 2 — the edge ab / ac / bc is used by exactly one face (a
     border edge); bit 3 / 4 / 5 — the vertex a / b / c is an end of some border edge (a border vertex, in every face that
     contains it).  A closed mesh gives zeros."""
-    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("faces must be int64 of shape [F,3]")
-    F, n = faces.shape[0], int(n_verts)
-    if F == 0:
-        return torch.zeros(0, dtype=torch.uint8, device=faces.device)
-    if int(faces.min()) < 0 or int(faces.max()) >= n:
-        raise ValueError("border_flags: a face index lies outside [0, %d)" % n)
-    ends = faces[:, [0, 1, 0, 2, 1, 2]].reshape(F, 3, 2)                           # ab, ac, bc
-    key = (ends.amin(-1) * n + ends.amax(-1)).reshape(-1)
-    _, inverse, count = torch.unique(key, return_inverse=True, return_counts=True)
-    edge = (count[inverse] == 1).reshape(F, 3)
-    vert = torch.zeros(n, dtype=torch.bool, device=faces.device)
-    vert[ends[edge].reshape(-1)] = True
-    bits = torch.cat([edge, vert[faces]], 1).to(torch.uint8)                       # [F,6]
+    table = EdgeTable(faces, n_verts)
+    edge = table.boundary_edge[table.face_to_edge[:, [2, 1, 0]]]                   # ab, ac, bc
+    bits = torch.cat([edge, table.boundary_vertex[faces]], 1).to(torch.uint8)      # [F,6]
     weight = torch.tensor([1, 2, 4, 8, 16, 32], dtype=torch.uint8, device=faces.device)
     return (bits * weight).sum(1, dtype=torch.int32).to(torch.uint8)
 

@@ -16,6 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
+from .connectivity import boundary_loops
 from .utils.constant import FL_EXTRACT, ZBUF_THRESHOLD  # noqa: E402,F401  (utils/constant.py:65-74, :219-227)
 
 FIT_ITERS = 20000            # AdamW steps of curve_to_mesh's fit to boundary loops (garment_structure.py:188)
@@ -198,31 +199,13 @@ def fit_curves_to_loops(curve, targets, target_idx, iters=FIT_ITERS, lr=1e-4, st
 def longest_boundary_loop(faces):
     """Vertex indices along the longer of the two boundary loops of a ribbon mesh — the curve a template feature line stands
     for (`Intersect_Free_Curve.extract_edge`, engineer/utils/garment_structure.py:149-173, which asks trimesh's `outline()`
-    for the boundary paths and keeps the one with more points).  trimesh is third party and absent: the loops are found here
-    by walking the edges that belong to exactly one face, starting at each loop's lowest vertex index towards its lower
-    neighbour — the same point set; start and direction of trimesh's path are not reproduced (parity unpinned)."""
-    import numpy as np
-    f = np.asarray(faces.detach().cpu().numpy() if torch.is_tensor(faces) else faces, dtype=np.int64)
-    edges = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]], axis=0), axis=1)
-    uniq, count = np.unique(edges, axis=0, return_counts=True)
-    border = uniq[count == 1]
-    nbrs = {}
-    for a, b in border:
-        nbrs.setdefault(int(a), []).append(int(b))
-        nbrs.setdefault(int(b), []).append(int(a))
-    assert all(len(v) == 2 for v in nbrs.values()), "a feature-line template is a band: every boundary vertex has two boundary edges"
-    loops, seen = [], set()
-    for start in sorted(nbrs):
-        if start in seen:
-            continue
-        loop, prev, cur = [start], start, min(nbrs[start])
-        seen.add(start)
-        while cur != start:
-            loop.append(cur)
-            seen.add(cur)
-            a, b = nbrs[cur]
-            prev, cur = cur, (b if a == prev else a)
-        loops.append(loop)
+    for the boundary paths and keeps the one with more points).  trimesh is third party and absent: the loops are
+    connectivity.boundary_loops' walks over the edges that belong to exactly one face, each from its lowest vertex index
+    towards its lower neighbour — the same point set; start and direction of trimesh's path are not reproduced (parity
+    unpinned)."""
+    loops = boundary_loops(faces)
+    walked = [v for loop in loops for v in loop]           # a vertex with four boundary edges is walked through twice
+    assert len(walked) == len(set(walked)), "a feature-line template is a band: every boundary vertex has two boundary edges"
     assert len(loops) == 2, "a feature-line template has two boundary loops, found %d" % len(loops)
     return loops[0] if len(loops[0]) > len(loops[1]) else loops[1]
 

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib as L
 from . import nricp
+from .connectivity import EdgeTable, compact, neighbours_csr
 
 MAX_PASSES = 16                    # split passes, collapse rounds and flip rounds per iteration
 
@@ -161,33 +162,27 @@ def _csr_rows(off, rows):
     return which, pos
 
 
-class _Topo:
-    """Edges and adjacency of one face table: edges [E,2] (v0 < v1, edges_packed order), f2e [F,3], per edge its face
-    count and its first / second (face * 3 + corner) slot — the corner opposite the edge — in ascending slot order,
-    boundary and valence per vertex, the neighbour CSR and the vertex -> face CSR."""
+class _Topo(EdgeTable):
+    """The EdgeTable of one edge-manifold face table (f2e / bedge / bvert: its face_to_edge / boundary_edge / boundary_vertex)
+    and what the remesher adds: per edge its first / second (face * 3 + corner) slot — the corner opposite the edge — in
+    ascending slot order, the valence per vertex, the neighbour CSR and the vertex -> face CSR."""
 
     def __init__(self, faces, V):
-        dev = faces.device
-        F = faces.shape[0]
-        self.V, self.F = V, F
-        self.edges, self.f2e = nricp.edges_packed(faces, V)
-        E = self.E = self.edges.shape[0]
+        super().__init__(faces, V)
+        dev, F, E = faces.device, self.F, self.E
+        self.f2e, self.bedge, self.bvert = self.face_to_edge, self.boundary_edge, self.boundary_vertex
+        if E and int(self.count.max()) > 2:
+            raise ValueError("iso_remesh: the mesh must be edge-manifold (an edge has %d faces)" % int(self.count.max()))
         fe = self.f2e.reshape(-1)
         slots = torch.arange(3 * F, device=dev)
         order = torch.argsort(fe * (3 * F) + slots)
-        self.count = torch.bincount(fe, minlength=E)
-        if E and int(self.count.max()) > 2:
-            raise ValueError("iso_remesh: the mesh must be edge-manifold (an edge has %d faces)" % int(self.count.max()))
         start = torch.cumsum(self.count, 0) - self.count
         self.slot0 = order[start]
         self.slot1 = torch.where(self.count > 1, order[(start + 1).clamp(max=max(3 * F - 1, 0))],
                                  torch.full_like(start, -1))
-        self.bedge = self.count == 1
-        self.bvert = torch.zeros(V, dtype=torch.bool, device=dev)
-        self.bvert[self.edges[self.bedge].reshape(-1)] = True
         ones = torch.ones(2 * E, dtype=torch.int64, device=dev)
         self.valence = torch.zeros(V, dtype=torch.int64, device=dev).index_add(0, self.edges.reshape(-1), ones)
-        self.nbr = nricp.neighbours_csr(self.edges, V)
+        self.nbr = neighbours_csr(self.edges, V)
         fv = faces.reshape(-1)
         o = torch.argsort(fv * (3 * F) + slots)
         cnt = torch.bincount(fv, minlength=V)
@@ -251,13 +246,6 @@ def _boundary_loop_length(faces, topo):
     out = torch.zeros(topo.E, dtype=torch.int64, device=dev)
     out[be] = size[label[a]]
     return out
-
-
-def _compact(verts, faces):
-    used = torch.zeros(verts.shape[0], dtype=torch.bool, device=verts.device)
-    used[faces.reshape(-1)] = True
-    remap = torch.cumsum(used.to(torch.int64), 0) - 1
-    return verts[used], remap[faces]
 
 
 class _Surface:
@@ -426,7 +414,7 @@ def _collapse(verts, faces, lo, hi, cos_feature, max_dist, surf):
         remap[cb] = ca
         faces = remap[faces]
         faces = faces[(faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 2] != faces[:, 0])]
-        verts, faces = _compact(verts, faces)
+        verts, faces, _ = compact(verts, faces)
     return verts, faces, collapses
 
 
@@ -532,7 +520,7 @@ def isotropic_remesh(verts, faces, target_len=None, iterations=3, feature_deg=30
         L.require_cuda(verts, "verts")
     if faces.shape[0] == 0:
         raise ValueError("isotropic_remesh: the mesh has no faces")
-    verts, faces = _compact(verts, faces)
+    verts, faces, _ = compact(verts, faces)
     diag = float((verts.max(0)[0] - verts.min(0)[0]).norm())
     L_ = float(target_len) if target_len is not None else 0.01 * diag
     if not L_ > 0:

@@ -2,7 +2,7 @@
 (engineer/optimizer/lap_deform_optimizer.py:25-190, with `Garment_Mesh.best_match`, engineer/utils/garment_structure.py:647-724).
 
 Matching (plain numpy / torch, once per epoch, on the CPU):
-  boundary_loops          closed walks over the edges that only one face uses
+  boundary_loops          closed walks over the edges that only one face uses (recmv.connectivity)
   assign_loops            which loop stands for which feature line: the templates here are plain meshes without the SMPL
                           colour labels the reference cuts its fields by, so every field of GARMENT_FL_MATCH[garment] gets a
                           distinct loop by a linear assignment on the squared distance between loop and curve centroids
@@ -22,6 +22,7 @@ import torch
 
 from . import _lib as L
 from . import nricp
+from .connectivity import boundary_loops  # noqa: F401  (the walk; callers say lap_align.boundary_loops)
 
 TOL = 1e-10                  # CG stops when |r| <= TOL |rhs| in every column
 MAX_ITER = 50000             # ... or after this many iterations
@@ -30,47 +31,6 @@ COS_MIN = 0.5                # best_match's centred-direction filter (garment_st
 
 
 # ------------------------------------------------------------------------------------------------- matching
-def boundary_loops(faces, V=None):
-    """Boundary loops of a triangle mesh: lists of vertex indices along closed walks over the edges used by one face.
-    Each walk starts at the lowest vertex index with an unwalked boundary edge and always takes the lowest unwalked
-    neighbour, so the result is deterministic (a vertex where two loops touch appears in both)."""
-    f = np.asarray(faces.detach().cpu().numpy() if torch.is_tensor(faces) else faces, dtype=np.int64).reshape(-1, 3)
-    if f.shape[0] == 0:
-        return []
-    e = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]], axis=0), axis=1)
-    uniq, count = np.unique(e, axis=0, return_counts=True)
-    border = uniq[count == 1]
-    nbrs = {}
-    for a, b in border.tolist():
-        nbrs.setdefault(a, []).append(b)
-        nbrs.setdefault(b, []).append(a)
-    for k in nbrs:
-        nbrs[k].sort()
-    used = set()
-
-    def step(cur):
-        for n in nbrs[cur]:
-            if (min(cur, n), max(cur, n)) not in used:
-                return n
-        return None
-
-    loops = []
-    for start in sorted(nbrs):
-        while step(start) is not None:
-            loop, cur = [start], start
-            while True:
-                n = step(cur)
-                if n is None:
-                    break
-                used.add((min(cur, n), max(cur, n)))
-                if n == start:
-                    break
-                loop.append(n)
-                cur = n
-            loops.append(loop)
-    return loops
-
-
 def assign_loops(loops, verts, curves, fields, log=print, garment=''):
     """{field: loop index}: every field of `fields` that has a curve in `curves` ({name: [S,3]}) gets a distinct loop by
     linear_sum_assignment on the squared distance between the loop's and the curve's centroids.  A field without a curve,

@@ -1,17 +1,15 @@
-"""Non-rigid ICP building blocks: mesh topology helpers (plain torch, once per fit), the HIP kernels of csrc/nricp.hip and
-their plain-torch restatements.
+"""Non-rigid ICP building blocks: the HIP kernels of csrc/nricp.hip, their plain-torch restatements and the mesh helpers of a
+fit.  The edge tables (edges_packed, the CSR lists, the boundary) are recmv.connectivity's; their names stay importable here.
 
-Topology, as the reference's tools compute it:
-  edges_packed        pytorch3d `Meshes.edges_packed` (unique undirected edges, sorted) and `faces_packed_to_edges_packed`
   mesh_boundary       engineer/utils/mesh_utils.py:88 (vertices of edges used by one face)
   edge_subdivide      Garment_Mesh.__edge_dense_pcl (engineer/utils/garment_structure.py:989-1030) without colour labels
-  incident_edges_csr / neighbours_csr   the lists recmv_nricp_energy gathers over
 Kernels: knn1 (pytorch3d knn_points K=1 + knn_gather) and nricp_energy (one inner iteration of NRICP_Optimizer_AdamW,
 forward and gradient).  `knn1_torch` and `laplacian_smoothing_torch` are the restatements the torch path and the tests use.
 """
 import torch
 
 from . import _lib as L
+from .connectivity import EdgeTable, edges_packed, incident_edges_csr, neighbours_csr  # noqa: F401  (callers say K.edges_packed)
 
 
 class TriMesh:
@@ -29,32 +27,9 @@ class TriMesh:
 
 
 # ------------------------------------------------------------------------------------------------- topology
-def edges_packed(faces, V):
-    """(edges [E,2] int64, v0 < v1, sorted by V * v0 + v1; face_to_edge [F,3]: the edges (v1,v2), (v2,v0), (v0,v1) of
-    every face) — pytorch3d's `_compute_edges_packed`."""
-    faces = faces.to(torch.int64)
-    F = faces.shape[0]
-    v0, v1, v2 = faces.chunk(3, dim=1)
-    e = torch.cat([torch.cat([v1, v2], 1), torch.cat([v2, v0], 1), torch.cat([v0, v1], 1)], 0)
-    e, _ = e.sort(dim=1)
-    h = V * e[:, 0] + e[:, 1]
-    u, inverse = torch.unique(h, return_inverse=True)
-    edges = torch.stack([u // V, u % V], dim=1)
-    face_to_edge = inverse[torch.arange(3 * F, device=faces.device).view(3, F).t()]
-    return edges, face_to_edge
-
-
 def mesh_boundary(faces, V):
     """bool [V]: True on a vertex of an edge that only one face uses (engineer/utils/mesh_utils.py:88-116)."""
-    x, y, z = faces[:, 0], faces[:, 1], faces[:, 2]
-    h = torch.cat([torch.minimum(x * V + y, y * V + x), torch.minimum(x * V + z, z * V + x),
-                   torch.minimum(y * V + z, z * V + y)], 0)
-    out, count = torch.unique(h, return_counts=True, dim=0)
-    b = out[count == 1]
-    mask = torch.zeros(V, dtype=torch.bool, device=faces.device)
-    mask[b // V] = True
-    mask[b % V] = True
-    return mask
+    return EdgeTable(faces, V).boundary_vertex
 
 
 def edge_subdivide(verts, faces):
@@ -75,27 +50,6 @@ def densify(verts, faces, dense_pcl):
     while verts.shape[0] < dense_pcl:
         verts, faces = edge_subdivide(verts, faces)
     return verts, faces
-
-
-def _csr(rows, cols, V):
-    """Rows sorted by (row, col): (offsets int32 [V+1], cols int32)."""
-    order = torch.argsort(rows * max(int(cols.max()) + 1 if cols.numel() else 1, 1) + cols)
-    counts = torch.bincount(rows, minlength=V)
-    offsets = torch.zeros(V + 1, dtype=torch.int64, device=rows.device)
-    offsets[1:] = torch.cumsum(counts, 0)
-    return offsets.to(torch.int32).contiguous(), cols[order].to(torch.int32).contiguous()
-
-
-def incident_edges_csr(edges, V):
-    """Vertex -> incident edge indices, ascending: (offsets int32 [V+1], edge ids int32 [2E])."""
-    E = edges.shape[0]
-    eid = torch.arange(E, device=edges.device, dtype=torch.int64)
-    return _csr(torch.cat([edges[:, 0], edges[:, 1]]), torch.cat([eid, eid]), V)
-
-
-def neighbours_csr(edges, V):
-    """Vertex -> neighbour vertices, ascending: (offsets int32 [V+1], neighbours int32 [2E]); degree = row length."""
-    return _csr(torch.cat([edges[:, 0], edges[:, 1]]), torch.cat([edges[:, 1], edges[:, 0]]), V)
 
 
 def laplacian_smoothing_torch(verts, edges):
@@ -171,11 +125,10 @@ class EnergyTopology:
     """The per-fit lists recmv_nricp_energy reads: edges, incident-edge and neighbour CSR lists, interior mask."""
 
     def __init__(self, faces, V, device):
-        faces = faces.to(device)
+        table = EdgeTable(faces.to(device=device, dtype=torch.int64), V)
         self.V = V
-        self.edges, _ = edges_packed(faces, V)
-        self.edges = self.edges.contiguous()
-        self.interior = torch.logical_not(mesh_boundary(faces, V))
+        self.edges = table.edges.contiguous()
+        self.interior = torch.logical_not(table.boundary_vertex)
         self.inc = incident_edges_csr(self.edges, V)
         self.nbr = neighbours_csr(self.edges, V)
 

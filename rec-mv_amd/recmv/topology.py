@@ -33,6 +33,7 @@ import math
 import torch
 
 from . import _lib as L
+from .connectivity import EdgeTable, compact, edges_packed
 from .metrics import _check_mesh
 
 # Rounds of hook + compress launched between two read-backs of the device's "last round that hooked" counter.  A read-back
@@ -146,15 +147,6 @@ def _total(values):
     return s[0, 0], lo[0, 0], hi[0, 0]
 
 
-def _half_edges(faces, face_ids, n_verts):
-    """The 3 half-edges of the faces `face_ids` (valid ones): (key = min * V + max [3 Fv], face id, whether it runs from the
-    smaller to the larger index), ordered edge 0 of every face, then edge 1, then edge 2."""
-    f = faces[face_ids]
-    a = torch.cat([f[:, 0], f[:, 1], f[:, 2]])
-    b = torch.cat([f[:, 1], f[:, 2], f[:, 0]])
-    return torch.minimum(a, b) * n_verts + torch.maximum(a, b), face_ids.repeat(3), a < b
-
-
 @torch.no_grad()
 def components(verts, faces, connectivity='vertex'):
     """The pieces of the mesh verts [V,3] f32 / faces [F,3] int64 (CUDA) — the module docstring has the definitions.  A dict:
@@ -179,10 +171,10 @@ def components(verts, faces, connectivity='vertex'):
         label, info = graph_components(V, faces, return_info=True)                # (an invalid face is a row that joins nothing)
         face_label = label[faces[vf, 0]]
     else:
-        key, hface, _ = _half_edges(faces, vf, V)
-        order = torch.sort(key)[1]
-        key, hface = key[order], hface[order]
-        same = key[1:] == key[:-1]
+        # the half-edges face by face, sorted by edge id; the sort is stable, so the faces of an edge are chained in face order
+        edge, order = torch.sort(edges_packed(faces[vf], max(V, 1))[1].reshape(-1), stable=True)
+        hface = vf[order // 3]
+        same = edge[1:] == edge[:-1]
         label, info = graph_components(F, torch.stack([hface[:-1][same], hface[1:][same]], 1), return_info=True)
         face_label = label[vf]
     roots, dense = torch.unique(face_label, return_inverse=True)                  # sorted: the order of the smallest member
@@ -234,13 +226,12 @@ def report(verts, faces, top=8):
     area, angle, _, counts = face_stats(verts, faces)
     nonfinite = int(counts[1].item())
     fine = vf[~torch.isnan(area[vf])]                                              # valid, every corner finite
-    key, _, forward = _half_edges(faces, vf, V)
-    ukey, inv, uses = torch.unique(key, return_inverse=True, return_counts=True)
-    E = int(ukey.shape[0])
-    ea, eb = (ukey // V, ukey % V) if V else (ukey, ukey)
-    ahead = torch.zeros(E, dtype=torch.int64, device=dev).index_add_(0, inv, forward.long())
-    boundary, nonmanifold = uses == 1, uses > 2
-    conflict = (uses == 2) & (ahead != 1)
+    table = EdgeTable(faces[vf], V)
+    E, ea, eb = table.E, table.edges[:, 0], table.edges[:, 1]
+    ahead = torch.zeros(E, dtype=torch.int64, device=dev).index_add_(0, table.face_to_edge.reshape(-1),
+                                                                     table.forward.reshape(-1).long())
+    boundary, nonmanifold = table.boundary_edge, table.nonmanifold_edge
+    conflict = (table.count == 2) & (ahead != 1)
     border = torch.stack([ea[boundary], eb[boundary]], 1)
     loop_label = graph_components(V, border)
     degree = torch.bincount(border.reshape(-1), minlength=V)
@@ -320,12 +311,10 @@ def keep_components(verts, faces, largest=None, min_area_frac=None, min_faces=No
         keep = [k and per[c] >= int(min_faces) for c, k in enumerate(keep)]
     keep_t = torch.tensor(keep + [False], dtype=torch.bool, device=dev)            # (the last entry: component -1, invalid faces)
     kept_faces = keep_t[comp['face_component']].nonzero().squeeze(1)
-    used = torch.zeros(verts.shape[0], dtype=torch.bool, device=dev)
-    used[faces[kept_faces].reshape(-1)] = True
-    vertex_map = torch.where(used, torch.cumsum(used.long(), 0) - 1, torch.full((verts.shape[0],), -1, dtype=torch.int64, device=dev))
+    new_verts, new_faces, vertex_map = compact(verts, faces[kept_faces])
     dropped = [c for c in range(Cn) if not keep[c]]
     info = {'kept_faces': kept_faces, 'vertex_map': vertex_map, 'components': Cn,
             'kept_components': [c for c in range(Cn) if keep[c]], 'dropped_components': len(dropped),
             'dropped_faces': sum(per[c] for c in dropped), 'dropped_area': math.fsum(area[c] for c in dropped),
             'invalid_faces': comp['invalid_faces']}
-    return verts[used].contiguous(), vertex_map[faces[kept_faces]].contiguous(), info
+    return new_verts.contiguous(), new_faces.contiguous(), info

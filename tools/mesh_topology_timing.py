@@ -81,14 +81,13 @@ def main(argv=None):
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     import torch
-    from recmv import topology
+    from recmv import connectivity, topology
     dev = torch.device("cuda:0")
     v, f = scene(args.levels, args.floaters, dev)
     V, F = v.shape[0], f.shape[0]
-    key, hface, _ = topology._half_edges(f, torch.arange(F, device=dev), V)
-    order = torch.sort(key)[1]
-    key, hface = key[order], hface[order]
-    same = key[1:] == key[:-1]
+    edge, order = torch.sort(connectivity.edges_packed(f, V)[1].reshape(-1), stable=True)     # as topology.components does
+    hface = order // 3
+    same = edge[1:] == edge[:-1]
     pairs = torch.stack([hface[:-1][same], hface[1:][same]], 1).contiguous()
     perm = torch.randperm(V, generator=torch.Generator().manual_seed(0)).to(dev)
     chain = torch.arange(V - 1, device=dev)
