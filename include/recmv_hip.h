@@ -35,7 +35,8 @@ extern "C" {
  *   v11: the mesh-grid entry points take a recmv_mesh_grid descriptor in place of the grid's loose arguments
  *        (recmv_mesh_grid_count / _fill, recmv_closest_point_grid, recmv_mesh_intersect_grid_count / _fill,
  *        recmv_segment_mesh_grid).  Added since without a bump: recmv_icp_accumulate and its workspace size;
- *        recmv_graph_components, recmv_mesh_face_stats, recmv_segment_sums with its chunk and workspace sizes.
+ *        recmv_graph_components, recmv_mesh_face_stats, recmv_segment_sums with its chunk and workspace sizes;
+ *        recmv_vertex_quadrics, recmv_edge_collapse_cost, recmv_collapse_flip_check.
  *   v10: recmv_verts_normals, recmv_hard_phong_shade, recmv_hard_phong_params_floats added.  Added since without a bump (no
  *        existing signature changed, and _lib.py rejects a library that lacks them): recmv_knn1, recmv_nricp_energy,
  *        recmv_lap_align_solve, recmv_lap_smooth, recmv_closest_point, recmv_iso_relax, recmv_loop_subdivide,
@@ -916,6 +917,42 @@ int64_t recmv_segment_sums_workspace_bytes(int64_t N, int64_t S, int32_t C);
 int recmv_segment_sums(const double* values, int64_t N, int32_t C, const int64_t* offsets, int64_t S,
                        const int64_t* chunk_offsets, double* sum, double* vmin, double* vmax, void* workspace,
                        int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Quadric-error edge collapse (csrc/mesh_simplify.hip; added to ABI v11, no existing signature changed).  Not in the
+ * reference.  The kernels of recmv/simplify.py.  verts [V,3] f32, faces [F,3] int64; a face with an index outside [0, V) or a
+ * repeated index is INVALID and contributes nothing.  Integer atomics only (counters); every float64 sum is one thread's loop
+ * in table order, so results have the same bits on every run.  Argument errors (negative sizes, a weight or reach that is
+ * negative or not finite, NULL pointers with work to do) are found before any HIP call; an empty input (V = 0, E = 0) is a
+ * no-op that returns RECMV_OK.  Every index read from a table is checked against its array and row ranges are clamped.
+ * recmv_vertex_quadrics: Q [V,11] float64 = per vertex the entries xx xy xz xw yy yz yw zz zw ww of the Garland-Heckbert
+ *   quadric and a weight.  vf_offsets [V + 1] / vf_faces [n_vf] int64: vertex -> its faces, ascending; every face of the row
+ *   adds area * (n, d)(n, d)^T (unit normal, plane through its first corner) and its area to the weight, in row order.
+ *   border [B,3] int64 = (a, b, face): the boundary edges (used by one face) with that face; vb_offsets [V + 1] / vb_rows [n_vb]
+ *   int64: vertex -> its rows of border, ascending; every one adds, after the faces, boundary_weight * |b - a|^2 * (m, d)(m, d)^T,
+ *   m the unit vector of n x (b - a) (in the face's plane, perpendicular to the edge), the plane through a; nothing to the
+ *   weight.  Geometry in float64 from the f32 coordinates.  A face without area or with a corner that is not finite adds
+ *   nothing.  counts [1] int32 on the device: the invalid faces.
+ * recmv_edge_collapse_cost: candidate edges [E,2] int64 (a, b) and code [E] uint8: 1 the vertex stays at a, 2 at b, anything else
+ *   free.  With q = Q[a] + Q[b] the candidates of a free edge are, in this order, the solution of the 3x3 system (float64
+ *   cofactors), a, b, the midpoint; each is rounded to f32 and its cost x^T q x evaluated in float64 at the rounded point and
+ *   clamped at 0; the smallest wins, a tie goes to the earlier.  The solved point takes part only when it is finite and lies
+ *   within reach * |b - a| of the midpoint.  pos [E,3] f32, cost [E] float64, weight [E] float64 = Q[a][10] + Q[b][10].  An edge
+ *   with an index outside [0, V) or a == b: pos 0, the largest finite cost, weight 0; counts [1] int32 on the device counts them.
+ * recmv_collapse_flip_check: ok [E] uint8 = 1 when every face of a, then of b (vf tables as above), that does not hold both
+ *   ends keeps n_old . n_new > 0 with the moved end at pos [E,3] f32 (cross products in float64); 0 otherwise and for an edge
+ *   as above.
+ * ---------------------------------------------------------------------------------------------- */
+int recmv_vertex_quadrics(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* vf_offsets,
+                          const int64_t* vf_faces, int64_t n_vf, const int64_t* border, int64_t B, const int64_t* vb_offsets,
+                          const int64_t* vb_rows, int64_t n_vb, double boundary_weight, double* Q, int32_t* counts,
+                          void* stream);
+int recmv_edge_collapse_cost(const double* Q, const float* verts, int64_t V, const int64_t* edges, int64_t E,
+                             const uint8_t* code, double reach, float* pos, double* cost, double* weight, int32_t* counts,
+                             void* stream);
+int recmv_collapse_flip_check(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* vf_offsets,
+                              const int64_t* vf_faces, int64_t n_vf, const int64_t* edges, int64_t E, const float* pos,
+                              uint8_t* ok, void* stream);
 
 #ifdef __cplusplus
 }

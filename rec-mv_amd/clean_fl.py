@@ -6,13 +6,16 @@ characteristic, watertightness, triangle quality, the largest pieces with their 
 (recmv.topology.keep_components: a piece stays when it passes every rule given — `--largest N`: among the N largest by area,
 `--min-area-frac X`: at least X times the largest piece's area, `--min-faces N`: at least N faces; invalid faces and vertices
 that no kept face uses always go; `--connectivity edge` joins faces only across shared edges), described again and written to
-`--out` under its own name.  `--out`/topology.json holds per file the report `before`, the report `after` and what was
-`dropped`.  With `--report-only` nothing is cleaned or written but topology.json (with `before` alone; printed when there is no
-`--out`): on a registered run it is the check that `registry_<garment>.obj` is one piece with the expected number of boundary
+`--out` under its own name.  `--simplify-faces N` or `--simplify-ratio R` and / or `--simplify-max-error E` then thin what is left
+(recmv.simplify.simplify: quadric-error edge collapse down to N faces, or to the share R of the cleaned mesh's faces, never
+moving the surface by more than E in the root-mean-square sense of the quadrics) before it is described and written; the mesh
+must be edge-manifold by then.  `--out`/topology.json holds per file the report `before`, the report `after` and what was
+`dropped`, and with a simplify flag `simplify`: that call's info.  With `--report-only` nothing is cleaned or written but
+topology.json (with `before` alone; printed when there is no `--out`): on a registered run it is the check that `registry_<garment>.obj` is one piece with the expected number of boundary
 loops — an upper garment with four feature lines has four.
 
     python rec-mv_amd/clean_fl.py --gpu-ids 0 --in <obj|dir> --out <dir> [--largest N] [--min-area-frac X] [--min-faces N]
-        [--connectivity vertex|edge] [--report-only]
+        [--connectivity vertex|edge] [--simplify-faces N | --simplify-ratio R] [--simplify-max-error E] [--report-only]
 """
 import argparse
 import json
@@ -34,6 +37,11 @@ def build_parser():
     parser.add_argument('--min-faces', default=None, type=int, help='keep the pieces with at least this many faces')
     parser.add_argument('--connectivity', default='vertex', choices=['vertex', 'edge'],
                         help='what joins two faces into one piece: a shared vertex, or only a shared edge')
+    parser.add_argument('--simplify-faces', default=None, type=int, help='after cleaning, simplify every mesh to this many faces')
+    parser.add_argument('--simplify-ratio', default=None, type=float,
+                        help='after cleaning, simplify every mesh to this share of its faces')
+    parser.add_argument('--simplify-max-error', default=None, type=float,
+                        help='no collapse whose quadric error (a length) is above this; alone: collapse until none is left')
     parser.add_argument('--report-only', action='store_true', help='describe the meshes, clean and write none')
     return parser
 
@@ -56,6 +64,17 @@ def main(argv=None):
         parser.error("--largest must be at least 1")
     if args.min_faces is not None and args.min_faces < 0:
         parser.error("--min-faces must not be negative")
+    if args.simplify_faces is not None and args.simplify_ratio is not None:
+        parser.error("give --simplify-faces or --simplify-ratio, not both")
+    if args.simplify_faces is not None and args.simplify_faces < 0:
+        parser.error("--simplify-faces must not be negative")
+    if args.simplify_ratio is not None and not (0. <= args.simplify_ratio <= 1.):
+        parser.error("--simplify-ratio must be in [0, 1]")
+    if args.simplify_max_error is not None and not (args.simplify_max_error >= 0.):
+        parser.error("--simplify-max-error must not be negative")
+    simplifying = not (args.simplify_faces is None and args.simplify_ratio is None and args.simplify_max_error is None)
+    if simplifying and args.report_only:
+        parser.error("--report-only writes no mesh: the simplify flags need --out")
     if not args.report_only and not args.out:
         parser.error("--out is needed unless --report-only is given")
     try:
@@ -81,6 +100,11 @@ def main(argv=None):
         if not args.report_only:
             kv, kf, info = topology.keep_components(v, f, largest=args.largest, min_area_frac=args.min_area_frac,
                                                     min_faces=args.min_faces, connectivity=args.connectivity)
+            if simplifying:
+                from recmv import simplify
+                kept = int(kf.shape[0])
+                kv, kf, entry['simplify'] = simplify.simplify(kv, kf, target_faces=args.simplify_faces, ratio=args.simplify_ratio,
+                                                              max_error=args.simplify_max_error)
             entry['after'] = topology.report(kv, kf)
             entry['dropped'] = {'components': info['dropped_components'], 'faces': info['dropped_faces'],
                                 'area': info['dropped_area'], 'invalid_faces': info['invalid_faces'],
@@ -89,9 +113,16 @@ def main(argv=None):
             write_obj(osp.join(args.out, name), kv, kf)
             print('%s: dropped %d of %d pieces (%d faces, %d vertices)' % (name, info['dropped_components'], info['components'],
                                                                           info['dropped_faces'], entry['dropped']['vertices']))
+            if simplifying:
+                si = entry['simplify']
+                print('%s: simplified %d -> %d faces in %d rounds (%s), largest error %.3g' % (
+                    name, kept, si['faces_after'], si['rounds'], si['stopped'], si['max_error']))
         res[name] = entry
     out = {'files': res, 'connectivity': args.connectivity, 'largest': args.largest, 'min_area_frac': args.min_area_frac,
            'min_faces': args.min_faces, 'report_only': args.report_only}
+    if simplifying:                                        # (without these flags topology.json is what it always was)
+        out.update({'simplify_faces': args.simplify_faces, 'simplify_ratio': args.simplify_ratio,
+                    'simplify_max_error': args.simplify_max_error})
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         with open(osp.join(args.out, 'topology.json'), 'w') as fh:

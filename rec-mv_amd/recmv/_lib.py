@@ -211,6 +211,9 @@ def _declare(lib):
         "recmv_segment_sums_chunk": (i64, []),
         "recmv_segment_sums_workspace_bytes": (i64, [i64, i64, i32]),
         "recmv_segment_sums": (C.c_int, [vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i64, vp]),
+        "recmv_vertex_quadrics": (C.c_int, [vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, C.c_double, vp, vp, vp]),
+        "recmv_edge_collapse_cost": (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_double, vp, vp, vp, vp, vp]),
+        "recmv_collapse_flip_check": (C.c_int, [vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)       # AttributeError if the symbol is missing: fail loudly

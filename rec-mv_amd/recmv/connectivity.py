@@ -4,6 +4,7 @@ metrics.MeshGrid and topology.graph_components.  Plain torch on the faces' devic
   edges_packed        pytorch3d `Meshes.edges_packed` (unique undirected edges, sorted) and `faces_packed_to_edges_packed`
   incident_edges_csr / neighbours_csr   the per-vertex lists the NR-ICP and Laplacian kernels gather over
   EdgeTable           the one place that classifies edges: face count, border, non-manifold, border vertices, direction
+  vertex_slots_csr / boundary_edges_csr   vertex -> its faces and vertex -> its border edges, what the quadric kernel gathers over
   boundary_loops      closed walks over the border edges (on the host)
   compact             drop the vertices no face uses and renumber
 """
@@ -78,6 +79,35 @@ class EdgeTable:
     @property
     def forward(self):
         return self.faces[:, [1, 2, 0]] < self.faces[:, [2, 0, 1]]
+
+
+def vertex_slots_csr(faces, V):
+    """Vertex -> the corner slots (face * 3 + corner) that hold it, ascending: (offsets int64 [V+1], slots int64 [3F]).  A valid
+    face holds a vertex once, so slots // 3 are the vertex's faces, ascending."""
+    F = faces.shape[0]
+    fv = faces.reshape(-1)
+    o = torch.argsort(fv * (3 * F) + torch.arange(3 * F, device=faces.device))
+    cnt = torch.bincount(fv, minlength=V)
+    off = torch.zeros(V + 1, dtype=torch.int64, device=faces.device)
+    off[1:] = torch.cumsum(cnt, 0)
+    return off, o
+
+
+def boundary_edges_csr(table):
+    """The border of an EdgeTable as the quadric kernel reads it: (border [B,3] int64 = (v0, v1, the one face that uses the edge),
+    in edge order; offsets int64 [V+1], rows int64 [2B]: vertex -> its rows of border, ascending)."""
+    dev, V, F = table.faces.device, table.V, table.F
+    be = table.boundary_edge.nonzero().squeeze(1)
+    face_of = torch.zeros(table.E, dtype=torch.int64, device=dev)
+    face_of.scatter_(0, table.face_to_edge.reshape(-1), torch.arange(3 * F, device=dev) // 3)   # one writer per border edge
+    border = torch.cat([table.edges[be], face_of[be, None]], 1).contiguous()
+    B = border.shape[0]
+    rid = torch.arange(B, device=dev)
+    rows, cols = torch.cat([border[:, 0], border[:, 1]]), torch.cat([rid, rid])
+    order = torch.argsort(rows * max(B, 1) + cols)
+    off = torch.zeros(V + 1, dtype=torch.int64, device=dev)
+    off[1:] = torch.cumsum(torch.bincount(rows, minlength=V), 0)
+    return border, off, cols[order].contiguous()
 
 
 def boundary_loops(faces, V=None):

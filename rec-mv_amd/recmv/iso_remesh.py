@@ -18,7 +18,7 @@ import torch
 
 from . import _lib as L
 from . import nricp
-from .connectivity import EdgeTable, compact, neighbours_csr
+from .connectivity import EdgeTable, compact, neighbours_csr, vertex_slots_csr
 
 MAX_PASSES = 16                    # split passes, collapse rounds and flip rounds per iteration
 
@@ -183,12 +183,7 @@ class _Topo(EdgeTable):
         ones = torch.ones(2 * E, dtype=torch.int64, device=dev)
         self.valence = torch.zeros(V, dtype=torch.int64, device=dev).index_add(0, self.edges.reshape(-1), ones)
         self.nbr = neighbours_csr(self.edges, V)
-        fv = faces.reshape(-1)
-        o = torch.argsort(fv * (3 * F) + slots)
-        cnt = torch.bincount(fv, minlength=V)
-        off = torch.zeros(V + 1, dtype=torch.int64, device=dev)
-        off[1:] = torch.cumsum(cnt, 0)
-        self.vf = (off, o)                                                    # vertex -> face slots, ascending
+        self.vf = vertex_slots_csr(faces, V)                                  # vertex -> face slots, ascending
 
     def edge_key(self, u, w):
         lo, hi = torch.minimum(u, w), torch.maximum(u, w)
@@ -334,6 +329,61 @@ def _ring_min(key, nbr_off, nbr_idx):
     return out
 
 
+def _link_ok(topo, ca, cb, bnd):
+    """Link condition of the edges (ca, cb) (bnd: boundary edges): the common neighbours are exactly the opposite vertices."""
+    off, idx = topo.nbr
+    w_of, pos = _csr_rows(off, ca)
+    w = idx[pos].to(torch.int64)
+    common = torch.bincount(w_of[topo.has_edge(cb[w_of], w) & (w != cb[w_of])], minlength=ca.shape[0])
+    return common == torch.where(bnd, 1, 2)
+
+
+def _flip_ok(verts, faces, topo, ca, cb, p):
+    """No face that survives the collapse of (ca, cb) to p flips or degenerates (in the dtype of verts and p)."""
+    K = ca.shape[0]
+    ok = torch.ones(K, dtype=torch.bool, device=faces.device)
+    for ends in (ca, cb):
+        s_of, pos = _csr_rows(topo.vf[0], ends)
+        sl = topo.vf[1][pos]
+        f = sl // 3
+        tri = faces[f]
+        gone = ((tri == ca[s_of, None]) | (tri == cb[s_of, None])).sum(1) == 2
+        moved = tri == ends[s_of, None]
+        tv = verts[tri]
+        nv = torch.where(moved[..., None], p[s_of, None, :], tv)
+        n_old = torch.cross(tv[:, 1] - tv[:, 0], tv[:, 2] - tv[:, 0], dim=1)
+        n_new = torch.cross(nv[:, 1] - nv[:, 0], nv[:, 2] - nv[:, 0], dim=1)
+        bad = ~gone & ((n_old * n_new).sum(1) <= 0)
+        ok &= torch.bincount(s_of[bad], minlength=K) == 0
+    return ok
+
+
+def _independent(topo, ca, cb, key):
+    """bool over the edges (ca, cb): an independent set by priority (key ascending, then position): no two chosen edges within
+    two rings of each other."""
+    dev = ca.device
+    off, idx = topo.nbr
+    order = torch.sort(key, stable=True)[1]
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(order.shape[0], device=dev)
+    big = order.shape[0]
+    m = torch.full((topo.V,), big, dtype=torch.int64, device=dev)
+    m = m.scatter_reduce(0, torch.cat([ca, cb]), torch.cat([rank, rank]), reduce="amin")
+    m = _ring_min(_ring_min(m, off, idx), off, idx)
+    return (m[ca] == rank) & (m[cb] == rank)
+
+
+def _merge(verts, faces, ca, cb, p):
+    """Move the vertices ca to p, replace cb by ca in the faces and drop the faces that lose a corner."""
+    verts = verts.clone()
+    verts[ca] = p
+    remap = torch.arange(verts.shape[0], device=faces.device)
+    remap[cb] = ca
+    faces = remap[faces]
+    faces = faces[(faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 2] != faces[:, 0])]
+    return verts, faces
+
+
 def _collapse(verts, faces, lo, hi, cos_feature, max_dist, surf):
     """Collapse edges shorter than `lo` in rounds of independent sets (at most MAX_PASSES)."""
     collapses = 0
@@ -359,12 +409,8 @@ def _collapse(verts, faces, lo, hi, cos_feature, max_dist, surf):
         p = torch.where(bnd[:, None], verts[ca], p)                          # boundary edge: the lower-index endpoint
         K = ci.shape[0]
         ok = torch.ones(K, dtype=torch.bool, device=dev)
-        # link condition: the common neighbours are exactly the opposite vertices
         off, idx = topo.nbr
-        w_of, pos = _csr_rows(off, ca)
-        w = idx[pos].to(torch.int64)
-        common = torch.bincount(w_of[topo.has_edge(cb[w_of], w) & (w != cb[w_of])], minlength=K)
-        ok &= common == torch.where(bnd, 1, 2)
+        ok &= _link_ok(topo, ca, cb, bnd)
         # a boundary loop keeps at least 3 edges
         ok &= ~bnd | (_boundary_loop_length(faces, topo)[ci] > 3)
         # no new edge longer than hi
@@ -373,20 +419,7 @@ def _collapse(verts, faces, lo, hi, cos_feature, max_dist, surf):
             w = idx[pos].to(torch.int64)
             far = ((p[w_of] - verts[w]).norm(dim=1) > hi) & (w != ca[w_of]) & (w != cb[w_of])
             ok &= torch.bincount(w_of[far], minlength=K) == 0
-        # no surviving face flips or degenerates
-        for ends in (ca, cb):
-            s_of, pos = _csr_rows(topo.vf[0], ends)
-            sl = topo.vf[1][pos]
-            f = sl // 3
-            tri = faces[f]
-            gone = ((tri == ca[s_of, None]) | (tri == cb[s_of, None])).sum(1) == 2
-            moved = tri == ends[s_of, None]
-            tv = verts[tri]
-            nv = torch.where(moved[..., None], p[s_of, None, :], tv)
-            n_old = torch.cross(tv[:, 1] - tv[:, 0], tv[:, 2] - tv[:, 0], dim=1)
-            n_new = torch.cross(nv[:, 1] - nv[:, 0], nv[:, 2] - nv[:, 0], dim=1)
-            bad = ~gone & ((n_old * n_new).sum(1) <= 0)
-            ok &= torch.bincount(s_of[bad], minlength=K) == 0
+        ok &= _flip_ok(verts, faces, topo, ca, cb, p)
         # no vertex farther than max_dist from the reference surface (only a midpoint is new)
         newp = ~bnd & (fa == fb)
         if bool(newp.any()):
@@ -398,22 +431,10 @@ def _collapse(verts, faces, lo, hi, cos_feature, max_dist, surf):
         if ci.numel() == 0:
             break
         # independent set: priority by (length, edge id); no two chosen edges within two rings of each other
-        order = torch.sort(elen_c, stable=True)[1]
-        rank = torch.empty_like(order)
-        rank[order] = torch.arange(order.shape[0], device=dev)
-        big = order.shape[0]
-        m = torch.full((V,), big, dtype=torch.int64, device=dev)
-        m = m.scatter_reduce(0, torch.cat([ca, cb]), torch.cat([rank, rank]), reduce="amin")
-        m = _ring_min(_ring_min(m, off, idx), off, idx)
-        pick = (m[ca] == rank) & (m[cb] == rank)
+        pick = _independent(topo, ca, cb, elen_c)
         ca, cb, p = ca[pick], cb[pick], p[pick]
         collapses += int(ca.shape[0])
-        verts = verts.clone()
-        verts[ca] = p
-        remap = torch.arange(V, device=dev)
-        remap[cb] = ca
-        faces = remap[faces]
-        faces = faces[(faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 2] != faces[:, 0])]
+        verts, faces = _merge(verts, faces, ca, cb, p)
         verts, faces, _ = compact(verts, faces)
     return verts, faces, collapses
 
