@@ -524,6 +524,10 @@ int recmv_alpha_composite_backward(const int32_t* idx, const float* alphas, cons
  *   recmv_rootfind_update: unfinished &= !(|f| < dthreshold && angle < athreshold); on unfinished rays (and
  *                         do_update != 0) p -= E grad / |grad|^2 with E = w1|f| + w2 loss2,
  *                         grad = w1 sign(f) gf + w2 gd; *counter += number of unfinished rays.
+ * B (frames) is 1..128.  The entry points that take A stage its rows 0..2 in dynamic LDS, B * 24 * 12 * 4 bytes: 147 456 bytes
+ * at B = 128.  What one launch may ask for is a property of the device, not a constant of the HIP headers
+ * (hipDeviceAttributeMaxSharedMemoryPerBlock, hip_runtime_api.h); gfx950 reports 163 840 bytes (the CU's 160 KiB) for it and for
+ * hipDeviceAttributeSharedMemPerBlockOptin, so B = 128 fits and is an ordinary case of tests/test_gpu_skinning.py.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct recmv_lbs_grid {
   const float* volume;
