@@ -36,7 +36,8 @@ extern "C" {
  *        (recmv_mesh_grid_count / _fill, recmv_closest_point_grid, recmv_mesh_intersect_grid_count / _fill,
  *        recmv_segment_mesh_grid).  Added since without a bump: recmv_icp_accumulate and its workspace size;
  *        recmv_graph_components, recmv_mesh_face_stats, recmv_segment_sums with its chunk and workspace sizes;
- *        recmv_vertex_quadrics, recmv_edge_collapse_cost, recmv_collapse_flip_check.
+ *        recmv_vertex_quadrics, recmv_edge_collapse_cost, recmv_collapse_flip_check; recmv_cotan_weights,
+ *        recmv_laplacian_step, recmv_face_normal_filter, recmv_vertex_from_normals (mesh smoothing: pure additions, still v11).
  *   v10: recmv_verts_normals, recmv_hard_phong_shade, recmv_hard_phong_params_floats added.  Added since without a bump (no
  *        existing signature changed, and _lib.py rejects a library that lacks them): recmv_knn1, recmv_nricp_energy,
  *        recmv_lap_align_solve, recmv_lap_smooth, recmv_closest_point, recmv_iso_relax, recmv_loop_subdivide,
@@ -957,6 +958,46 @@ int recmv_edge_collapse_cost(const double* Q, const float* verts, int64_t V, con
 int recmv_collapse_flip_check(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* vf_offsets,
                               const int64_t* vf_faces, int64_t n_vf, const int64_t* edges, int64_t E, const float* pos,
                               uint8_t* ok, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Mesh smoothing (csrc/mesh_smooth.hip; added to ABI v11, no existing signature changed).  Not in the reference.  The kernels
+ * of recmv/smooth.py.  verts [V,3] f32, faces [F,3] int64.  Sums in float64, one thread per output row in table order, one
+ * rounding to f32 at the store, no float atomics: the same bits on every run.  Input and output are different buffers.
+ * Argument errors (negative sizes, sizes of 2^31 or more, a parameter that is not finite or out of range, NULL pointers with
+ * work to do) are found before any HIP call; an empty input is a no-op that returns RECMV_OK.  Every index read from a table
+ * is checked against its array and row ranges are clamped.
+ * Tables: nbr_offsets [V + 1] / nbr_idx [nnz] int32: vertex -> neighbour vertices, ascending; vs_offsets [V + 1] / vs_slots [n_vs]
+ *   int64: vertex -> the corner slots (face * 3 + corner) that hold it, ascending; ff_offsets [F + 1] / ff_idx [nnz] int32: face
+ *   -> the faces that share an edge with it, ascending, without the face itself.
+ * recmv_cotan_weights: weights [nnz] float64, one per neighbour entry: w[i->j] = the sum over the faces of edge (i, j), ascending,
+ *   of 1/2 max(0, cot) of the angle opposite the edge; cot at a corner = dot(e1, e2) / |cross(e1, e2)| of the edges to the next
+ *   and the previous corner in the face's cyclic order, float64.  w[i->j] and w[j->i] have the same bits.  A face with an
+ *   index outside [0, V), a repeated corner, a corner that is not finite or no area adds nothing; counts [1] int32 on the
+ *   device counts those faces.
+ * recmv_laplacian_step: out = x + lambda (sum_j w_ij x_j / sum_j w_ij - x).  weights NULL: the mean of the valid neighbours;
+ *   otherwise entries that are not finite and > 0 are left out.  fixed [V] uint8 (NULL: none): copied.  No valid neighbour, or
+ *   a weight sum that is not > 0: copied.  boundary_nbrs [V,2] int64 (NULL: none; -1 = none, as recmv_loop_subdivide reads
+ *   it): a vertex with an entry >= 0 moves toward the midpoint of its two boundary neighbours, or is copied when it does not
+ *   have two valid ones.  lambda must be finite and may be negative.
+ * recmv_face_normal_filter: out [F,3] f32 = the unit vector of sum_j areas[j] exp(-|c_i - c_j|^2 / 2 sigma_c^2)
+ *   exp(-|n_i - n_j|^2 / 2 sigma_s^2) n_j over the face itself, then its neighbours in row order; normals [F,3] f32, areas [F] and
+ *   centroids [F,3] float64.  A face whose sum has no finite positive length keeps its normal.  sigma_c, sigma_s finite, > 0.
+ * recmv_vertex_from_normals: out_i = x_i + 1/|F_i| sum_f n_f (n_f . (c_f - x_i)) over the valid faces of the vertex's slots, c_f
+ *   the centroid of the face in verts; a face with a corner or normal that is not finite, or a zero normal, is left out.  A
+ *   fixed vertex (NULL: none) and one without such a face are copied.
+ * ---------------------------------------------------------------------------------------------- */
+int recmv_cotan_weights(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* vs_offsets,
+                        const int64_t* vs_slots, int64_t n_vs, const int32_t* nbr_offsets, const int32_t* nbr_idx, int64_t nnz,
+                        double* weights, int32_t* counts, void* stream);
+int recmv_laplacian_step(const int32_t* nbr_offsets, const int32_t* nbr_idx, int64_t V, int64_t nnz, const float* verts,
+                         const double* weights, const uint8_t* fixed, const int64_t* boundary_nbrs, double lambda, float* out,
+                         void* stream);
+int recmv_face_normal_filter(const int32_t* ff_offsets, const int32_t* ff_idx, int64_t F, int64_t nnz, const float* normals,
+                             const double* areas, const double* centroids, double sigma_c, double sigma_s, float* out,
+                             void* stream);
+int recmv_vertex_from_normals(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* vs_offsets,
+                              const int64_t* vs_slots, int64_t n_vs, const float* normals, const uint8_t* fixed, float* out,
+                              void* stream);
 
 #ifdef __cplusplus
 }

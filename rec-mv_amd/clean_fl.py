@@ -9,13 +9,20 @@ that no kept face uses always go; `--connectivity edge` joins faces only across 
 `--out` under its own name.  `--simplify-faces N` or `--simplify-ratio R` and / or `--simplify-max-error E` then thin what is left
 (recmv.simplify.simplify: quadric-error edge collapse down to N faces, or to the share R of the cleaned mesh's faces, never
 moving the surface by more than E in the root-mean-square sense of the quadrics) before it is described and written; the mesh
-must be edge-manifold by then.  `--out`/topology.json holds per file the report `before`, the report `after` and what was
-`dropped`, and with a simplify flag `simplify`: that call's info.  With `--report-only` nothing is cleaned or written but
+must be edge-manifold by then.  `--smooth taubin|laplacian|bilateral` smooths what is left BEFORE it is simplified, so that the
+quadrics see the de-noised planes (recmv.smooth.smooth; `--smooth-iters`, `--smooth-lambda`, `--smooth-mu`, `--smooth-weights
+uniform|cotangent` for the first two, `--smooth-normal-iters`, `--smooth-vertex-iters`, `--smooth-sigma-s` for bilateral;
+`--smooth-boundary fixed|curve|free`: open boundaries stay where they are by default).  `--out`/topology.json holds per file
+the report `before`, the report `after` and what was `dropped`, with a simplify flag `simplify`: that call's info, and with
+`--smooth` `smooth`: that call's info, beside the smooth parameters at the top level.  With `--report-only` nothing is cleaned or written but
 topology.json (with `before` alone; printed when there is no `--out`): on a registered run it is the check that `registry_<garment>.obj` is one piece with the expected number of boundary
 loops — an upper garment with four feature lines has four.
 
     python rec-mv_amd/clean_fl.py --gpu-ids 0 --in <obj|dir> --out <dir> [--largest N] [--min-area-frac X] [--min-faces N]
         [--connectivity vertex|edge] [--simplify-faces N | --simplify-ratio R] [--simplify-max-error E] [--report-only]
+        [--smooth taubin|laplacian|bilateral] [--smooth-iters N] [--smooth-lambda L] [--smooth-mu M]
+        [--smooth-weights uniform|cotangent] [--smooth-boundary fixed|curve|free] [--smooth-normal-iters N]
+        [--smooth-vertex-iters N] [--smooth-sigma-s S]
 """
 import argparse
 import json
@@ -42,6 +49,17 @@ def build_parser():
                         help='after cleaning, simplify every mesh to this share of its faces')
     parser.add_argument('--simplify-max-error', default=None, type=float,
                         help='no collapse whose quadric error (a length) is above this; alone: collapse until none is left')
+    parser.add_argument('--smooth', default=None, choices=['taubin', 'laplacian', 'bilateral'],
+                        help='after cleaning and before simplifying, smooth every mesh with this method')
+    parser.add_argument('--smooth-iters', default=10, type=int, help='taubin / laplacian iterations')
+    parser.add_argument('--smooth-lambda', default=0.5, type=float, help='the step, in (0, 1]')
+    parser.add_argument('--smooth-mu', default=None, type=float, help='taubin\'s second step, < 0 (default: pass-band 0.1)')
+    parser.add_argument('--smooth-weights', default='uniform', choices=['uniform', 'cotangent'], help='the neighbours\' weights')
+    parser.add_argument('--smooth-boundary', default='fixed', choices=['fixed', 'curve', 'free'],
+                        help='boundary vertices stay, move along their curve, or move like the interior')
+    parser.add_argument('--smooth-normal-iters', default=5, type=int, help='bilateral: iterations of the normal filter')
+    parser.add_argument('--smooth-vertex-iters', default=10, type=int, help='bilateral: iterations of the vertex update')
+    parser.add_argument('--smooth-sigma-s', default=0.35, type=float, help='bilateral: the normal difference that still counts')
     parser.add_argument('--report-only', action='store_true', help='describe the meshes, clean and write none')
     return parser
 
@@ -75,6 +93,17 @@ def main(argv=None):
     simplifying = not (args.simplify_faces is None and args.simplify_ratio is None and args.simplify_max_error is None)
     if simplifying and args.report_only:
         parser.error("--report-only writes no mesh: the simplify flags need --out")
+    if args.smooth is not None:
+        if args.report_only:
+            parser.error("--report-only writes no mesh: --smooth needs --out")
+        if args.smooth_iters < 0 or args.smooth_normal_iters < 0 or args.smooth_vertex_iters < 0:
+            parser.error("the --smooth-*-iters must not be negative")
+        if not (0. < args.smooth_lambda <= 1.):
+            parser.error("--smooth-lambda must be in (0, 1]")
+        if args.smooth_mu is not None and not (-float('inf') < args.smooth_mu < 0.):
+            parser.error("--smooth-mu must be finite and below 0")
+        if not (0. < args.smooth_sigma_s < float('inf')):
+            parser.error("--smooth-sigma-s must be finite and above 0")
     if not args.report_only and not args.out:
         parser.error("--out is needed unless --report-only is given")
     try:
@@ -100,6 +129,15 @@ def main(argv=None):
         if not args.report_only:
             kv, kf, info = topology.keep_components(v, f, largest=args.largest, min_area_frac=args.min_area_frac,
                                                     min_faces=args.min_faces, connectivity=args.connectivity)
+            if args.smooth is not None:                    # before the quadrics are built: they then see the de-noised planes
+                from recmv import smooth
+                kv, entry['smooth'] = smooth.smooth(kv, kf, method=args.smooth, iterations=args.smooth_iters, lam=args.smooth_lambda,
+                                                    mu=args.smooth_mu, weights=args.smooth_weights, boundary=args.smooth_boundary,
+                                                    normal_iterations=args.smooth_normal_iters,
+                                                    vertex_iterations=args.smooth_vertex_iters, sigma_s=args.smooth_sigma_s)
+                si = entry['smooth']
+                print('%s: smoothed (%s), %d vertices moved by at most %.3g, roughness %.4f -> %.4f' % (
+                    name, args.smooth, si['moved'], si['displacement_max'], si['roughness_before'], si['roughness_after']))
             if simplifying:
                 from recmv import simplify
                 kept = int(kf.shape[0])
@@ -123,6 +161,11 @@ def main(argv=None):
     if simplifying:                                        # (without these flags topology.json is what it always was)
         out.update({'simplify_faces': args.simplify_faces, 'simplify_ratio': args.simplify_ratio,
                     'simplify_max_error': args.simplify_max_error})
+    if args.smooth is not None:                            # (likewise)
+        out.update({'smooth': args.smooth, 'smooth_iters': args.smooth_iters, 'smooth_lambda': args.smooth_lambda,
+                    'smooth_mu': args.smooth_mu, 'smooth_weights': args.smooth_weights, 'smooth_boundary': args.smooth_boundary,
+                    'smooth_normal_iters': args.smooth_normal_iters, 'smooth_vertex_iters': args.smooth_vertex_iters,
+                    'smooth_sigma_s': args.smooth_sigma_s})
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         with open(osp.join(args.out, 'topology.json'), 'w') as fh:

@@ -214,6 +214,10 @@ def _declare(lib):
         "recmv_vertex_quadrics": (C.c_int, [vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, C.c_double, vp, vp, vp]),
         "recmv_edge_collapse_cost": (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_double, vp, vp, vp, vp, vp]),
         "recmv_collapse_flip_check": (C.c_int, [vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, vp, vp]),
+        "recmv_cotan_weights": (C.c_int, [vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp]),
+        "recmv_laplacian_step": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp, C.c_double, vp, vp]),
+        "recmv_face_normal_filter": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, C.c_double, C.c_double, vp, vp]),
+        "recmv_vertex_from_normals": (C.c_int, [vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)       # AttributeError if the symbol is missing: fail loudly

@@ -5,6 +5,8 @@ metrics.MeshGrid and topology.graph_components.  Plain torch on the faces' devic
   incident_edges_csr / neighbours_csr   the per-vertex lists the NR-ICP and Laplacian kernels gather over
   EdgeTable           the one place that classifies edges: face count, border, non-manifold, border vertices, direction
   vertex_slots_csr / boundary_edges_csr   vertex -> its faces and vertex -> its border edges, what the quadric kernel gathers over
+  face_neighbours_csr / boundary_neighbours   face -> the faces across its edges and vertex -> its two boundary neighbours, what the
+                      smoothing kernels gather over
   boundary_loops      closed walks over the border edges (on the host)
   compact             drop the vertices no face uses and renumber
 """
@@ -108,6 +110,53 @@ def boundary_edges_csr(table):
     off = torch.zeros(V + 1, dtype=torch.int64, device=dev)
     off[1:] = torch.cumsum(torch.bincount(rows, minlength=V), 0)
     return border, off, cols[order].contiguous()
+
+
+def face_neighbours_csr(table):
+    """Face -> the faces that share an edge with it, ascending and without the face itself, of an EdgeTable: (offsets int32
+    [F+1], faces int32).  At a non-manifold edge those are all of the edge's other faces; a face met across two edges is
+    listed once."""
+    dev, F, E = table.faces.device, table.F, table.E
+    fe = table.face_to_edge.reshape(-1)                                            # [3F], slot -> edge
+    face = torch.arange(3 * F, device=dev) // 3
+    order = torch.argsort(fe * max(F, 1) + face)                                   # slots by (edge, face)
+    start = torch.zeros(E + 1, dtype=torch.int64, device=dev)
+    start[1:] = torch.cumsum(table.count, 0)
+    D = int(table.count.max()) if E else 0
+    rows, cols = [], []
+    for k in range(D):                                                             # the k-th face of every slot's edge
+        has = table.count[fe] > k
+        rows.append(face[has])
+        cols.append(face[order[(start[fe[has]] + k)]])
+    rows = torch.cat(rows) if rows else face[:0]
+    cols = torch.cat(cols) if cols else face[:0]
+    key = torch.unique((rows * max(F, 1) + cols)[rows != cols])                    # sorted by (row, col), repeats gone
+    rows, cols = key // max(F, 1), key % max(F, 1)
+    off = torch.zeros(F + 1, dtype=torch.int64, device=dev)
+    off[1:] = torch.cumsum(torch.bincount(rows, minlength=F), 0)
+    return off.to(torch.int32).contiguous(), cols.to(torch.int32).contiguous()
+
+
+def boundary_neighbours(table):
+    """[V,2] int64 of an EdgeTable, the layout recmv_loop_subdivide and recmv_laplacian_step read: the two boundary neighbours
+    of a vertex with exactly two boundary edges, ascending; (-1, -1) for an interior vertex; (lowest neighbour, -1) for a
+    boundary vertex with any other number of boundary edges (where loops touch), which the readers then leave where it is."""
+    dev, V = table.faces.device, table.V
+    be = table.edges[table.boundary_edge]
+    rows = torch.cat([be[:, 0], be[:, 1]])
+    cols = torch.cat([be[:, 1], be[:, 0]])
+    o = torch.argsort(rows * max(V, 1) + cols)
+    rows, cols = rows[o], cols[o]
+    degree = torch.bincount(rows, minlength=V)
+    first = torch.ones_like(rows, dtype=torch.bool)
+    first[1:] = rows[1:] != rows[:-1]
+    bn = torch.full((V, 2), -1, dtype=torch.int64, device=dev)
+    bn[rows[first], 0] = cols[first]
+    second = torch.zeros_like(first)
+    second[1:] = first[:-1] & ~first[1:]
+    second &= degree[rows] == 2
+    bn[rows[second], 1] = cols[second]
+    return bn.contiguous()
 
 
 def boundary_loops(faces, V=None):
