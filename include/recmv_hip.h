@@ -37,7 +37,9 @@ extern "C" {
  *        recmv_segment_mesh_grid).  Added since without a bump: recmv_icp_accumulate and its workspace size;
  *        recmv_graph_components, recmv_mesh_face_stats, recmv_segment_sums with its chunk and workspace sizes;
  *        recmv_vertex_quadrics, recmv_edge_collapse_cost, recmv_collapse_flip_check; recmv_cotan_weights,
- *        recmv_laplacian_step, recmv_face_normal_filter, recmv_vertex_from_normals (mesh smoothing: pure additions, still v11).
+ *        recmv_laplacian_step, recmv_face_normal_filter, recmv_vertex_from_normals (mesh smoothing: pure additions, still v11);
+ *        recmv_points_within_cells, recmv_points_within_count, recmv_points_within_fill, recmv_points_within_max_cells (the
+ *        point-pair search of mesh repair: pure additions, still v11).
  *   v10: recmv_verts_normals, recmv_hard_phong_shade, recmv_hard_phong_params_floats added.  Added since without a bump (no
  *        existing signature changed, and _lib.py rejects a library that lacks them): recmv_knn1, recmv_nricp_energy,
  *        recmv_lap_align_solve, recmv_lap_smooth, recmv_closest_point, recmv_iso_relax, recmv_loop_subdivide,
@@ -998,6 +1000,35 @@ int recmv_face_normal_filter(const int32_t* ff_offsets, const int32_t* ff_idx, i
 int recmv_vertex_from_normals(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* vs_offsets,
                               const int64_t* vs_slots, int64_t n_vs, const float* normals, const uint8_t* fixed, float* out,
                               void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Fixed-radius neighbour search over points (csrc/point_grid.hip; added to ABI v11, no existing signature changed).  Not in
+ * the reference.  The kernels of recmv/repair.py (points_within, which weld joins).  verts [V,3] f32, eps >= 0 a float64.  The
+ * result is every pair (i, j), i < j, of FINITE vertices with d2 <= eps * eps, d2 = (dx * dx + dy * dy) + dz * dz in float64 from
+ * the f32 coordinates, no contraction: membership is exact and equals an O(V^2) loop's.  eps = 0: coincident vertices
+ * (+0.0 == -0.0).  No atomics at all: the same array on every run.
+ * The grid (chosen by the caller): nx x ny x nz cubic cells of edge `cell` with the corner at (ox, oy, oz), cell (x, y, z) has
+ * index (z ny + y) nx + x; cell >= eps (the caller keeps cell >= eps (1 + 2^-20), which makes the 27-cell search complete under
+ * float64 rounding), every axis 1 .. 2^20 cells, at most recmv_points_within_max_cells() = 2^24 in all; a coordinate outside is
+ * clamped to the edge.
+ * recmv_points_within_cells: cell_of [V] int32 = the cell of every vertex, -1 for a vertex with a NaN or inf coordinate.
+ * The caller sorts the finite vertices by cell, by id inside a cell: pts [n,3] f32 their coordinates, ids [n] int64 their
+ *   vertex ids, cell_start [cells + 1] int32 the first sorted position of every cell (cell_start[cells] = n).
+ * recmv_points_within_count: counts [V] int64 = per vertex i the partners j > i (0 for a vertex that is not sorted).
+ * recmv_points_within_fill: offsets [V] int64 = the exclusive scan of counts; pairs [P,2] int64 receives the rows (i, j) of
+ *   vertex i from row offsets[i] on; a row outside [0, P) is not written.
+ * Argument errors (negative sizes, n > V, eps or cell not finite, cell < eps, cells out of range, NULL pointers with work to do)
+ * are found before any HIP call.  Values read from ids, cell_start and offsets are checked before they index anything.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t recmv_points_within_max_cells(void);
+int recmv_points_within_cells(const float* verts, int64_t V, double ox, double oy, double oz, double cell, int32_t nx, int32_t ny,
+                              int32_t nz, int32_t* cell_of, void* stream);
+int recmv_points_within_count(const float* pts, const int64_t* ids, int64_t n, int64_t V, double eps, double ox, double oy,
+                              double oz, double cell, int32_t nx, int32_t ny, int32_t nz, const int32_t* cell_start,
+                              int64_t* counts, void* stream);
+int recmv_points_within_fill(const float* pts, const int64_t* ids, int64_t n, int64_t V, double eps, double ox, double oy,
+                             double oz, double cell, int32_t nx, int32_t ny, int32_t nz, const int32_t* cell_start,
+                             const int64_t* offsets, int64_t* pairs, int64_t P, void* stream);
 
 #ifdef __cplusplus
 }

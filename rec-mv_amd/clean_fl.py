@@ -12,7 +12,12 @@ moving the surface by more than E in the root-mean-square sense of the quadrics)
 must be edge-manifold by then.  `--smooth taubin|laplacian|bilateral` smooths what is left BEFORE it is simplified, so that the
 quadrics see the de-noised planes (recmv.smooth.smooth; `--smooth-iters`, `--smooth-lambda`, `--smooth-mu`, `--smooth-weights
 uniform|cotangent` for the first two, `--smooth-normal-iters`, `--smooth-vertex-iters`, `--smooth-sigma-s` for bilateral;
-`--smooth-boundary fixed|curve|free`: open boundaries stay where they are by default).  `--out`/topology.json holds per file
+`--smooth-boundary fixed|curve|free`: open boundaries stay where they are by default).  `--repair` mends every mesh FIRST OF ALL,
+before any of the above (recmv.repair.repair: degenerate and duplicate faces dropped, every edge with more than two faces and every
+pinch vertex taken apart, every orientable piece consistently oriented, unused vertices dropped); `--weld-eps E` (a length; it
+implies `--repair`) first welds the vertices within E of each other, 0 the coincident ones — without it nothing is welded.  That
+is the way to an edge-manifold mesh; topology.json then holds `repair` per file, the numbers of that call's info.
+`--out`/topology.json holds per file
 the report `before`, the report `after` and what was `dropped`, with a simplify flag `simplify`: that call's info, and with
 `--smooth` `smooth`: that call's info, beside the smooth parameters at the top level.  With `--report-only` nothing is cleaned or written but
 topology.json (with `before` alone; printed when there is no `--out`): on a registered run it is the check that `registry_<garment>.obj` is one piece with the expected number of boundary
@@ -22,7 +27,7 @@ loops — an upper garment with four feature lines has four.
         [--connectivity vertex|edge] [--simplify-faces N | --simplify-ratio R] [--simplify-max-error E] [--report-only]
         [--smooth taubin|laplacian|bilateral] [--smooth-iters N] [--smooth-lambda L] [--smooth-mu M]
         [--smooth-weights uniform|cotangent] [--smooth-boundary fixed|curve|free] [--smooth-normal-iters N]
-        [--smooth-vertex-iters N] [--smooth-sigma-s S]
+        [--smooth-vertex-iters N] [--smooth-sigma-s S] [--repair] [--weld-eps E]
 """
 import argparse
 import json
@@ -60,6 +65,10 @@ def build_parser():
     parser.add_argument('--smooth-normal-iters', default=5, type=int, help='bilateral: iterations of the normal filter')
     parser.add_argument('--smooth-vertex-iters', default=10, type=int, help='bilateral: iterations of the vertex update')
     parser.add_argument('--smooth-sigma-s', default=0.35, type=float, help='bilateral: the normal difference that still counts')
+    parser.add_argument('--repair', action='store_true',
+                        help='first of all mend every mesh: drop degenerate faces, split non-manifold edges and vertices, orient')
+    parser.add_argument('--weld-eps', default=None, type=float,
+                        help='a length: weld the vertices within it of each other before the repair (implies --repair)')
     parser.add_argument('--report-only', action='store_true', help='describe the meshes, clean and write none')
     return parser
 
@@ -104,6 +113,11 @@ def main(argv=None):
             parser.error("--smooth-mu must be finite and below 0")
         if not (0. < args.smooth_sigma_s < float('inf')):
             parser.error("--smooth-sigma-s must be finite and above 0")
+    if args.weld_eps is not None and not (0. <= args.weld_eps < float('inf')):
+        parser.error("--weld-eps must be finite and not negative")
+    repairing = args.repair or args.weld_eps is not None
+    if repairing and args.report_only:
+        parser.error("--report-only writes no mesh: --repair and --weld-eps need --out")
     if not args.report_only and not args.out:
         parser.error("--out is needed unless --report-only is given")
     try:
@@ -126,6 +140,16 @@ def main(argv=None):
         print('%s: %d faces, %d pieces (%d by edges), %d boundary loops, euler characteristic %d, watertight %s' % (
             name, b['faces'], b['components_vertex'], b['components_edge'], b['boundary_loops'], b['euler_characteristic'],
             b['watertight']))
+        if repairing:                                      # first of all: every later stage sees the mended mesh
+            from recmv import repair
+            faces_before = int(f.shape[0])
+            v, f, ri = repair.repair(v, f, weld_eps=args.weld_eps)
+            entry['repair'] = ri = repair.info_json(ri)
+            print('%s: repaired, %d vertices welded, %d of %d faces dropped, %d vertices added at non-manifold places, %d faces '
+                  'flipped, %d pieces not orientable' % (
+                      name, ri['weld']['merged_vertices'] if 'weld' in ri else 0, faces_before - int(f.shape[0]), faces_before,
+                      ri['split_nonmanifold']['added_vertices'], ri['orient']['flipped_faces'],
+                      ri['orient']['non_orientable_pieces']))
         if not args.report_only:
             kv, kf, info = topology.keep_components(v, f, largest=args.largest, min_area_frac=args.min_area_frac,
                                                     min_faces=args.min_faces, connectivity=args.connectivity)
@@ -161,6 +185,8 @@ def main(argv=None):
     if simplifying:                                        # (without these flags topology.json is what it always was)
         out.update({'simplify_faces': args.simplify_faces, 'simplify_ratio': args.simplify_ratio,
                     'simplify_max_error': args.simplify_max_error})
+    if repairing:                                          # (likewise)
+        out.update({'repair': True, 'weld_eps': args.weld_eps})
     if args.smooth is not None:                            # (likewise)
         out.update({'smooth': args.smooth, 'smooth_iters': args.smooth_iters, 'smooth_lambda': args.smooth_lambda,
                     'smooth_mu': args.smooth_mu, 'smooth_weights': args.smooth_weights, 'smooth_boundary': args.smooth_boundary,

@@ -24,12 +24,17 @@ distance of one of them to its surface (`body_inside_vertices`, `body_max_depth`
 its largest piece's (recmv.topology.keep_components; one floater decides `accuracy_max` and drags the precision down) and
 records what went under `floaters` in the pair's entry; `--topology` adds `topology_pred` and `topology_gt`
 (recmv.topology.report: pieces, boundary loops, Euler characteristic, watertightness, triangle quality) to it.  `mean` is
-taken over the numeric entries.
+taken over the numeric entries.  `--repair` mends the prediction AND the ground truth before anything else (after `--scale`;
+recmv.repair.repair: degenerate and duplicate faces dropped, non-manifold edges and pinch vertices taken apart, orientable pieces
+oriented, unused vertices dropped), and `--weld-eps E` (a length, implies `--repair`) first welds the vertices within E of each
+other: a scan exported with one vertex triple per face reads as F pieces until it is welded, and `--topology` and
+`--drop-floaters` mean nothing for it.  The numbers of the two calls' info go into the pair's entry as `repair_pred` and
+`repair_gt`.
 
     python rec-mv_amd/eval_fl.py --gpu-ids 0 --pred <obj|dir> --gt <obj|dir> [--samples N] [--seed S] [--thresholds t ...]
         [--scale s] [--method auto|grid|brute] [--intersections [--body <obj|dir> [--penetration]]] [--out metrics.json]
         [--align none|rigid|similarity [--align-metric plane|point] [--align-trim f] [--align-iters n]
-         [--align-from each|first] [--align-out DIR]] [--drop-floaters FRAC] [--topology]
+         [--align-from each|first] [--align-out DIR]] [--drop-floaters FRAC] [--topology] [--repair] [--weld-eps E]
 """
 import argparse
 import json
@@ -69,6 +74,10 @@ def build_parser():
                         help='add the topology report of the prediction and of the ground truth to every pair')
     parser.add_argument('--drop-floaters', default=None, type=float, metavar='FRAC',
                         help='drop the pieces of the prediction with less than FRAC of its largest piece\'s area, before everything else')
+    parser.add_argument('--repair', action='store_true',
+                        help='mend the prediction and the ground truth before everything else (recmv.repair.repair)')
+    parser.add_argument('--weld-eps', default=None, type=float,
+                        help='a length: weld the vertices within it of each other before the repair (implies --repair)')
     return parser
 
 
@@ -121,6 +130,9 @@ def main(argv=None):
         parser.error("--align-iters must not be negative")
     if args.drop_floaters is not None and not (0. <= args.drop_floaters <= 1.):
         parser.error("--drop-floaters must be in [0, 1]")
+    if args.weld_eps is not None and not (0. <= args.weld_eps < float('inf')):
+        parser.error("--weld-eps must be finite and not negative")
+    repairing = args.repair or args.weld_eps is not None
     import torch
     from infer_fl_animation import temporal_smoothness
     from recmv import align, metrics, topology
@@ -128,11 +140,20 @@ def main(argv=None):
 
     device = torch.device('cuda:%d' % args.gpu_ids[0])
     thresholds = tuple(args.thresholds) if args.thresholds else metrics.DEFAULT_THRESHOLDS
-    per_pair, sequence, alignment, shared, floaters = {}, [], {}, None, {}
+    per_pair, sequence, alignment, shared, floaters, repaired = {}, [], {}, None, {}, {}
     for stem, pf, gf in pairs:
         pv, pfaces = read_obj(pf)
         gv, gfaces = read_obj(gf)
         pv = pv * args.scale
+        if repairing:
+            from recmv import repair
+            rv, rf, rp = repair.repair(pv.to(device), pfaces.to(device), weld_eps=args.weld_eps)
+            pv, pfaces = rv.cpu(), rf.cpu()
+            rv, rf, rg = repair.repair(gv.to(device), gfaces.to(device), weld_eps=args.weld_eps)
+            gv, gfaces = rv.cpu(), rf.cpu()
+            repaired[stem] = {'repair_pred': repair.info_json(rp), 'repair_gt': repair.info_json(rg)}
+            print('%s: repaired, prediction %d vertices and %d faces, ground truth %d vertices and %d faces' % (
+                stem, pv.shape[0], pfaces.shape[0], gv.shape[0], gfaces.shape[0]))
         if args.drop_floaters is not None:
             kv, kf, kept = topology.keep_components(pv.to(device), pfaces.to(device), min_area_frac=args.drop_floaters)
             floaters[stem] = {'min_area_frac': args.drop_floaters, 'components': kept['components'],
@@ -181,6 +202,8 @@ def main(argv=None):
                     per_pair[stem].update({'body_inside_vertices': pen['count'], 'body_max_depth': pen['max_depth']})
         if stem in floaters:
             per_pair[stem]['floaters'] = floaters[stem]
+        if stem in repaired:
+            per_pair[stem].update(repaired[stem])
         if args.topology:
             per_pair[stem]['topology_pred'] = topology.report(pv.to(device), pfaces.to(device))
             per_pair[stem]['topology_gt'] = topology.report(gv.to(device), gfaces.to(device))
@@ -191,6 +214,8 @@ def main(argv=None):
     mean = {k: sum(m[k] for m in per_pair.values()) / len(per_pair) for k in keys}
     res = {'pairs': per_pair, 'mean': mean, 'samples': args.samples, 'seed': args.seed, 'method': args.method,
            'thresholds': list(thresholds), 'scale': args.scale, 'unmatched_pred': only_pred, 'unmatched_gt': only_gt}
+    if repairing:                                          # (without these flags the output is what it always was)
+        res['repair'] = {'weld_eps': args.weld_eps}
     if args.align != 'none':                               # (not into pairs[stem]: `mean` sums every key there)
         res['align'] = {'mode': args.align, 'metric': args.align_metric, 'trim': args.align_trim, 'iters': args.align_iters,
                         'from': args.align_from}

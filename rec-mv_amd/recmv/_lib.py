@@ -74,7 +74,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
 
 
 def _declare(lib):
-    vp, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
+    vp, i64, i32, f32, f64 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double
     T5, MG = C.POINTER(Tensor5), C.POINTER(MeshGridDesc)
     sigs = {
         "recmv_abi_version": (C.c_int, []),
@@ -218,6 +218,10 @@ def _declare(lib):
         "recmv_laplacian_step": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp, C.c_double, vp, vp]),
         "recmv_face_normal_filter": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, C.c_double, C.c_double, vp, vp]),
         "recmv_vertex_from_normals": (C.c_int, [vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp]),
+        "recmv_points_within_max_cells": (i64, []),
+        "recmv_points_within_cells": (C.c_int, [vp, i64, f64, f64, f64, f64, i32, i32, i32, vp, vp]),
+        "recmv_points_within_count": (C.c_int, [vp, vp, i64, i64, f64, f64, f64, f64, f64, i32, i32, i32, vp, vp, vp]),
+        "recmv_points_within_fill": (C.c_int, [vp, vp, i64, i64, f64, f64, f64, f64, f64, i32, i32, i32, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)       # AttributeError if the symbol is missing: fail loudly
