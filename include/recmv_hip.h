@@ -396,7 +396,10 @@ int recmv_mlp_vjp_input(const recmv_mlp* m, const float* x, int64_t P, int n_out
  * gather, skip concatenation, bias, activation, residual; in the reverse pass the activation gradients and the encoding's VJP),
  * the weights stream from L2 in MFMA-fragment order.  Replaces, like the chains, model/network.py:98-133 (SDF value + input
  * gradient) and model/Deformer.py:141-206 (offset MLP + VJP) as they are called by utils/FindSurfacePs.py:273-353.
- *   recmv_mlp_rows_supported : 1 when the descriptor fits (2..12 layers, widths <= 512, <= 8 encoding bands, one net).
+ *   recmv_mlp_rows_supported : 1 when the descriptor fits (2..12 layers, every layer's inputs and outputs <= 512 wide — the last
+ *                              layer's rows included, although only 16 of them can be evaluated —, <= 8 encoding bands, one net,
+ *                              the skip connection not on layer 0); 0 otherwise: recmv_mlp_pack_bytes is then 0 and the pack and
+ *                              the two passes return RECMV_ERR_ARG without a launch.
  *   recmv_mlp_pack(_bytes)   : lays every layer's weight (and its transpose) out in fragment order, zero-padded — once per
  *                              weight version; the packed buffer is what the two passes read.
  *   recmv_mlp_rows_forward   : as recmv_mlp_forward with n_out <= 16; keep = 1 stores the hidden activations in `workspace`

@@ -265,6 +265,7 @@ extern "C" int recmv_mlp_vjp_input(const recmv_mlp* m, const float* x, int64_t P
   RECMV_REQUIRE(x && gx && workspace, "mlp_vjp_input: NULL pointer");
   RECMV_REQUIRE(n_out >= 1 && n_out <= m->rows[n - 1], "mlp_vjp_input: bad n_out");
   RECMV_REQUIRE(g_out || n_out == 1, "mlp_vjp_input: a NULL cotangent means ones and needs n_out == 1");
+  RECMV_REQUIRE(!m->residual || (g_out && n_out == 3), "mlp_vjp_input: residual nets need their 3-d cotangent");
   for (int l = 0; l < n; ++l) RECMV_REQUIRE(m->Wt[l], "mlp_vjp_input: layer %d has no transposed weight", l);
   const int64_t split = second_net_from(m, P);
   if (split)

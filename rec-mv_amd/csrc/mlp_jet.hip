@@ -136,7 +136,10 @@ JetLayout jet_layout(const recmv_mlp* m, int64_t P) {
     L.off_z[l] = take(L.R * L.ld_act * 4);
     L.off_h[l] = take(L.R * L.ld_act * 4);
   }
-  L.off_ga = take(L.R * L.ld_act * 4);
+  // the reverse sweep also forms the [n_j, dims[n-1]] product gtang^T T of the last layer in the first of the two cotangent buffers:
+  // with fewer than rows_last / 4 points the 4P rows of a cotangent block would not hold it
+  const int64_t ga_rows = L.R > m->rows[m->n_layers - 1] ? L.R : m->rows[m->n_layers - 1];
+  L.off_ga = take(ga_rows * L.ld_act * 4);
   L.off_gb = take(L.R * L.ld_act * 4);
   L.off_park = take(L.R * L.ld_in * 4);
   L.tn_bytes = (recmv_gemm_tn_workspace_bytes(L.ld_act, L.ld_act, L.R) + 255) / 256 * 256 +

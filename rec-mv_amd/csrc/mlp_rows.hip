@@ -621,7 +621,8 @@ int rows_supported(const recmv_mlp* m) {
   if (m->split_row > 0 && m->W2[0]) return 0;
   for (int l = 0; l <= m->n_layers; ++l)
     if (m->dims[l] > kMaxWidth && l < m->n_layers) return 0;
-  for (int l = 0; l + 1 < m->n_layers; ++l)
+  // the last layer too: the reverse pass stages ceil(rows / 16) chunks of its cotangent in an LDS row of kLD floats
+  for (int l = 0; l < m->n_layers; ++l)
     if (m->rows[l] > kMaxWidth) return 0;
   if (m->skip_layer == 0 || m->skip_layer >= m->n_layers) return 0;
   return 1;
