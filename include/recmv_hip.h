@@ -39,7 +39,9 @@ extern "C" {
  *        recmv_vertex_quadrics, recmv_edge_collapse_cost, recmv_collapse_flip_check; recmv_cotan_weights,
  *        recmv_laplacian_step, recmv_face_normal_filter, recmv_vertex_from_normals (mesh smoothing: pure additions, still v11);
  *        recmv_points_within_cells, recmv_points_within_count, recmv_points_within_fill, recmv_points_within_max_cells (the
- *        point-pair search of mesh repair: pure additions, still v11).
+ *        point-pair search of mesh repair: pure additions, still v11); recmv_voxel_band_workspace_bytes,
+ *        recmv_voxel_band_distance, recmv_voxel_sign_fill with the recmv_lattice descriptor (mesh voxelisation: pure additions,
+ *        still v11).
  *   v10: recmv_verts_normals, recmv_hard_phong_shade, recmv_hard_phong_params_floats added.  Added since without a bump (no
  *        existing signature changed, and _lib.py rejects a library that lacks them): recmv_knn1, recmv_nricp_energy,
  *        recmv_lap_align_solve, recmv_lap_smooth, recmv_closest_point, recmv_iso_relax, recmv_loop_subdivide,
@@ -1032,6 +1034,42 @@ int recmv_points_within_count(const float* pts, const int64_t* ids, int64_t n, i
 int recmv_points_within_fill(const float* pts, const int64_t* ids, int64_t n, int64_t V, double eps, double ox, double oy,
                              double oz, double cell, int32_t nx, int32_t ny, int32_t nz, const int32_t* cell_start,
                              const int64_t* offsets, int64_t* pairs, int64_t P, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Mesh voxelisation (csrc/mesh_voxelize.hip; added to ABI v11, no existing signature changed).  Not in the reference.  The
+ * kernels of recmv/voxelize.py: a triangle mesh (verts [V,3] f32, faces [F,3] int64, F < 2^31) turned into a distance lattice.
+ * The lattice is a descriptor in HOST memory: node (i, j, k) sits at origin[a] + (float)idx[a] * step — one multiply and one
+ * add in f32, not contracted — and has the index (i * ny + j) * nz + k: [NX, NY, NZ] with z contiguous, the volume layout of the
+ * marching-cubes entry points.  At most 2^28 nodes (their limit); step positive and finite, the origin finite.
+ * recmv_voxel_band_distance: for every node the exact nearest face among the faces within `band` of it: dist2 [N] f32 its
+ *   squared distance and face [N] int64 its id, ties to the lowest id; a node with no face within the band gets +inf and -1.
+ *   "Within the band": dist2 <= band * band, the product formed once in f32.  The distance is that of the closest-point entry
+ *   point above (the same function on the same (a, b - a, c - a)): the same bits.  A face with an index outside [0, V) is
+ *   skipped; NaN never wins.  One wave per face strides over the nodes of the face's box dilated by band and one further
+ *   node; a node in the band does one 64-bit integer atomicMin on (float bits of dist2) << 32 | face id — no float atomics, and
+ *   the result does not depend on the arrival order.  Workspace: recmv_voxel_band_workspace_bytes(lattice) bytes (8 per node;
+ *   -1 for an unusable lattice), 8-byte aligned; it is not needed for F = 0 or V = 0.
+ * recmv_voxel_sign_fill: inside [N] uint8 and sdf [N] f32 from dist2 and inside_band [N] uint8 (read at band nodes only).  One
+ *   thread walks one (j, k) column along +x: a band node (dist2 <= band * band) takes inside_band, a node outside the band the
+ *   value of the last band node before it in its column, outside if there is none — sound whenever band >= step, since a
+ *   lattice edge the surface crosses has both ends within one step of it.  sdf = (inside ? -1 : +1) * min(sqrt(dist2), band).
+ *   open_columns (one int64 in DEVICE memory) = the number of columns that end inside: 0 for a closed mesh well inside the
+ *   lattice, not 0 for an open mesh or a lost parity; a diagnostic, no error.  signed_field = 0: every node is outside and
+ *   inside_band is not read (it may be NULL).
+ * Argument errors (NULL pointers with nodes to write, a step that is not positive and finite, a band that is negative or not
+ * finite, negative dimensions, more than 2^28 nodes, a short or misaligned workspace) are found before any HIP call.  A
+ * dimension of 0 is a no-op; F = 0 or V = 0 fills dist2 with +inf and face with -1.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct recmv_lattice {
+  float origin[3];
+  float step;
+  int32_t nx, ny, nz;
+} recmv_lattice;
+int64_t recmv_voxel_band_workspace_bytes(const recmv_lattice* lattice);
+int recmv_voxel_band_distance(const float* verts, int64_t V, const int64_t* faces, int64_t F, const recmv_lattice* lattice,
+                              float band, float* dist2, int64_t* face, void* workspace, int64_t workspace_bytes, void* stream);
+int recmv_voxel_sign_fill(const float* dist2, const uint8_t* inside_band, const recmv_lattice* lattice, float band,
+                          int signed_field, float* sdf, uint8_t* inside, int64_t* open_columns, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,14 @@ before any of the above (recmv.repair.repair: degenerate and duplicate faces dro
 pinch vertex taken apart, every orientable piece consistently oriented, unused vertices dropped); `--weld-eps E` (a length; it
 implies `--repair`) first welds the vertices within E of each other, 0 the coincident ones — without it nothing is welded.  That
 is the way to an edge-manifold mesh; topology.json then holds `repair` per file, the numbers of that call's info.
+`--voxel-remesh STEP` (or `--voxel-resolution N`, the nodes along the longest axis) remeshes what is left through a distance
+lattice BEFORE it is smoothed or simplified (recmv.voxelize.remesh: exact distances in a narrow band, a crossing-parity sign,
+marching cubes — a watertight manifold mesh of uniform resolution from a CLOSED mesh, whatever its self-intersections);
+topology.json then holds `voxel` per file (lattice, band_nodes, open_columns, sign_conflicts, faces before and after).  A mesh
+that is not closed shows as open_columns > 0 or sign_conflicts > 0 and the command refuses it, writing nothing, unless
+`--voxel-force` is given.  `--solidify T` takes the
+unsigned route instead (recmv.voxelize.solidify: a closed shell of thickness T around an open garment; the voxel flag gives the
+step).
 `--out`/topology.json holds per file
 the report `before`, the report `after` and what was `dropped`, with a simplify flag `simplify`: that call's info, and with
 `--smooth` `smooth`: that call's info, beside the smooth parameters at the top level.  With `--report-only` nothing is cleaned or written but
@@ -28,6 +36,7 @@ loops — an upper garment with four feature lines has four.
         [--smooth taubin|laplacian|bilateral] [--smooth-iters N] [--smooth-lambda L] [--smooth-mu M]
         [--smooth-weights uniform|cotangent] [--smooth-boundary fixed|curve|free] [--smooth-normal-iters N]
         [--smooth-vertex-iters N] [--smooth-sigma-s S] [--repair] [--weld-eps E]
+        [--voxel-remesh STEP | --voxel-resolution N] [--voxel-force] [--solidify T]
 """
 import argparse
 import json
@@ -69,6 +78,15 @@ def build_parser():
                         help='first of all mend every mesh: drop degenerate faces, split non-manifold edges and vertices, orient')
     parser.add_argument('--weld-eps', default=None, type=float,
                         help='a length: weld the vertices within it of each other before the repair (implies --repair)')
+    parser.add_argument('--voxel-remesh', default=None, type=float, metavar='STEP',
+                        help='after cleaning and before smoothing, remesh every (closed) mesh through a distance lattice of this step')
+    parser.add_argument('--voxel-resolution', default=None, type=int, metavar='N',
+                        help='the same with the step chosen so that the lattice has N nodes along the longest axis')
+    parser.add_argument('--voxel-force', action='store_true',
+                        help='write the voxel remesh even when columns of the lattice end inside (the mesh is not closed)')
+    parser.add_argument('--solidify', default=None, type=float, metavar='T',
+                        help='instead of the signed remesh: a closed shell of thickness T around every (open) mesh; '
+                             '--voxel-remesh or --voxel-resolution gives the step')
     parser.add_argument('--report-only', action='store_true', help='describe the meshes, clean and write none')
     return parser
 
@@ -118,6 +136,22 @@ def main(argv=None):
     repairing = args.repair or args.weld_eps is not None
     if repairing and args.report_only:
         parser.error("--report-only writes no mesh: --repair and --weld-eps need --out")
+    voxelising = args.voxel_remesh is not None or args.voxel_resolution is not None
+    if args.voxel_remesh is not None and args.voxel_resolution is not None:
+        parser.error("give --voxel-remesh or --voxel-resolution, not both")
+    if args.voxel_remesh is not None and not (0. < args.voxel_remesh < float('inf')):
+        parser.error("--voxel-remesh must be a positive, finite step")
+    if args.voxel_resolution is not None and args.voxel_resolution < 2:
+        parser.error("--voxel-resolution must be at least 2")
+    if args.solidify is not None:
+        if not voxelising:
+            parser.error("--solidify needs --voxel-remesh or --voxel-resolution for the step")
+        if not (0. < args.solidify < float('inf')):
+            parser.error("--solidify must be a positive, finite thickness")
+    if args.voxel_force and not voxelising:
+        parser.error("--voxel-force needs --voxel-remesh or --voxel-resolution")
+    if voxelising and args.report_only:
+        parser.error("--report-only writes no mesh: the voxel flags need --out")
     if not args.report_only and not args.out:
         parser.error("--out is needed unless --report-only is given")
     try:
@@ -153,7 +187,28 @@ def main(argv=None):
         if not args.report_only:
             kv, kf, info = topology.keep_components(v, f, largest=args.largest, min_area_frac=args.min_area_frac,
                                                     min_faces=args.min_faces, connectivity=args.connectivity)
-            if args.smooth is not None:                    # before the quadrics are built: they then see the de-noised planes
+            if voxelising:                                 # behind the repair and the floaters, before smoothing and simplifying
+                from recmv import voxelize
+                try:
+                    if args.solidify is not None:
+                        kv, kf, vi = voxelize.solidify(kv, kf, args.solidify, step=args.voxel_remesh,
+                                                       resolution=args.voxel_resolution)
+                    else:
+                        kv, kf, vi = voxelize.remesh(kv, kf, step=args.voxel_remesh, resolution=args.voxel_resolution)
+                except ValueError as e:
+                    parser.error("%s: %s" % (name, e))
+                if (vi['open_columns'] > 0 or vi['sign_conflicts'] > 0) and not args.voxel_force:
+                    parser.error("%s: open_columns = %d, sign_conflicts = %d: columns of the lattice end inside the mesh, or nodes far "
+                                 "from the surface disagree about their side, so the mesh is not closed (or a parity was lost) and "
+                                 "its voxel remesh is not to be trusted; nothing written.  --solidify is for open surfaces; "
+                                 "--voxel-force writes the remesh all the same" % (name, vi['open_columns'], vi['sign_conflicts']))
+                entry['voxel'] = {'mode': 'solidify' if args.solidify is not None else 'remesh', 'lattice': vi['lattice'].json(),
+                                  'band': vi['band'], 'band_nodes': vi['band_nodes'], 'open_columns': vi['open_columns'],
+                                  'sign_conflicts': vi['sign_conflicts'], 'faces_before': vi['faces_in'], 'faces_after': vi['faces_out']}
+                print('%s: voxel %s on %d x %d x %d nodes of step %g: %d -> %d faces, %d band nodes, %d open columns, %d sign '
+                      'conflicts' % (name, entry['voxel']['mode'], *vi['lattice'].dims, vi['lattice'].step, vi['faces_in'],
+                                     vi['faces_out'], vi['band_nodes'], vi['open_columns'], vi['sign_conflicts']))
+            if args.smooth is not None:                   # before the quadrics are built: they then see the de-noised planes
                 from recmv import smooth
                 kv, entry['smooth'] = smooth.smooth(kv, kf, method=args.smooth, iterations=args.smooth_iters, lam=args.smooth_lambda,
                                                     mu=args.smooth_mu, weights=args.smooth_weights, boundary=args.smooth_boundary,
@@ -187,6 +242,9 @@ def main(argv=None):
                     'simplify_max_error': args.simplify_max_error})
     if repairing:                                          # (likewise)
         out.update({'repair': True, 'weld_eps': args.weld_eps})
+    if voxelising:                                         # (likewise)
+        out.update({'voxel_remesh': args.voxel_remesh, 'voxel_resolution': args.voxel_resolution, 'voxel_force': args.voxel_force,
+                    'solidify': args.solidify})
     if args.smooth is not None:                            # (likewise)
         out.update({'smooth': args.smooth, 'smooth_iters': args.smooth_iters, 'smooth_lambda': args.smooth_lambda,
                     'smooth_mu': args.smooth_mu, 'smooth_weights': args.smooth_weights, 'smooth_boundary': args.smooth_boundary,

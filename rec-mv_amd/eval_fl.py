@@ -29,12 +29,17 @@ recmv.repair.repair: degenerate and duplicate faces dropped, non-manifold edges 
 oriented, unused vertices dropped), and `--weld-eps E` (a length, implies `--repair`) first welds the vertices within E of each
 other: a scan exported with one vertex triple per face reads as F pieces until it is welded, and `--topology` and
 `--drop-floaters` mean nothing for it.  The numbers of the two calls' info go into the pair's entry as `repair_pred` and
-`repair_gt`.
+`repair_gt`.  `--volume` adds to every pair the volumetric intersection over union of the two meshes and their volumes
+(`volume_iou`, `volume_pred`, `volume_gt`; recmv.voxelize.volume_iou on one lattice around both, of step `--volume-step` or with
+129 nodes along the longest axis; the counts and the lattice under `volume`).  The sign is a crossing parity, so both meshes must
+be closed: when a diagnostic of either says it is not (`open_columns`, `sign_conflicts`) the three figures are None, `volume`
+holds the `reason`, and they have no `mean`.
 
     python rec-mv_amd/eval_fl.py --gpu-ids 0 --pred <obj|dir> --gt <obj|dir> [--samples N] [--seed S] [--thresholds t ...]
         [--scale s] [--method auto|grid|brute] [--intersections [--body <obj|dir> [--penetration]]] [--out metrics.json]
         [--align none|rigid|similarity [--align-metric plane|point] [--align-trim f] [--align-iters n]
          [--align-from each|first] [--align-out DIR]] [--drop-floaters FRAC] [--topology] [--repair] [--weld-eps E]
+        [--volume [--volume-step S]]
 """
 import argparse
 import json
@@ -78,6 +83,10 @@ def build_parser():
                         help='mend the prediction and the ground truth before everything else (recmv.repair.repair)')
     parser.add_argument('--weld-eps', default=None, type=float,
                         help='a length: weld the vertices within it of each other before the repair (implies --repair)')
+    parser.add_argument('--volume', action='store_true',
+                        help='add the volumetric IoU and the two volumes of every pair (closed meshes; recmv.voxelize.volume_iou)')
+    parser.add_argument('--volume-step', default=None, type=float, metavar='S',
+                        help='with --volume: the lattice step (default: 129 nodes along the longest axis of the pair\'s box)')
     return parser
 
 
@@ -133,6 +142,10 @@ def main(argv=None):
     if args.weld_eps is not None and not (0. <= args.weld_eps < float('inf')):
         parser.error("--weld-eps must be finite and not negative")
     repairing = args.repair or args.weld_eps is not None
+    if args.volume_step is not None and not args.volume:
+        parser.error("--volume-step needs --volume")
+    if args.volume_step is not None and not (0. < args.volume_step < float('inf')):
+        parser.error("--volume-step must be positive and finite")
     import torch
     from infer_fl_animation import temporal_smoothness
     from recmv import align, metrics, topology
@@ -200,6 +213,19 @@ def main(argv=None):
                 if args.penetration:
                     pen = metrics.penetration(pv.to(device), bv.to(device), bfaces.to(device), method=args.method)
                     per_pair[stem].update({'body_inside_vertices': pen['count'], 'body_max_depth': pen['max_depth']})
+        if args.volume:
+            from recmv import voxelize
+            vol = voxelize.volume_iou(pv.to(device), pfaces.to(device), gv.to(device), gfaces.to(device), step=args.volume_step,
+                                      method=args.method)
+            closed = not (vol['open_columns_a'] or vol['open_columns_b'] or vol['sign_conflicts_a'] or vol['sign_conflicts_b'])
+            per_pair[stem].update({'volume_iou': vol['iou'] if closed else None, 'volume_pred': vol['volume_a'] if closed else None,
+                                   'volume_gt': vol['volume_b'] if closed else None})
+            per_pair[stem]['volume'] = {'step': vol['step'], 'lattice': vol['lattice'].json(), 'intersection': vol['intersection'],
+                                        'union': vol['union'], 'open_columns_pred': vol['open_columns_a'],
+                                        'open_columns_gt': vol['open_columns_b'], 'sign_conflicts_pred': vol['sign_conflicts_a'],
+                                        'sign_conflicts_gt': vol['sign_conflicts_b'],
+                                        'reason': None if closed else 'a mesh of the pair is not closed (open_columns or sign_conflicts > 0): '
+                                                                      'a crossing parity gives it no volume'}
         if stem in floaters:
             per_pair[stem]['floaters'] = floaters[stem]
         if stem in repaired:
@@ -211,6 +237,8 @@ def main(argv=None):
             stem, per_pair[stem]['chamfer_l1'], per_pair[stem]['accuracy'], per_pair[stem]['completeness'],
             per_pair[stem]['normal_consistency']))
     keys = [k for k, x in next(iter(per_pair.values())).items() if not isinstance(x, dict)]
+    if args.volume:                                        # a figure that is None for a pair (a mesh that is not closed) has no mean
+        keys = [k for k in keys if all(m[k] is not None for m in per_pair.values())]
     mean = {k: sum(m[k] for m in per_pair.values()) / len(per_pair) for k in keys}
     res = {'pairs': per_pair, 'mean': mean, 'samples': args.samples, 'seed': args.seed, 'method': args.method,
            'thresholds': list(thresholds), 'scale': args.scale, 'unmatched_pred': only_pred, 'unmatched_gt': only_gt}

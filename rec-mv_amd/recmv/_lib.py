@@ -51,6 +51,11 @@ class LbsGrid(C.Structure):
                 ("center", C.c_float * 3), ("scale", C.c_float * 3)]
 
 
+class Lattice(C.Structure):
+    """recmv_lattice of include/recmv_hip.h."""
+    _fields_ = [("origin", C.c_float * 3), ("step", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32)]
+
+
 _lib = None
 
 
@@ -75,7 +80,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
 
 def _declare(lib):
     vp, i64, i32, f32, f64 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double
-    T5, MG = C.POINTER(Tensor5), C.POINTER(MeshGridDesc)
+    T5, MG, LT = C.POINTER(Tensor5), C.POINTER(MeshGridDesc), C.POINTER(Lattice)
     sigs = {
         "recmv_abi_version": (C.c_int, []),
         "recmv_no_packed_f32": (C.c_int, []),
@@ -222,6 +227,9 @@ def _declare(lib):
         "recmv_points_within_cells": (C.c_int, [vp, i64, f64, f64, f64, f64, i32, i32, i32, vp, vp]),
         "recmv_points_within_count": (C.c_int, [vp, vp, i64, i64, f64, f64, f64, f64, f64, i32, i32, i32, vp, vp, vp]),
         "recmv_points_within_fill": (C.c_int, [vp, vp, i64, i64, f64, f64, f64, f64, f64, i32, i32, i32, vp, vp, vp, i64, vp]),
+        "recmv_voxel_band_workspace_bytes": (i64, [LT]),
+        "recmv_voxel_band_distance": (C.c_int, [vp, i64, vp, i64, LT, f32, vp, vp, vp, i64, vp]),
+        "recmv_voxel_sign_fill": (C.c_int, [vp, vp, LT, f32, i32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)       # AttributeError if the symbol is missing: fail loudly
