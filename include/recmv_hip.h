@@ -41,7 +41,8 @@ extern "C" {
  *        recmv_points_within_cells, recmv_points_within_count, recmv_points_within_fill, recmv_points_within_max_cells (the
  *        point-pair search of mesh repair: pure additions, still v11); recmv_voxel_band_workspace_bytes,
  *        recmv_voxel_band_distance, recmv_voxel_sign_fill with the recmv_lattice descriptor (mesh voxelisation: pure additions,
- *        still v11).
+ *        still v11); recmv_hole_triangulate, recmv_hole_triangulate_workspace_bytes, recmv_hole_fill_lds_max_edges,
+ *        recmv_hole_fill_auto_max_edges, recmv_hole_fill_max_edges (hole filling: pure additions, still v11).
  *   v10: recmv_verts_normals, recmv_hard_phong_shade, recmv_hard_phong_params_floats added.  Added since without a bump (no
  *        existing signature changed, and _lib.py rejects a library that lacks them): recmv_knn1, recmv_nricp_energy,
  *        recmv_lap_align_solve, recmv_lap_smooth, recmv_closest_point, recmv_iso_relax, recmv_loop_subdivide,
@@ -1070,6 +1071,37 @@ int recmv_voxel_band_distance(const float* verts, int64_t V, const int64_t* face
                               float band, float* dist2, int64_t* face, void* workspace, int64_t workspace_bytes, void* stream);
 int recmv_voxel_sign_fill(const float* dist2, const uint8_t* inside_band, const recmv_lattice* lattice, float band,
                           int signed_field, float* sdf, uint8_t* inside, int64_t* open_columns, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Hole filling (csrc/hole_fill.hip; added to ABI v11, no existing signature changed).  Not in the reference.  The kernel of
+ * recmv/holes.py: the minimum-area triangulation of L closed loops in one call.  Loop l is the vertex ids
+ * loop_verts[loop_offsets[l] .. loop_offsets[l+1]) (DEVICE memory, int64), n = 3 .. recmv_hole_fill_max_edges() of them, with
+ * the points p_i = verts[l_i] (verts [V,3] f32; an id outside [0, V) reads as a NaN point).  Interval dynamic programming in
+ * float64 on the f32 coordinates, un-contracted, every operation correctly rounded:
+ *   W[i][i+1] = 0;  W[i][j] = min over i < k < j of (W[i][k] + W[k][j]) + A(i,k,j);
+ *   A = 0.5 * sqrt((cx*cx + cy*cy) + cz*cz), (cx, cy, cz) = u x v component by component (cx = u.y*v.z - u.z*v.y, ...),
+ *   u = p_k - p_i, v = p_j - p_i.  A candidate wins only when it is smaller (<) than the best so far, k ascending from +inf:
+ *   ties go to the lowest k, NaN never wins, an entry without a winner is +inf with k = i + 1.
+ * out_weight [L] f64 = W[0][n-1] per loop (not finite: the loop has a point that is not finite).  out_faces [total - 2 L, 3]
+ * int64: loop l's n - 2 faces from row loop_offsets[l] - 2 l, in pre-order of the split tree (the triangle of (i, j), then the
+ * subtree of (i, k), then that of (k, j)), each written (l_j, l_k, l_i): the reverse of the loop's direction.
+ * loop_offsets [L+1] is read in HOST memory (the sizes decide launches and the workspace layout) and loop_offsets_device is
+ * the same array in device memory.  route: 0 auto (a loop of at most recmv_hole_fill_auto_max_edges() vertices runs in one
+ * workgroup with its tables in LDS, a longer one in the workspace with one launch per diagonal), 1 every loop in LDS (a
+ * loop of more than recmv_hole_fill_lds_max_edges() vertices is an argument error), 2 every loop through the workspace.  The routes give the same bits.
+ * Workspace: recmv_hole_triangulate_workspace_bytes(loop_offsets, L, route) bytes, 8-byte aligned (24 B and n(n-1)/2 * 18 B
+ * + 12 n B, rounded to 8, per loop that does not run in LDS; 0 when all do; -1 with a message for unusable sizes); a shorter
+ * one returns RECMV_ERR_WORKSPACE.  Argument errors (L < 0, a bad route, NULL pointers, loop_offsets[0] != 0, a loop shorter
+ * than 3 or longer than the cap, an output that aliases an input or the other output) are found before any HIP call.  L = 0
+ * is a no-op.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t recmv_hole_fill_lds_max_edges(void);
+int64_t recmv_hole_fill_auto_max_edges(void);
+int64_t recmv_hole_fill_max_edges(void);
+int64_t recmv_hole_triangulate_workspace_bytes(const int64_t* loop_offsets, int64_t L, int route);
+int recmv_hole_triangulate(const float* verts, int64_t V, const int64_t* loop_verts, const int64_t* loop_offsets,
+                           const int64_t* loop_offsets_device, int64_t L, int64_t* out_faces, double* out_weight,
+                           void* workspace, int64_t workspace_bytes, int route, void* stream);
 
 #ifdef __cplusplus
 }

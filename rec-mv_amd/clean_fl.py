@@ -25,6 +25,14 @@ that is not closed shows as open_columns > 0 or sign_conflicts > 0 and the comma
 `--voxel-force` is given.  `--solidify T` takes the
 unsigned route instead (recmv.voxelize.solidify: a closed shell of thickness T around an open garment; the voxel flag gives the
 step).
+`--fill-holes` closes the holes of what is left AFTER the repair and the floaters and BEFORE the voxel remesh, the smoothing and
+the simplification (recmv.holes.fill: every boundary loop triangulated with the least area; the mesh must be edge-manifold and
+consistently oriented, which `--repair` sees to).  Garments are open by design, so say which loops are holes: `--fill-max-edges N`
+and `--fill-max-perimeter P` leave longer loops open, `--fill-keep-largest K` leaves the K longest open (a skirt has 2 openings,
+trousers 3, a shirt 4).  `--fill-refine` splits and flips the patches' inner edges down to the length of their borders' and
+`--fill-fair-iters N` (with it) then relaxes the new vertices.  topology.json then holds `holes` per file, that call's info, and
+the per-file report shows the boundary loops before and after.  With it `--voxel-remesh` takes a holed mesh without
+`--voxel-force`.
 `--out`/topology.json holds per file
 the report `before`, the report `after` and what was `dropped`, with a simplify flag `simplify`: that call's info, and with
 `--smooth` `smooth`: that call's info, beside the smooth parameters at the top level.  With `--report-only` nothing is cleaned or written but
@@ -37,6 +45,8 @@ loops — an upper garment with four feature lines has four.
         [--smooth-weights uniform|cotangent] [--smooth-boundary fixed|curve|free] [--smooth-normal-iters N]
         [--smooth-vertex-iters N] [--smooth-sigma-s S] [--repair] [--weld-eps E]
         [--voxel-remesh STEP | --voxel-resolution N] [--voxel-force] [--solidify T]
+        [--fill-holes] [--fill-max-edges N] [--fill-max-perimeter P] [--fill-keep-largest K] [--fill-refine]
+        [--fill-fair-iters N]
 """
 import argparse
 import json
@@ -87,8 +97,38 @@ def build_parser():
     parser.add_argument('--solidify', default=None, type=float, metavar='T',
                         help='instead of the signed remesh: a closed shell of thickness T around every (open) mesh; '
                              '--voxel-remesh or --voxel-resolution gives the step')
+    parser.add_argument('--fill-holes', action='store_true',
+                        help='after the repair and the floaters and before every later stage, close the holes (least-area patches)')
+    parser.add_argument('--fill-max-edges', default=None, type=int, metavar='N', help='loops of more than N edges stay open')
+    parser.add_argument('--fill-max-perimeter', default=None, type=float, metavar='P', help='loops longer than P stay open')
+    parser.add_argument('--fill-keep-largest', default=None, type=int, metavar='K',
+                        help='the K loops of longest perimeter stay open (the openings of a garment)')
+    parser.add_argument('--fill-refine', action='store_true', help='split and flip the inner edges of the patches')
+    parser.add_argument('--fill-fair-iters', default=None, type=int, metavar='N',
+                        help='with --fill-refine: Laplacian iterations on the new vertices')
     parser.add_argument('--report-only', action='store_true', help='describe the meshes, clean and write none')
     return parser
+
+
+def check_fill_flags(parser, args):
+    """The parser errors of the --fill-* flags."""
+    given = [flag for flag, x in (('--fill-max-edges', args.fill_max_edges), ('--fill-max-perimeter', args.fill_max_perimeter),
+                                  ('--fill-keep-largest', args.fill_keep_largest), ('--fill-refine', args.fill_refine or None),
+                                  ('--fill-fair-iters', args.fill_fair_iters)) if x is not None]
+    if given and not args.fill_holes:
+        parser.error("%s needs --fill-holes" % given[0])
+    if args.fill_holes and args.report_only:
+        parser.error("--report-only writes no mesh: --fill-holes needs --out")
+    if args.fill_max_edges is not None and args.fill_max_edges < 0:
+        parser.error("--fill-max-edges must not be negative")
+    if args.fill_max_perimeter is not None and not (0. <= args.fill_max_perimeter < float('inf')):
+        parser.error("--fill-max-perimeter must be finite and not negative")
+    if args.fill_keep_largest is not None and args.fill_keep_largest < 0:
+        parser.error("--fill-keep-largest must not be negative")
+    if args.fill_fair_iters is not None and args.fill_fair_iters < 0:
+        parser.error("--fill-fair-iters must not be negative")
+    if args.fill_fair_iters and not args.fill_refine:
+        parser.error("--fill-fair-iters needs --fill-refine: without it a patch has no vertex of its own")
 
 
 def mesh_files(path):
@@ -152,6 +192,7 @@ def main(argv=None):
         parser.error("--voxel-force needs --voxel-remesh or --voxel-resolution")
     if voxelising and args.report_only:
         parser.error("--report-only writes no mesh: the voxel flags need --out")
+    check_fill_flags(parser, args)
     if not args.report_only and not args.out:
         parser.error("--out is needed unless --report-only is given")
     try:
@@ -187,6 +228,17 @@ def main(argv=None):
         if not args.report_only:
             kv, kf, info = topology.keep_components(v, f, largest=args.largest, min_area_frac=args.min_area_frac,
                                                     min_faces=args.min_faces, connectivity=args.connectivity)
+            if args.fill_holes:                            # behind the repair and the floaters, before every later stage
+                from recmv import holes
+                try:
+                    kv, kf, hi = holes.fill(kv, kf, max_edges=args.fill_max_edges, max_perimeter=args.fill_max_perimeter,
+                                            keep_largest=args.fill_keep_largest or 0, refine=args.fill_refine,
+                                            fair_iterations=args.fill_fair_iters or 0)
+                except ValueError as e:
+                    parser.error("%s: %s" % (name, e))
+                entry['holes'] = hi = holes.info_json(hi)
+                print('%s: %d boundary loops, %d filled with %d faces and %d vertices, %d left open' % (
+                    name, hi['loops'], hi['filled'], sum(hi['faces_added']), sum(hi['verts_added']), hi['loops'] - hi['filled']))
             if voxelising:                                 # behind the repair and the floaters, before smoothing and simplifying
                 from recmv import voxelize
                 try:
@@ -245,6 +297,10 @@ def main(argv=None):
     if voxelising:                                         # (likewise)
         out.update({'voxel_remesh': args.voxel_remesh, 'voxel_resolution': args.voxel_resolution, 'voxel_force': args.voxel_force,
                     'solidify': args.solidify})
+    if args.fill_holes:                                    # (likewise)
+        out.update({'fill_holes': True, 'fill_max_edges': args.fill_max_edges, 'fill_max_perimeter': args.fill_max_perimeter,
+                    'fill_keep_largest': args.fill_keep_largest, 'fill_refine': args.fill_refine,
+                    'fill_fair_iters': args.fill_fair_iters})
     if args.smooth is not None:                            # (likewise)
         out.update({'smooth': args.smooth, 'smooth_iters': args.smooth_iters, 'smooth_lambda': args.smooth_lambda,
                     'smooth_mu': args.smooth_mu, 'smooth_weights': args.smooth_weights, 'smooth_boundary': args.smooth_boundary,

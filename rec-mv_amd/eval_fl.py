@@ -39,7 +39,12 @@ holds the `reason`, and they have no `mean`.
         [--scale s] [--method auto|grid|brute] [--intersections [--body <obj|dir> [--penetration]]] [--out metrics.json]
         [--align none|rigid|similarity [--align-metric plane|point] [--align-trim f] [--align-iters n]
          [--align-from each|first] [--align-out DIR]] [--drop-floaters FRAC] [--topology] [--repair] [--weld-eps E]
-        [--volume [--volume-step S]]
+        [--volume [--volume-step S]] [--fill-holes [--fill-max-edges N] [--fill-keep-largest K]]
+
+`--fill-holes` closes the holes of the prediction AND the ground truth after `--repair` and before every metric
+(recmv.holes.fill: least-area patches; `--fill-max-edges N` leaves loops of more than N edges open, `--fill-keep-largest K` the
+K longest), so that `--volume` has something to measure on scans with missing patches; the two calls' info goes into the pair's
+entry as `holes_pred` and `holes_gt`.
 """
 import argparse
 import json
@@ -85,6 +90,11 @@ def build_parser():
                         help='a length: weld the vertices within it of each other before the repair (implies --repair)')
     parser.add_argument('--volume', action='store_true',
                         help='add the volumetric IoU and the two volumes of every pair (closed meshes; recmv.voxelize.volume_iou)')
+    parser.add_argument('--fill-holes', action='store_true',
+                        help='close the holes of both meshes after --repair and before the metrics (recmv.holes.fill)')
+    parser.add_argument('--fill-max-edges', default=None, type=int, metavar='N', help='with --fill-holes: longer loops stay open')
+    parser.add_argument('--fill-keep-largest', default=None, type=int, metavar='K',
+                        help='with --fill-holes: the K loops of longest perimeter stay open')
     parser.add_argument('--volume-step', default=None, type=float, metavar='S',
                         help='with --volume: the lattice step (default: 129 nodes along the longest axis of the pair\'s box)')
     return parser
@@ -146,6 +156,11 @@ def main(argv=None):
         parser.error("--volume-step needs --volume")
     if args.volume_step is not None and not (0. < args.volume_step < float('inf')):
         parser.error("--volume-step must be positive and finite")
+    if (args.fill_max_edges is not None or args.fill_keep_largest is not None) and not args.fill_holes:
+        parser.error("--fill-max-edges and --fill-keep-largest need --fill-holes")
+    if (args.fill_max_edges is not None and args.fill_max_edges < 0) or (args.fill_keep_largest is not None
+                                                                         and args.fill_keep_largest < 0):
+        parser.error("--fill-max-edges and --fill-keep-largest must not be negative")
     import torch
     from infer_fl_animation import temporal_smoothness
     from recmv import align, metrics, topology
@@ -153,7 +168,7 @@ def main(argv=None):
 
     device = torch.device('cuda:%d' % args.gpu_ids[0])
     thresholds = tuple(args.thresholds) if args.thresholds else metrics.DEFAULT_THRESHOLDS
-    per_pair, sequence, alignment, shared, floaters, repaired = {}, [], {}, None, {}, {}
+    per_pair, sequence, alignment, shared, floaters, repaired, filled = {}, [], {}, None, {}, {}, {}
     for stem, pf, gf in pairs:
         pv, pfaces = read_obj(pf)
         gv, gfaces = read_obj(gf)
@@ -167,6 +182,21 @@ def main(argv=None):
             repaired[stem] = {'repair_pred': repair.info_json(rp), 'repair_gt': repair.info_json(rg)}
             print('%s: repaired, prediction %d vertices and %d faces, ground truth %d vertices and %d faces' % (
                 stem, pv.shape[0], pfaces.shape[0], gv.shape[0], gfaces.shape[0]))
+        if args.fill_holes:
+            from recmv import holes
+            filled[stem] = {}
+            try:
+                hv, hf, hi = holes.fill(pv.to(device), pfaces.to(device), max_edges=args.fill_max_edges,
+                                        keep_largest=args.fill_keep_largest or 0)
+                pv, pfaces, filled[stem]['holes_pred'] = hv.cpu(), hf.cpu(), holes.info_json(hi)
+                hv, hf, hi = holes.fill(gv.to(device), gfaces.to(device), max_edges=args.fill_max_edges,
+                                        keep_largest=args.fill_keep_largest or 0)
+                gv, gfaces, filled[stem]['holes_gt'] = hv.cpu(), hf.cpu(), holes.info_json(hi)
+            except ValueError as e:
+                parser.error("%s: %s" % (stem, e))
+            print('%s: holes filled, prediction %d of %d loops, ground truth %d of %d' % (
+                stem, filled[stem]['holes_pred']['filled'], filled[stem]['holes_pred']['loops'],
+                filled[stem]['holes_gt']['filled'], filled[stem]['holes_gt']['loops']))
         if args.drop_floaters is not None:
             kv, kf, kept = topology.keep_components(pv.to(device), pfaces.to(device), min_area_frac=args.drop_floaters)
             floaters[stem] = {'min_area_frac': args.drop_floaters, 'components': kept['components'],
@@ -230,6 +260,8 @@ def main(argv=None):
             per_pair[stem]['floaters'] = floaters[stem]
         if stem in repaired:
             per_pair[stem].update(repaired[stem])
+        if stem in filled:
+            per_pair[stem].update(filled[stem])
         if args.topology:
             per_pair[stem]['topology_pred'] = topology.report(pv.to(device), pfaces.to(device))
             per_pair[stem]['topology_gt'] = topology.report(gv.to(device), gfaces.to(device))
@@ -244,6 +276,8 @@ def main(argv=None):
            'thresholds': list(thresholds), 'scale': args.scale, 'unmatched_pred': only_pred, 'unmatched_gt': only_gt}
     if repairing:                                          # (without these flags the output is what it always was)
         res['repair'] = {'weld_eps': args.weld_eps}
+    if args.fill_holes:
+        res['fill_holes'] = {'max_edges': args.fill_max_edges, 'keep_largest': args.fill_keep_largest}
     if args.align != 'none':                               # (not into pairs[stem]: `mean` sums every key there)
         res['align'] = {'mode': args.align, 'metric': args.align_metric, 'trim': args.align_trim, 'iters': args.align_iters,
                         'from': args.align_from}

@@ -230,6 +230,11 @@ def _declare(lib):
         "recmv_voxel_band_workspace_bytes": (i64, [LT]),
         "recmv_voxel_band_distance": (C.c_int, [vp, i64, vp, i64, LT, f32, vp, vp, vp, i64, vp]),
         "recmv_voxel_sign_fill": (C.c_int, [vp, vp, LT, f32, i32, vp, vp, vp, vp]),
+        "recmv_hole_fill_lds_max_edges": (i64, []),
+        "recmv_hole_fill_auto_max_edges": (i64, []),
+        "recmv_hole_fill_max_edges": (i64, []),
+        "recmv_hole_triangulate_workspace_bytes": (i64, [vp, i64, i32]),
+        "recmv_hole_triangulate": (C.c_int, [vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)       # AttributeError if the symbol is missing: fail loudly

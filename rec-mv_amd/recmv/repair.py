@@ -49,7 +49,7 @@ Definitions (INTEGRATION.md §5 repeats them; tests/mesh_repair_reference.py res
                     is idempotent: a second call with the same arguments changes nothing.
 
 Deliberately out of scope: hole filling (garments are open by design, so which boundary loops are holes needs a rule of its
-own), outward orientation by signed volume, T-junctions, and the removal of self-intersections.
+own: recmv.holes has it), outward orientation by signed volume, T-junctions, and the removal of self-intersections.
 """
 import math
 
