@@ -364,6 +364,8 @@ int recmv_kinematic_chain_backward(const float* poses, const float* Js_host, con
  *   last layer: no activation; only its first n_out rows are evaluated; residual: out = x + out (Deformer.py:201-206)
  * Wt[l] = W[l]^T ([dims[l], rows[l]] row-major) is only read by recmv_mlp_vjp_input.
  * pe_weights: the 2L annealing weights (utils/utils.py:40-46), ones when not annealed.
+ * Every function that takes a recmv_mlp validates it first, in one way (csrc/mlp_desc.h): an inconsistent descriptor is
+ * RECMV_ERR_ARG with the function's name in front of the message, and 0 from the *_bytes functions and recmv_mlp_rows_supported.
  * ---------------------------------------------------------------------------------------------- */
 #define RECMV_MLP_MAX_LAYERS 12
 typedef struct recmv_mlp {
@@ -605,6 +607,7 @@ int recmv_linear_backward(const float* gy, int64_t ldgy, const float* y, int64_t
  *             g_in [4P, pad4(dims[0])] (cotangent of the stacked layer-0 input; rows [0,P) x columns [3+6L, dims[0])
  *             are the per-point cotangents of the gathered code) and gx [P,3]; each may be NULL.
  * eye3: 9 floats on the device = the 3x3 identity.  The workspace carries the activations from forward to backward.
+ * One net: a descriptor that carries a second weight set (split_row > 0 and W2[0]) is RECMV_ERR_ARG in both passes.
  * recmv_gather_rows: out[r, 0:cols] = table[index[r] (or 0), 0:cols], columns [cols, fill) zeroed.
  * ---------------------------------------------------------------------------------------------- */
 int64_t recmv_mlp_jet_workspace_bytes(const recmv_mlp* m, int64_t P);

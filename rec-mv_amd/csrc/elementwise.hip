@@ -9,27 +9,12 @@
 //                forward and backward (gv, gg from gW), one workgroup per row.
 // All memory-bound; 16-byte accesses where the row length allows.
 #include "common.h"
+#include "activation.h"
 
 namespace recmv {
 namespace {
 
 constexpr int kBlk = 256;
-
-__device__ __forceinline__ float dact(float y, int act, float p) {
-  switch (act) {
-    case RECMV_ACT_RELU: return y > 0.f ? 1.f : 0.f;
-    case RECMV_ACT_SOFTPLUS: return -expm1f(-p * y);
-    case RECMV_ACT_TANH: return 1.f - y * y;
-    default: return 1.f;
-  }
-}
-__device__ __forceinline__ float d2act(float y, int act, float p) {
-  switch (act) {
-    case RECMV_ACT_SOFTPLUS: return p * expf(-p * y);
-    case RECMV_ACT_TANH: return -2.f * y;
-    default: return 0.f;
-  }
-}
 
 __global__ __launch_bounds__(kBlk) void act_grad_kernel(const float* __restrict__ gy, const float* __restrict__ y,
                                                         float* __restrict__ out, int64_t n, int act, float p,
@@ -38,21 +23,21 @@ __global__ __launch_bounds__(kBlk) void act_grad_kernel(const float* __restrict_
   for (int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kBlk) {
     const float4 a = reinterpret_cast<const float4*>(gy)[i], b = reinterpret_cast<const float4*>(y)[i];
     float4 o;
-    o.x = a.x * dact(b.x, act, p);
-    o.y = a.y * dact(b.y, act, p);
-    o.z = a.z * dact(b.z, act, p);
-    o.w = a.w * dact(b.w, act, p);
+    o.x = a.x * dact_libm(b.x, act, p);
+    o.y = a.y * dact_libm(b.y, act, p);
+    o.z = a.z * dact_libm(b.z, act, p);
+    o.w = a.w * dact_libm(b.w, act, p);
     reinterpret_cast<float4*>(out)[i] = o;
   }
   for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * kBlk + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlk)
-    out[i] = gy[i] * dact(y[i], act, p);
+    out[i] = gy[i] * dact_libm(y[i], act, p);
 }
 
 __global__ __launch_bounds__(kBlk) void act_grad2_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                          const float* __restrict__ y, float* __restrict__ out,
                                                          int64_t n, int act, float p) {
   for (int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlk)
-    out[i] = a[i] * b[i] * d2act(y[i], act, p);
+    out[i] = a[i] * b[i] * d2act_libm(y[i], act, p);
 }
 
 __device__ __forceinline__ float block_sum(float v, float* sh) {

@@ -3,15 +3,7 @@
 #pragma once
 #include "common.h"
 #include "gemm_route.h"
-// RECMV_LIBM_SOFTPLUS (an experiment build of tools/trajectory_seeds.py, never the product's): the activation through the
-// correctly-rounded-to-an-ulp library functions instead of the hardware exp2 / log2 units.
-#ifdef RECMV_LIBM_SOFTPLUS
-#define RECMV_EXPF(x) expf(x)
-#define RECMV_LOG1PF(t) log1pf(t)
-#else
-#define RECMV_EXPF(x) __expf(x)
-#define RECMV_LOG1PF(t) __logf(1.f + (t))
-#endif
+#include "activation.h"
 
 namespace recmv {
 using route::BM;      // large NT tile and the TN kernels' tile

@@ -36,41 +36,8 @@ namespace {
 
 constexpr int LDK = BK + 4;    // NT: padded k stride (floats) of an LDS row
 
-// Activations of the fused epilogue.  ACT is a compile-time constant inside the epilogue loops.
-//   softplus(beta): torch semantics (x*beta > 20 ? x : log1p(exp(x*beta))/beta), evaluated as
-//   (max(zb,0) + log1p(exp(-|zb|))) / beta with the hardware exp2/log2 units: exp(-|zb|) = t in (0,1];
-//   log1p(t) by its alternating series below 2^-6 (keeps the relative accuracy of tiny outputs, which the
-//   backward recovers sigmoid(zb) = 1 - exp(-beta*y) from) and log(1+t) above.  |error| < 2e-7/beta.
-template <int ACT>
-__device__ __forceinline__ float apply_act(float z, float p, float inv_p) {
-  if (ACT == RECMV_ACT_RELU) return z > 0.f ? z : 0.f;
-  if (ACT == RECMV_ACT_SOFTPLUS) {
-    const float zb = z * p;
-    const float t = RECMV_EXPF(-fabsf(zb));
-    const float series = t * (1.f - t * (0.5f - t * (0.33333334f - 0.25f * t)));
-    const float l = t < 0.015625f ? series : RECMV_LOG1PF(t);
-    const float y = (fmaxf(zb, 0.f) + l) * inv_p;
-    return zb > 20.f ? z : y;
-  }
-  if (ACT == RECMV_ACT_TANH) return tanhf(z);
-  return z;
-}
-
-// act'(z) expressed through y = act(z) (elementwise.hip has the same formulas)
-__device__ __forceinline__ float dact_y(float y, int act, float p) {
-  switch (act) {
-    case RECMV_ACT_RELU: return y > 0.f ? 1.f : 0.f;
-    case RECMV_ACT_SOFTPLUS: {
-      // sigmoid(beta z) = 1 - exp(-beta y).  This runs on the operand-staging path of an MFMA kernel, so it uses
-      // the hardware exp2 unit; below t = 1/64 the alternating series keeps the relative accuracy expm1 would give.
-      const float t = p * y;
-      const float series = t * (1.f - t * (0.5f - t * (0.16666667f - 0.041666668f * t)));
-      return t < 0.015625f ? series : 1.f - RECMV_EXPF(-t);
-    }
-    case RECMV_ACT_TANH: return 1.f - y * y;
-    default: return 1.f;
-  }
-}
+// The activations of the fused epilogue (apply_act<ACT>) and act'(z) through y = act(z) on the staging and epilogue paths (dact_hw):
+// activation.h.  elementwise.hip and mlp_chain.hip use another form of that derivative (dact_libm); the two agree to rounding.
 
 // Optional transform of the A operand while it is staged: A_eff = A (.) act'(y_scale * Y) * a_scale — the
 // dZ = dY (.) act'(Z) step of a layer's backward fused into the dX = dZ W product (no dZ round trip through HBM).
@@ -87,10 +54,10 @@ struct AMul {
 };
 
 __device__ __forceinline__ float4 amul4(float4 a, float4 y, const AMul& m) {
-  a.x *= dact_y(y.x * m.y_scale, m.act, m.param) * m.a_scale;
-  a.y *= dact_y(y.y * m.y_scale, m.act, m.param) * m.a_scale;
-  a.z *= dact_y(y.z * m.y_scale, m.act, m.param) * m.a_scale;
-  a.w *= dact_y(y.w * m.y_scale, m.act, m.param) * m.a_scale;
+  a.x *= dact_hw(y.x * m.y_scale, m.act, m.param) * m.a_scale;
+  a.y *= dact_hw(y.y * m.y_scale, m.act, m.param) * m.a_scale;
+  a.z *= dact_hw(y.z * m.y_scale, m.act, m.param) * m.a_scale;
+  a.w *= dact_hw(y.w * m.y_scale, m.act, m.param) * m.a_scale;
   return a;
 }
 
@@ -119,11 +86,20 @@ __device__ __forceinline__ float4 emul4(float4 v, const AMul& m, int gm, int gn,
     if (gn + 2 < N) yv.z = y[2];
     if (gn + 3 < N) yv.w = y[3];
   }
-  v.x *= dact_y(yv.x * m.y_scale, m.act, m.param) * m.a_scale;
-  v.y *= dact_y(yv.y * m.y_scale, m.act, m.param) * m.a_scale;
-  v.z *= dact_y(yv.z * m.y_scale, m.act, m.param) * m.a_scale;
-  v.w *= dact_y(yv.w * m.y_scale, m.act, m.param) * m.a_scale;
+  v.x *= dact_hw(yv.x * m.y_scale, m.act, m.param) * m.a_scale;
+  v.y *= dact_hw(yv.y * m.y_scale, m.act, m.param) * m.a_scale;
+  v.z *= dact_hw(yv.z * m.y_scale, m.act, m.param) * m.a_scale;
+  v.w *= dact_hw(yv.w * m.y_scale, m.act, m.param) * m.a_scale;
   return v;
+}
+
+// Row-segmented weights (see AMul): the tiles whose first row m0 is >= split take the second weight set.  split is a multiple of every
+// tile height (128) or M, so the choice is uniform over a workgroup.
+__device__ __forceinline__ void seg_operands(const AMul& am, int m0, const float* __restrict__& B, const float* __restrict__& bias) {
+  if (am.B2 && m0 >= am.split) {
+    B = am.B2;
+    bias = am.bias2;
+  }
 }
 
 template <int TBM, int TBN, int ACT>
@@ -193,10 +169,7 @@ __global__ __launch_bounds__(kBlk) void gemm_nt_kernel(const float* __restrict__
   const int64_t logical = xcd_remap(blockIdx.x, (int64_t)nbm * nbn);
   const int tile_m = (int)(logical / nbn), tile_n = (int)(logical % nbn);
   const int m0 = tile_m * TBM, n0 = tile_n * TBN;
-  if (am.B2 && m0 >= am.split) {              // second weight set for the rows of the second net (see AMul)
-    B = am.B2;
-    bias = am.bias2;
-  }
+  seg_operands(am, m0, B, bias);
 
   f32x16 acc[T][T];
 #pragma unroll
@@ -373,10 +346,7 @@ void gemm_nt_occ_kernel(const float* __restrict__ A, int64_t lda, const float* _
   const int64_t logical = xcd_remap(blockIdx.x, (int64_t)nbm * nbn);
   const int tile_m = (int)(logical / nbn), tile_n = (int)(logical % nbn);
   const int m0 = tile_m * TBM, n0 = tile_n * TBN;
-  if (am.B2 && m0 >= am.split) {
-    B = am.B2;
-    bias = am.bias2;
-  }
+  seg_operands(am, m0, B, bias);
   f32x16 acc[MI][NI];
 #pragma unroll
   for (int a = 0; a < MI; ++a)
@@ -553,10 +523,7 @@ __global__ __launch_bounds__(kThinRows) void gemm_nt_thin_n_kernel(const float* 
   __shared__ __attribute__((aligned(16))) float Bs[4 * LDK];
   const int tid = threadIdx.x;
   const int m0 = blockIdx.x * kThinRows;
-  if (am.B2 && m0 >= am.split) {              // second weight set for the rows of the second net (see AMul)
-    B = am.B2;
-    bias = am.bias2;
-  }
+  seg_operands(am, m0, B, bias);
   constexpr int NLD = kThinRows * 8 / kThinRows;   // float4 per thread and K-tile
   float4 ra[NLD];
   float rb;
@@ -630,7 +597,7 @@ __global__ __launch_bounds__(kThinRows) void gemm_nt_thin_n_kernel(const float* 
   for (int n = 0; n < NN; ++n) {
     const float z = halves ? acc[0][n] + acc[1][n] : acc[0][n];
     float v = apply_act_rt(z + (bias ? bias[n] : 0.f), act, act_param, inv_p) * out_scale;
-    if (am.Y) v *= dact_y(am.Y[(int64_t)gm * am.ldy + n] * am.y_scale, am.act, am.param) * am.a_scale;
+    if (am.Y) v *= dact_hw(am.Y[(int64_t)gm * am.ldy + n] * am.y_scale, am.act, am.param) * am.a_scale;
     C[(int64_t)gm * ldc + n] = v;
   }
 }
@@ -649,7 +616,7 @@ __global__ __launch_bounds__(kBlk) void gemm_nt_thin_k_kernel(const float* __res
   const int cw = 1 << cw_log2, cl = tid & (cw - 1), rsub = tid >> cw_log2, rstep = kBlk >> cw_log2;
   const int m0 = blockIdx.x * kThinKRows;
   const int mend = m0 + kThinKRows < M ? m0 + kThinKRows : M;
-  if (am.B2 && m0 >= am.split) {              // split is a multiple of 128 (or M): uniform over the 32 rows of a workgroup
+  if (am.B2 && m0 >= am.split) {              // (written out: through seg_operands this kernel's instructions come out differently)
     B = am.B2;
     bias = am.bias2;
   }
@@ -668,7 +635,7 @@ __global__ __launch_bounds__(kBlk) void gemm_nt_thin_k_kernel(const float* __res
 #pragma unroll
       for (int k = 0; k < KK; ++k) {
         a[k] = A[(int64_t)gm * lda + k];
-        if (AMUL) a[k] *= dact_y(am.Y[(int64_t)gm * am.ldy + k] * am.y_scale, am.act, am.param) * am.a_scale;
+        if (AMUL) a[k] *= dact_hw(am.Y[(int64_t)gm * am.ldy + k] * am.y_scale, am.act, am.param) * am.a_scale;
       }
       float o[4];
 #pragma unroll
@@ -1023,10 +990,7 @@ __global__ __launch_bounds__(kBlk) void gemm_nt_narrow_kernel(const float* __res
   const int64_t logical = xcd_remap(blockIdx.x, (int64_t)nbm * nbn);
   const int tile_m = (int)(logical / nbn), tile_n = (int)(logical % nbn);
   const int m0 = tile_m * TBM, n0 = tile_n * TBN;
-  if (am.B2 && m0 >= am.split) {              // second weight set for the rows of the second net (see AMul)
-    B = am.B2;
-    bias = am.bias2;
-  }
+  seg_operands(am, m0, B, bias);
 
   f32x16 acc;
 #pragma unroll

@@ -7,6 +7,8 @@
 //   gx = gz W      = gz (W^T)^T            MFMA gemm_nt against the cached W^T
 //   gW = gz^T x                            MFMA gemm_tn (split-K over the points, fixed reduction order)
 #include "common.h"
+#include "activation.h"
+#include "mlp_desc.h"
 
 namespace recmv {
 namespace {
@@ -39,15 +41,6 @@ __global__ __launch_bounds__(kBlk) void colsum_partial_kernel(const float* __res
   }
 }
 
-__device__ __forceinline__ float dact_y(float y, int act, float p) {
-  switch (act) {
-    case RECMV_ACT_RELU: return y > 0.f ? 1.f : 0.f;
-    case RECMV_ACT_SOFTPLUS: return -expm1f(-p * y);
-    case RECMV_ACT_TANH: return 1.f - y * y;
-    default: return 1.f;
-  }
-}
-
 // gz[r,c] = gy[r,c] * act'(z) (through y = act(z)), written out, AND partial[chunk][c] = column sums of gz over the
 // chunk's rows: the bias gradient comes out of the same pass over dY that produces dZ.
 // VEC = 4: 16-byte accesses (16 threads span the 64-column tile, 16 rows in flight per block pass); VEC = 1: scalar.
@@ -75,17 +68,17 @@ __global__ __launch_bounds__(kBlk) void act_grad_colsum_kernel(const float* __re
         const float4 g4 = *reinterpret_cast<const float4*>(gy + r * ldg + c);
         const float4 y4 = *reinterpret_cast<const float4*>(y + r * ldy + c);
         float4 o;
-        o.x = g4.x * dact_y(y4.x, act, p);
-        o.y = g4.y * dact_y(y4.y, act, p);
-        o.z = g4.z * dact_y(y4.z, act, p);
-        o.w = g4.w * dact_y(y4.w, act, p);
+        o.x = g4.x * dact_libm(y4.x, act, p);
+        o.y = g4.y * dact_libm(y4.y, act, p);
+        o.z = g4.z * dact_libm(y4.z, act, p);
+        o.w = g4.w * dact_libm(y4.w, act, p);
         *reinterpret_cast<float4*>(gz + r * ldz + c) = o;
         s[0] += o.x;
         s[VEC > 1 ? 1 : 0] += o.y;
         s[VEC > 2 ? 2 : 0] += o.z;
         s[VEC > 3 ? 3 : 0] += o.w;
       } else {
-        const float v = gy[r * ldg + c] * dact_y(y[r * ldy + c], act, p);
+        const float v = gy[r * ldg + c] * dact_libm(y[r * ldy + c], act, p);
         gz[r * ldz + c] = v;
         s[0] += v;
       }
@@ -130,8 +123,6 @@ inline int colsum_chunks(int64_t rows) {
   return (int)ch;
 }
 
-inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 }  // namespace recmv
 
@@ -170,8 +161,11 @@ extern "C" int recmv_colsum(const float* g, int64_t ld, int64_t rows, int64_t co
 
 extern "C" int64_t recmv_linear_backward_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   if (M <= 0 || N <= 0) return 256;
-  return align256(M * ((N + 3) & ~3ll) * 4) + align256(recmv_gemm_tn_workspace_bytes(N, K, M)) +
-         align256(recmv_colsum_workspace_bytes(M, N)) + 256;
+  Carve c;     // dZ [M, N padded to 4] | the dW product's | the column sums' | 256 spare bytes, as recmv_linear_backward takes them
+  c.take(M * align_up(N, 4) * 4);
+  c.take(recmv_gemm_tn_workspace_bytes(N, K, M));
+  c.take(recmv_colsum_workspace_bytes(M, N));
+  return c.o + 256;
 }
 
 // y, gy: [M,N] (outputs of the layer and their cotangent); x: [M,K]; Wt: [K,N] = W^T.
@@ -195,12 +189,13 @@ extern "C" int recmv_linear_backward(const float* gy, int64_t ldgy, const float*
     return RECMV_ERR_WORKSPACE;
   }
   char* ws = (char*)workspace;
-  float* gzbuf = (float*)ws;
-  const int64_t ldz = (N + 3) & ~3ll;     // dZ rows padded to whole float4s: the dW product then takes its aligned path for N = 473
-  char* tn_ws = ws + align256(M * ldz * 4);
-  const int64_t tn_bytes = align256(recmv_gemm_tn_workspace_bytes(N, K, M));
-  char* cs_ws = tn_ws + tn_bytes;
-  const int64_t cs_bytes = align256(recmv_colsum_workspace_bytes(M, N));
+  Carve c;
+  const int64_t ldz = align_up(N, 4);     // dZ rows padded to whole float4s: the dW product then takes its aligned path for N = 473
+  float* gzbuf = (float*)(ws + c.take(M * ldz * 4));
+  const int64_t tn_bytes = align_up(recmv_gemm_tn_workspace_bytes(N, K, M), 256);
+  char* tn_ws = ws + c.take(tn_bytes);
+  const int64_t cs_bytes = align_up(recmv_colsum_workspace_bytes(M, N), 256);
+  char* cs_ws = ws + c.take(cs_bytes);
   const float* gz = gy;
   int64_t ldgz = ldgy;
   int rc;

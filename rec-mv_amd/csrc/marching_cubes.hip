@@ -36,6 +36,7 @@
 //
 // Algorithmic bytes: 4*NX*NY*NZ (volume read once) + 12*V + 24*F.
 #include "common.h"
+#include "mlp_desc.h"
 #include "mc_tables.inc"
 
 namespace recmv {
@@ -88,19 +89,14 @@ inline void make_layout(int64_t nx, int64_t ny, int64_t nz, McLayout* L) {
   L->nword = ceil_div(L->nvox, 64);
   L->nchunk = ceil_div(L->nseg > 0 ? L->nseg : 1, kScanChunk);
   L->npart = L->nchunk * kScanPer;
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) {
-    int64_t r = o;
-    o += (bytes + 255) / 256 * 256;
-    return r;
-  };
-  L->off_bits = take((L->nword + 2) * 8);
-  L->off_cnt = take(L->nchunk * kScanChunk * 4);
-  L->off_part = take(3 * L->npart * 4);
-  L->off_rec = take(L->nseg * (int64_t)sizeof(McRec));
-  L->off_act = take(L->nseg * 64 * 4);
-  L->off_total = take(16);
-  L->bytes = o;
+  Carve c;
+  L->off_bits = c.take((L->nword + 2) * 8);
+  L->off_cnt = c.take(L->nchunk * kScanChunk * 4);
+  L->off_part = c.take(3 * L->npart * 4);
+  L->off_rec = c.take(L->nseg * (int64_t)sizeof(McRec));
+  L->off_act = c.take(L->nseg * 64 * 4);
+  L->off_total = c.take(16);
+  L->bytes = c.o;
 }
 
 #pragma clang fp contract(off)

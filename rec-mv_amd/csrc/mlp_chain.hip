@@ -13,22 +13,13 @@
 //
 // Activations live in a caller-provided workspace (recmv_mlp_workspace_bytes); nothing is allocated here.
 #include "common.h"
+#include "activation.h"
+#include "mlp_desc.h"
 
 namespace recmv {
 namespace {
 
 constexpr int kBlk = 256;
-constexpr float kInvSqrt2 = 0.70710678118654752440f;
-constexpr float kSqrt2 = 1.41421356237309504880f;
-
-__device__ __forceinline__ float dact(float y, int act, float p) {
-  switch (act) {
-    case RECMV_ACT_RELU: return y > 0.f ? 1.f : 0.f;
-    case RECMV_ACT_SOFTPLUS: return -expm1f(-p * y);
-    case RECMV_ACT_TANH: return 1.f - y * y;
-    default: return 1.f;
-  }
-}
 
 // out[r,c] = out_scale * gy[r*ldg + c] * act'(z) with y = act(z) = y_scale * ybuf[r*ldy + c]   (ldg may be 0:
 // one cotangent row broadcast to every point)
@@ -41,7 +32,7 @@ __global__ __launch_bounds__(kBlk) void act_grad_2d_kernel(const float* __restri
   for (int64_t e = (int64_t)blockIdx.x * kBlk + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlk) {
     const int64_t r = e / cols;
     const int c = (int)(e - r * cols);
-    out[r * ldo + c] = out_scale * gy[r * ldg + c] * dact(y[r * ldy + c] * y_scale, act, p);
+    out[r * ldo + c] = out_scale * gy[r * ldg + c] * dact_libm(y[r * ldy + c] * y_scale, act, p);
   }
 }
 
@@ -58,10 +49,10 @@ __global__ __launch_bounds__(kBlk) void act_grad_2d_vec4_kernel(const float* __r
     const float4 g = *reinterpret_cast<const float4*>(gy + r * ldg + c);
     const float4 v = *reinterpret_cast<const float4*>(y + r * ldy + c);
     float4 o;
-    o.x = out_scale * g.x * dact(v.x * y_scale, act, p);
-    o.y = out_scale * g.y * dact(v.y * y_scale, act, p);
-    o.z = out_scale * g.z * dact(v.z * y_scale, act, p);
-    o.w = out_scale * g.w * dact(v.w * y_scale, act, p);
+    o.x = out_scale * g.x * dact_libm(v.x * y_scale, act, p);
+    o.y = out_scale * g.y * dact_libm(v.y * y_scale, act, p);
+    o.z = out_scale * g.z * dact_libm(v.z * y_scale, act, p);
+    o.w = out_scale * g.w * dact_libm(v.w * y_scale, act, p);
     *reinterpret_cast<float4*>(out + r * ldo + c) = o;
   }
 }
@@ -92,8 +83,6 @@ __global__ __launch_bounds__(kBlk) void gather_rows_kernel(const float* __restri
   }
 }
 
-inline int64_t pad4(int64_t v) { return (v + 3) / 4 * 4; }
-
 struct Layout {
   int64_t ld_in;          // row stride of the input buffer
   int64_t ld_act;         // row stride of every activation / gradient buffer
@@ -105,58 +94,28 @@ Layout make_layout(const recmv_mlp* m, int64_t P, int keep) {
   Layout L;
   int64_t maxw = 4;
   for (int l = 0; l <= m->n_layers; ++l) maxw = m->dims[l] > maxw ? m->dims[l] : maxw;
-  L.ld_in = pad4(m->dims[0]);
-  L.ld_act = pad4(maxw);
-  int64_t o = 0;
-  auto take = [&](int64_t floats) {
-    int64_t r = o;
-    o += (floats * 4 + 255) / 256 * 256;
-    return r;
-  };
-  L.off_in = take(P * L.ld_in);
+  L.ld_in = align_up(m->dims[0], 4);
+  L.ld_act = align_up(maxw, 4);
+  Carve c;
+  L.off_in = c.take(P * L.ld_in * 4);
   const int nact = m->n_layers - 1;
-  for (int l = 0; l < nact; ++l) L.off_act[l] = (keep || l < 2) ? take(P * L.ld_act) : L.off_act[l & 1];
-  L.off_g[0] = keep ? take(P * L.ld_act) : 0;
-  L.off_g[1] = keep ? take(P * L.ld_act) : 0;
-  L.off_g[2] = keep ? take(P * L.ld_act) : 0;      // dZ of the layer being differentiated
-  L.bytes = o;
+  for (int l = 0; l < nact; ++l) L.off_act[l] = (keep || l < 2) ? c.take(P * L.ld_act * 4) : L.off_act[l & 1];
+  L.off_g[0] = keep ? c.take(P * L.ld_act * 4) : 0;
+  L.off_g[1] = keep ? c.take(P * L.ld_act * 4) : 0;
+  L.off_g[2] = keep ? c.take(P * L.ld_act * 4) : 0;      // dZ of the layer being differentiated
+  L.bytes = c.o;
   return L;
-}
-
-int check_desc(const recmv_mlp* m) {
-  RECMV_REQUIRE(m, "mlp: NULL descriptor");
-  RECMV_REQUIRE(m->n_layers >= 1 && m->n_layers <= RECMV_MLP_MAX_LAYERS, "mlp: bad layer count %d", m->n_layers);
-  RECMV_REQUIRE(m->multires >= 0 && m->multires <= 16 && m->cond_dim >= 0, "mlp: bad encoding");
-  RECMV_REQUIRE(m->dims[0] == 3 + 6 * m->multires + m->cond_dim, "mlp: dims[0] != 3+6L+cond_dim");
-  for (int l = 0; l < m->n_layers; ++l) {
-    RECMV_REQUIRE(m->W[l] && m->rows[l] > 0 && m->dims[l] > 0, "mlp: layer %d incomplete", l);
-    const int expect = (l + 1 == m->skip_layer) ? m->dims[l + 1] - (3 + 6 * m->multires) : m->dims[l + 1];
-    RECMV_REQUIRE(m->rows[l] == expect, "mlp: layer %d has %d rows, expected %d", l, m->rows[l], expect);
-  }
-  RECMV_REQUIRE(m->skip_layer < m->n_layers, "mlp: bad skip layer");
-  if (m->split_row > 0 && m->W2[0]) {
-    RECMV_REQUIRE(m->split_row % 128 == 0, "mlp: split_row %lld is not a multiple of 128", (long long)m->split_row);
-    for (int l = 0; l < m->n_layers; ++l)
-      RECMV_REQUIRE(m->W2[l] && (!m->bias[l] == !m->bias2[l]), "mlp: the second net's layer %d is incomplete", l);
-  }
-  return RECMV_OK;
 }
 
 // rows [split, P) of this call belong to the second net (0: there is none)
 inline int64_t second_net_from(const recmv_mlp* m, int64_t P) {
-  return (m->split_row > 0 && m->W2[0] && m->split_row < P) ? m->split_row : 0;
+  return (mlp_has_second(m) && m->split_row < P) ? m->split_row : 0;
 }
 
 }  // namespace
 }  // namespace recmv
 
 using namespace recmv;
-
-#define RECMV_TRY(expr)            \
-  do {                             \
-    int rc__ = (expr);             \
-    if (rc__ != RECMV_OK) return rc__; \
-  } while (0)
 
 extern "C" int recmv_act_grad_2d(const float* gy, int64_t ldg, const float* y, int64_t ldy, float* out, int64_t ldo,
                                  int64_t rows, int64_t cols, int act, float act_param, float y_scale,
@@ -198,14 +157,14 @@ extern "C" int recmv_gather_rows(const float* table, int64_t ldt, const int64_t*
 }
 
 extern "C" int64_t recmv_mlp_workspace_bytes(const recmv_mlp* m, int64_t P, int keep) {
-  if (!m || P <= 0 || m->n_layers < 1 || m->n_layers > RECMV_MLP_MAX_LAYERS) return 0;
+  if (mlp_validate(m, "mlp_workspace_bytes") != RECMV_OK || P <= 0) return 0;
   return make_layout(m, P, keep).bytes;
 }
 
 extern "C" int recmv_mlp_forward(const recmv_mlp* m, const float* x, const float* cond, int64_t ld_cond,
                                  const int64_t* cond_index, int64_t P, int n_out, float* out, int64_t ldo,
                                  void* workspace, int64_t workspace_bytes, int keep, void* stream) {
-  RECMV_TRY(check_desc(m));
+  RECMV_TRY(mlp_validate(m, "mlp_forward"));
   RECMV_REQUIRE(P >= 0, "mlp_forward: negative P");
   if (P == 0) return RECMV_OK;
   const int n = m->n_layers;
@@ -220,7 +179,7 @@ extern "C" int recmv_mlp_forward(const recmv_mlp* m, const float* x, const float
   }
   float* base = (float*)workspace;
   float* in = base + L.off_in / 4;
-  const int d_pe = 3 + 6 * m->multires;
+  const int d_pe = mlp_d_pe(m);
   // input = [gamma(x) | code[frame] | zero pad]
   RECMV_TRY(recmv_posenc_forward(x, 3, in, L.ld_in, m->cond_dim ? d_pe : (int)L.ld_in, P, m->multires, m->pe_weights,
                                  1.f, stream));
@@ -258,7 +217,7 @@ extern "C" int recmv_mlp_forward(const recmv_mlp* m, const float* x, const float
 
 extern "C" int recmv_mlp_vjp_input(const recmv_mlp* m, const float* x, int64_t P, int n_out, const float* g_out,
                                    int64_t ldg, float* gx, void* workspace, int64_t workspace_bytes, void* stream) {
-  RECMV_TRY(check_desc(m));
+  RECMV_TRY(mlp_validate(m, "mlp_vjp_input"));
   RECMV_REQUIRE(P >= 0, "mlp_vjp_input: negative P");
   if (P == 0) return RECMV_OK;
   const int n = m->n_layers;
@@ -277,7 +236,7 @@ extern "C" int recmv_mlp_vjp_input(const recmv_mlp* m, const float* x, int64_t P
   }
   float* base = (float*)workspace;
   float* gbuf[2] = {base + L.off_g[0] / 4, base + L.off_g[1] / 4};
-  const int d_pe = 3 + 6 * m->multires;
+  const int d_pe = mlp_d_pe(m);
   // g = cotangent of the last layer's output -> gradient wrt its input
   const float* g;      // gradient wrt the OUTPUT of layer l-1 (= input of layer l), [P, dims[l]]
   int64_t ld;

@@ -19,55 +19,13 @@
 //
 // down to the encoding (second-derivative kernel of gamma for the tangent rows).  Two C calls per term.
 #include "common.h"
+#include "activation.h"
+#include "mlp_desc.h"
 
 namespace recmv {
 namespace {
 
 constexpr int kBlk = 256;
-constexpr float kInvSqrt2 = 0.70710678118654752440f;
-
-struct ActD {
-  float f, d1, d2;
-};
-
-// phi, phi', phi'' at z.  Softplus follows torch (threshold 20 on beta*z).
-__device__ __forceinline__ ActD act_jet(float z, int act, float p) {
-  ActD r;
-  switch (act) {
-    case RECMV_ACT_RELU:
-      r.f = z > 0.f ? z : 0.f;
-      r.d1 = z > 0.f ? 1.f : 0.f;
-      r.d2 = 0.f;
-      break;
-    case RECMV_ACT_SOFTPLUS: {
-      const float zb = z * p;
-      if (zb > 20.f) {
-        r.f = z;
-        r.d1 = 1.f;
-        r.d2 = 0.f;
-      } else {
-        const float e = expf(-fabsf(zb));                  // in (0,1]
-        const float sig = zb >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-        r.f = (fmaxf(zb, 0.f) + log1pf(e)) / p;
-        r.d1 = sig;
-        r.d2 = p * sig * (1.f - sig);
-      }
-      break;
-    }
-    case RECMV_ACT_TANH: {
-      const float t = tanhf(z);
-      r.f = t;
-      r.d1 = 1.f - t * t;
-      r.d2 = -2.f * t * r.d1;
-      break;
-    }
-    default:
-      r.f = z;
-      r.d1 = 1.f;
-      r.d2 = 0.f;
-  }
-  return r;
-}
 
 // Z: [4P, ldz] pre-activations (value rows WITHOUT bias on entry; the biased z is written back), Y: [4P, ldy].
 __global__ __launch_bounds__(kBlk) void jet_act_forward_kernel(float* __restrict__ Z, int64_t ldz,
@@ -110,8 +68,6 @@ __global__ __launch_bounds__(kBlk) void jet_act_backward_kernel(const float* Yba
   }
 }
 
-inline int64_t pad4(int64_t v) { return (v + 3) / 4 * 4; }
-
 struct JetLayout {
   int64_t R, ld_in, ld_act;
   int64_t off_in, off_z[RECMV_MLP_MAX_LAYERS], off_h[RECMV_MLP_MAX_LAYERS], off_ga, off_gb, off_park, off_tn;
@@ -123,41 +79,31 @@ JetLayout jet_layout(const recmv_mlp* m, int64_t P) {
   int64_t maxw = 4;
   for (int l = 0; l <= m->n_layers; ++l) maxw = m->dims[l] > maxw ? m->dims[l] : maxw;
   L.R = 4 * P;
-  L.ld_in = pad4(m->dims[0]);
-  L.ld_act = pad4(maxw);
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) {
-    int64_t r = o;
-    o += (bytes + 255) / 256 * 256;
-    return r;
-  };
-  L.off_in = take(L.R * L.ld_in * 4);
+  L.ld_in = align_up(m->dims[0], 4);
+  L.ld_act = align_up(maxw, 4);
+  Carve c;
+  L.off_in = c.take(L.R * L.ld_in * 4);
   for (int l = 0; l + 1 < m->n_layers; ++l) {
-    L.off_z[l] = take(L.R * L.ld_act * 4);
-    L.off_h[l] = take(L.R * L.ld_act * 4);
+    L.off_z[l] = c.take(L.R * L.ld_act * 4);
+    L.off_h[l] = c.take(L.R * L.ld_act * 4);
   }
   // the reverse sweep also forms the [n_j, dims[n-1]] product gtang^T T of the last layer in the first of the two cotangent buffers:
   // with fewer than rows_last / 4 points the 4P rows of a cotangent block would not hold it
   const int64_t ga_rows = L.R > m->rows[m->n_layers - 1] ? L.R : m->rows[m->n_layers - 1];
-  L.off_ga = take(ga_rows * L.ld_act * 4);
-  L.off_gb = take(L.R * L.ld_act * 4);
-  L.off_park = take(L.R * L.ld_in * 4);
-  L.tn_bytes = (recmv_gemm_tn_workspace_bytes(L.ld_act, L.ld_act, L.R) + 255) / 256 * 256 +
+  L.off_ga = c.take(ga_rows * L.ld_act * 4);
+  L.off_gb = c.take(L.R * L.ld_act * 4);
+  L.off_park = c.take(L.R * L.ld_in * 4);
+  L.tn_bytes = align_up(recmv_gemm_tn_workspace_bytes(L.ld_act, L.ld_act, L.R), 256) +
                recmv_colsum_workspace_bytes(P, L.ld_act) + 512;
-  L.off_tn = take(L.tn_bytes);
-  L.bytes = o;
+  L.off_tn = c.take(L.tn_bytes);
+  L.bytes = c.o;
   return L;
 }
 
-int jet_check(const recmv_mlp* m) {
-  RECMV_REQUIRE(m, "mlp_jet: NULL descriptor");
-  RECMV_REQUIRE(m->n_layers >= 1 && m->n_layers <= RECMV_MLP_MAX_LAYERS, "mlp_jet: bad layer count");
-  RECMV_REQUIRE(m->dims[0] == 3 + 6 * m->multires + m->cond_dim, "mlp_jet: dims[0] != 3+6L+cond_dim");
-  for (int l = 0; l < m->n_layers; ++l) {
-    RECMV_REQUIRE(m->W[l] && m->rows[l] > 0, "mlp_jet: layer %d incomplete", l);
-    const int expect = (l + 1 == m->skip_layer) ? m->dims[l + 1] - (3 + 6 * m->multires) : m->dims[l + 1];
-    RECMV_REQUIRE(m->rows[l] == expect, "mlp_jet: layer %d has %d rows, expected %d", l, m->rows[l], expect);
-  }
+// the jet evaluates ONE net: a descriptor with a second weight set is refused, not evaluated with the first net on every row
+int jet_check(const recmv_mlp* m, const char* who) {
+  RECMV_TRY(mlp_validate(m, who));
+  RECMV_REQUIRE(!mlp_has_second(m), "%s: the jet pass takes one net, this descriptor carries a second weight set", who);
   return RECMV_OK;
 }
 
@@ -188,12 +134,6 @@ inline bool jet_fill_kernel() {
 
 using namespace recmv;
 
-#define RECMV_TRY(expr)                \
-  do {                                 \
-    int rc__ = (expr);                 \
-    if (rc__ != RECMV_OK) return rc__; \
-  } while (0)
-
 extern "C" int recmv_set_jet_fill(int use_kernel) {
   const int prev = jet_fill_kernel() ? 1 : 0;
   g_jet_fill = use_kernel ? 1 : 0;
@@ -201,7 +141,7 @@ extern "C" int recmv_set_jet_fill(int use_kernel) {
 }
 
 extern "C" int64_t recmv_mlp_jet_workspace_bytes(const recmv_mlp* m, int64_t P) {
-  if (!m || P <= 0 || m->n_layers < 1 || m->n_layers > RECMV_MLP_MAX_LAYERS) return 0;
+  if (mlp_validate(m, "mlp_jet_workspace_bytes") != RECMV_OK || P <= 0) return 0;
   return jet_layout(m, P).bytes;
 }
 
@@ -209,7 +149,7 @@ extern "C" int recmv_mlp_jet_forward(const recmv_mlp* m, const float* x, const f
                                      const int64_t* cond_index, const float* eye3, int64_t P, int n_j, float* y,
                                      int64_t ldy, float* tang, void* workspace, int64_t workspace_bytes,
                                      void* stream) {
-  RECMV_TRY(jet_check(m));
+  RECMV_TRY(jet_check(m, "mlp_jet_forward"));
   RECMV_REQUIRE(P >= 0, "mlp_jet_forward: negative P");
   if (P == 0) return RECMV_OK;
   const int n = m->n_layers;
@@ -226,7 +166,7 @@ extern "C" int recmv_mlp_jet_forward(const recmv_mlp* m, const float* x, const f
   hipStream_t s = (hipStream_t)stream;
   char* base = (char*)workspace;
   float* in = (float*)(base + L.off_in);
-  const int d_pe = 3 + 6 * m->multires;
+  const int d_pe = mlp_d_pe(m);
   // value rows: [gamma(x) | code[frame] | 0]; tangent rows k: [d gamma / d x_k | 0]
   RECMV_TRY(recmv_posenc_forward(x, 3, in, L.ld_in, m->cond_dim ? d_pe : (int)L.ld_in, P, m->multires, m->pe_weights,
                                  1.f, stream));
@@ -278,7 +218,7 @@ extern "C" int recmv_mlp_jet_backward(const recmv_mlp* m, const float* x, const 
                                       const float* gy, int64_t ldgy, const float* gtang, float* const* gW,
                                       float* const* gb, float* g_in, float* gx, void* workspace,
                                       int64_t workspace_bytes, void* stream) {
-  RECMV_TRY(jet_check(m));
+  RECMV_TRY(jet_check(m, "mlp_jet_backward"));
   RECMV_REQUIRE(P >= 0, "mlp_jet_backward: negative P");
   if (P == 0) return RECMV_OK;
   const int n = m->n_layers;
@@ -300,7 +240,7 @@ extern "C" int recmv_mlp_jet_backward(const recmv_mlp* m, const float* x, const 
   const int64_t cs_bytes = recmv_colsum_workspace_bytes(P, L.ld_act) + 256;
   char* csws = tnws + (L.tn_bytes - cs_bytes);
   const int64_t tn_bytes = L.tn_bytes - cs_bytes;
-  const int d_pe = 3 + 6 * m->multires;
+  const int d_pe = mlp_d_pe(m);
   bool parked = false;
   int cur = 0;
   // ---- last layer (no activation)

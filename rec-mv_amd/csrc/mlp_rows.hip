@@ -23,16 +23,8 @@
 // over a pass), which is why this form is for the few-thousand-row passes only; recmv_mlp_forward keeps the per-layer kernels
 // above RECMV_MLP_ROWS_MAX rows.
 #include "common.h"
-// RECMV_LIBM_SOFTPLUS (an experiment build of tools/trajectory_seeds.py, never the product's): the activation through the
-// correctly-rounded-to-an-ulp library functions instead of the hardware exp2 / log2 units.
-#ifdef RECMV_LIBM_SOFTPLUS
-#define RECMV_EXPF(x) expf(x)
-#define RECMV_LOG1PF(t) log1pf(t)
-#else
-#define RECMV_EXPF(x) __expf(x)
-#define RECMV_LOG1PF(t) __logf(1.f + (t))
-#endif
-
+#include "activation.h"
+#include "mlp_desc.h"
 
 namespace recmv {
 namespace {
@@ -44,8 +36,6 @@ constexpr int kThreads = 64 * kWaves;  // each wave owns an eighth of a layer's 
 constexpr int kLD = 520;               // LDS row stride in floats (= 8 mod 64, >= 512 + 8)
 constexpr int kMaxWidth = 512;
 constexpr int kPeLD = 52;              // gamma(x) rows kept for the skip connection (3 + 6 * 8 = 51 max)
-constexpr float kInvSqrt2 = 0.70710678118654752440f;
-constexpr float kSqrt2 = 1.41421356237309504880f;
 
 // -DRECMV_ROWS_TIMING: thread 0 of workgroup 0 stamps the 100 MHz wall clock at the phase boundaries of a pass (read back
 // through recmv_debug_rows_clock, tools/mlp_rows_clock.py).  Not part of the shipped build.
@@ -83,49 +73,7 @@ struct RowsArgs {
   float pe_w[32];
 };
 
-// Softplus is the hot activation (SDF net, offset MLP): straight-line code, both branches of the small-t split evaluated and
-// selected, so that the epilogue of a tile is one basic block.  The formulas are those of gemm_f32.hip's epilogue.
-__device__ __forceinline__ float softplus_fwd(float z, float p, float inv_p) {
-  const float zb = z * p;
-  const float t = RECMV_EXPF(-fabsf(zb));
-  const float series = t * (1.f - t * (0.5f - t * (0.33333334f - 0.25f * t)));
-  #ifdef RECMV_LIBM_SOFTPLUS
-  const float lg = log1pf(t);
-#else
-  const float lg = __log2f(1.f + t) * 0.69314718f;          // 1 + t in [1, 2]: the bare v_log_f32, no range fix-ups
-#endif
-  const float l = t < 0.015625f ? series : lg;
-  const float y = (fmaxf(zb, 0.f) + l) * inv_p;
-  return zb > 20.f ? z : y;
-}
-
-__device__ __forceinline__ float softplus_grad(float y, float p) {   // sigmoid(beta z) = 1 - exp(-beta y), series below 1/64
-  const float t = p * y;
-  const float series = t * (1.f - t * (0.5f - t * (0.16666667f - 0.041666668f * t)));
-  const float e = 1.f - RECMV_EXPF(-t);
-  return t < 0.015625f ? series : e;
-}
-
-// ACT: a compile-time activation (RECMV_ACT_SOFTPLUS) or -1 = look at the run-time value.
-template <int ACT>
-__device__ __forceinline__ float act_fwd(float z, int act, float p, float inv_p) {
-  if (ACT == RECMV_ACT_SOFTPLUS) return softplus_fwd(z, p, inv_p);
-  if (act == RECMV_ACT_RELU) return z > 0.f ? z : 0.f;
-  if (act == RECMV_ACT_SOFTPLUS) return softplus_fwd(z, p, inv_p);
-  if (act == RECMV_ACT_TANH) return tanhf(z);
-  return z;
-}
-
-template <int ACT>
-__device__ __forceinline__ float act_grad(float y, int act, float p) {   // act'(z) through y = act(z) (mlp_chain.hip)
-  if (ACT == RECMV_ACT_SOFTPLUS) return softplus_grad(y, p);
-  switch (act) {
-    case RECMV_ACT_RELU: return y > 0.f ? 1.f : 0.f;
-    case RECMV_ACT_SOFTPLUS: return softplus_grad(y, p);
-    case RECMV_ACT_TANH: return 1.f - y * y;
-    default: return 1.f;
-  }
-}
+// Softplus is the hot activation (SDF net, offset MLP): act_fwd / act_grad of activation.h are its straight-line forms.
 
 // acc[rt][t] += A_rt[16 x 16*KC] . B_t^T for the wave's TPW column tiles and the workgroup's RT row tiles.  A: LDS, row stride
 // kLD, lane (r = l & 15, j = l >> 4) reads the four inputs 16c + 4j .. + 3 of row 16 rt + r with one ds_read_b128; the packed B
@@ -600,7 +548,7 @@ inline int64_t packed_floats(int N, int K, bool whole_tiles_only) {
 PackPlan make_plan(const recmv_mlp* m) {
   PackPlan pl;
   int64_t o = 0;
-  const int n = m->n_layers, d_pe = 3 + 6 * m->multires;
+  const int n = m->n_layers, d_pe = mlp_d_pe(m);
   for (int l = 0; l < n; ++l) {
     pl.N_fwd[l] = m->rows[l];
     pl.K_fwd[l] = m->dims[l];
@@ -615,17 +563,22 @@ PackPlan make_plan(const recmv_mlp* m) {
   return pl;
 }
 
-int rows_supported(const recmv_mlp* m) {
-  if (!m || m->n_layers < 2 || m->n_layers > RECMV_MLP_MAX_LAYERS) return 0;
-  if (m->multires < 0 || m->multires > 8) return 0;
-  if (m->split_row > 0 && m->W2[0]) return 0;
+// does a VALID descriptor (mlp_validate) fit the row-tile kernels?  No error message: "does not fit" is an answer, not a failure.
+bool rows_fit(const recmv_mlp* m) {
+  if (m->n_layers < 2 || m->multires > 8 || mlp_has_second(m)) return false;
   for (int l = 0; l <= m->n_layers; ++l)
-    if (m->dims[l] > kMaxWidth && l < m->n_layers) return 0;
+    if (m->dims[l] > kMaxWidth && l < m->n_layers) return false;
   // the last layer too: the reverse pass stages ceil(rows / 16) chunks of its cotangent in an LDS row of kLD floats
   for (int l = 0; l < m->n_layers; ++l)
-    if (m->rows[l] > kMaxWidth) return 0;
-  if (m->skip_layer == 0 || m->skip_layer >= m->n_layers) return 0;
-  return 1;
+    if (m->rows[l] > kMaxWidth) return false;
+  return m->skip_layer != 0;
+}
+
+// what every row-tile entry point does first
+int rows_check(const recmv_mlp* m, const char* who) {
+  RECMV_TRY(mlp_validate(m, who));
+  RECMV_REQUIRE(rows_fit(m), "%s: this net does not fit the row-tile kernels", who);
+  return RECMV_OK;
 }
 
 void fill_args(const recmv_mlp* m, const float* packed, RowsArgs* a) {
@@ -660,9 +613,6 @@ void fill_args(const recmv_mlp* m, const float* packed, RowsArgs* a) {
 inline size_t fwd_lds(int rt) { return (size_t)(2 * 16 * rt * kLD + 16 * rt * kPeLD + 16 * rt * 4 + kWaves * 64 * 4) * sizeof(float); }
 inline size_t vjp_lds(int rt) { return (size_t)(2 * 16 * rt * kLD + 16 * rt * kPeLD + 16 * rt * 4) * sizeof(float); }
 
-inline int64_t pad16(int64_t v) { return (v + 15) / 16 * 16; }
-inline int64_t pad32(int64_t v) { return (v + 31) / 32 * 32; }
-
 // Row tiles per workgroup: 16 rows while one round of workgroups covers the rows (lowest latency), 32 rows past that — or whatever
 // recmv_set_mlp_rows_tile says (2 = every weight byte from L2 feeds twice the FLOP and a pass takes half the CUs).
 int g_rows_rt = 0;       // 0 = by row count
@@ -679,8 +629,8 @@ RowsLayout rows_layout(const recmv_mlp* m, int64_t P) {
   RowsLayout L;
   int64_t maxw = 16;
   for (int l = 1; l < m->n_layers; ++l) maxw = m->dims[l] > maxw ? m->dims[l] : maxw;
-  L.ld_act = pad16(maxw);
-  L.act_stride = pad32(P) * L.ld_act;
+  L.ld_act = align_up(maxw, 16);
+  L.act_stride = align_up(P, 32) * L.ld_act;
   L.bytes = (int64_t)(m->n_layers - 1) * L.act_stride * 4;
   return L;
 }
@@ -705,7 +655,9 @@ extern "C" int recmv_debug_rows_clock(long long* out, int cap, int reset) {
 }
 #endif
 
-extern "C" int recmv_mlp_rows_supported(const recmv_mlp* m) { return rows_supported(m); }
+extern "C" int recmv_mlp_rows_supported(const recmv_mlp* m) {
+  return mlp_validate(m, "mlp_rows_supported") == RECMV_OK && rows_fit(m);
+}
 
 extern "C" int recmv_set_mlp_rows_tile(int row_tiles) {
   RECMV_REQUIRE(row_tiles >= 0 && row_tiles <= 2, "set_mlp_rows_tile: 0 (by row count), 1 (16 rows) or 2 (32 rows)");
@@ -714,19 +666,18 @@ extern "C" int recmv_set_mlp_rows_tile(int row_tiles) {
 }
 
 extern "C" int64_t recmv_mlp_pack_bytes(const recmv_mlp* m) {
-  if (!rows_supported(m)) return 0;
+  if (!recmv_mlp_rows_supported(m)) return 0;
   return make_plan(m).floats * 4;
 }
 
 extern "C" int recmv_mlp_pack(const recmv_mlp* m, void* packed, int64_t packed_bytes, void* stream) {
-  RECMV_REQUIRE(rows_supported(m), "mlp_pack: this net does not fit the row-tile kernels");
+  RECMV_TRY(rows_check(m, "mlp_pack"));
   const PackPlan pl = make_plan(m);
   RECMV_REQUIRE(packed && packed_bytes >= pl.floats * 4, "mlp_pack: buffer %lld < %lld bytes", (long long)packed_bytes,
                 (long long)(pl.floats * 4));
   float* out = (float*)packed;
   const int n = m->n_layers;
   for (int l = 0; l < n; ++l) {
-    RECMV_REQUIRE(m->W[l], "mlp_pack: layer %d has no weight", l);
     const int ldw = m->dims[l];
     {
       const int KC = (pl.K_fwd[l] + 15) / 16;
@@ -745,14 +696,14 @@ extern "C" int recmv_mlp_pack(const recmv_mlp* m, void* packed, int64_t packed_b
 }
 
 extern "C" int64_t recmv_mlp_rows_workspace_bytes(const recmv_mlp* m, int64_t P) {
-  if (!rows_supported(m) || P <= 0) return 0;
+  if (!recmv_mlp_rows_supported(m) || P <= 0) return 0;
   return rows_layout(m, P).bytes;
 }
 
 extern "C" int recmv_mlp_rows_forward(const recmv_mlp* m, const void* packed, const float* x, const float* cond, int64_t ld_cond,
                                       const int64_t* cond_index, int64_t P, int n_out, float* out, int64_t ldo, void* workspace,
                                       int64_t workspace_bytes, int keep, void* stream) {
-  RECMV_REQUIRE(rows_supported(m), "mlp_rows_forward: this net does not fit the row-tile kernels");
+  RECMV_TRY(rows_check(m, "mlp_rows_forward"));
   RECMV_REQUIRE(P >= 0, "mlp_rows_forward: negative P");
   if (P == 0) return RECMV_OK;
   RECMV_REQUIRE(packed && x && out, "mlp_rows_forward: NULL pointer");
@@ -789,7 +740,7 @@ extern "C" int recmv_mlp_rows_forward(const recmv_mlp* m, const void* packed, co
 extern "C" int recmv_mlp_rows_vjp_input(const recmv_mlp* m, const void* packed, const float* x, int64_t P, int n_out,
                                         const float* g_out, int64_t ldg, float* gx, const void* workspace, int64_t workspace_bytes,
                                         void* stream) {
-  RECMV_REQUIRE(rows_supported(m), "mlp_rows_vjp_input: this net does not fit the row-tile kernels");
+  RECMV_TRY(rows_check(m, "mlp_rows_vjp_input"));
   RECMV_REQUIRE(P >= 0, "mlp_rows_vjp_input: negative P");
   if (P == 0) return RECMV_OK;
   RECMV_REQUIRE(packed && x && gx && workspace, "mlp_rows_vjp_input: NULL pointer");
