@@ -42,7 +42,10 @@ extern "C" {
  *        point-pair search of mesh repair: pure additions, still v11); recmv_voxel_band_workspace_bytes,
  *        recmv_voxel_band_distance, recmv_voxel_sign_fill with the recmv_lattice descriptor (mesh voxelisation: pure additions,
  *        still v11); recmv_hole_triangulate, recmv_hole_triangulate_workspace_bytes, recmv_hole_fill_lds_max_edges,
- *        recmv_hole_fill_auto_max_edges, recmv_hole_fill_max_edges (hole filling: pure additions, still v11).
+ *        recmv_hole_fill_auto_max_edges, recmv_hole_fill_max_edges (hole filling: pure additions, still v11);
+ *        recmv_winding_chunk_faces, recmv_winding_exact_workspace_bytes, recmv_winding_exact, recmv_winding_tree_nodes,
+ *        recmv_winding_tree_cells, recmv_winding_tree_build, recmv_winding_tree_query with the recmv_winding_tree descriptor
+ *        (generalized winding numbers: pure additions, still v11).
  *   v10: recmv_verts_normals, recmv_hard_phong_shade, recmv_hard_phong_params_floats added.  Added since without a bump (no
  *        existing signature changed, and _lib.py rejects a library that lacks them): recmv_knn1, recmv_nricp_energy,
  *        recmv_lap_align_solve, recmv_lap_smooth, recmv_closest_point, recmv_iso_relax, recmv_loop_subdivide,
@@ -1105,6 +1108,73 @@ int64_t recmv_hole_triangulate_workspace_bytes(const int64_t* loop_offsets, int6
 int recmv_hole_triangulate(const float* verts, int64_t V, const int64_t* loop_verts, const int64_t* loop_offsets,
                            const int64_t* loop_offsets_device, int64_t L, int64_t* out_faces, double* out_weight,
                            void* workspace, int64_t workspace_bytes, int route, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Generalized winding numbers (csrc/winding.hip, csrc/solid_angle.h; added to ABI v11, no existing signature changed).  Not in
+ * the reference.  The kernels of recmv/winding.py: w(q) of P points (p [P,3] f32) about a triangle mesh (verts [V,3] f32,
+ * faces [F,3] int64), w [P] f64.
+ * Definition.  For a face with corners A, B, C and a query q, all f32: a = A - q, b = B - q, c = C - q,
+ *   Omega = 2 atan2( a . (b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b| ),      w(q) = (sum over the faces of Omega) / 4 pi.
+ *   Omega is computed in f32, un-contracted; the sum is accumulated in f64, and w = sum / 4 pi is one f64 division.  For a
+ *   closed mesh w is an integer (0 outside, +-1 inside, +-2 inside two overlapping pieces), for an open one it varies smoothly;
+ *   |w| > 1/2 is the inside test of recmv/winding.py (two-sided; NaN is outside).
+ *   A face with an index outside [0, V) contributes 0.  A face without area contributes 0 (its numerator is 0).  A face with
+ *   a corner that is not finite makes every w NaN.  A query that is not finite gets NaN.  A query exactly on a face gets
+ *   2 atan2(+-0, negative) = +-2 pi for that face, a term of +-1/2.  None of these is an error.
+ * Determinism.  The result of a query depends on the query and the mesh alone: not on P, on the other queries, on the launch
+ *   or on scheduling.  No atomics.
+ * recmv_winding_exact: every face for every query.  The faces are cut into chunks of recmv_winding_chunk_faces() faces, a
+ *   constant of the library: chunk c holds the faces [c K, min(F, (c + 1) K)).  partial[c][q] = the f64 sum of chunk c's terms
+ *   in ascending face order from 0., and w[q] = (((0. + partial[0][q]) + partial[1][q]) + ...) / 4 pi in ascending chunk order.
+ *   The workspace holds the partials, [chunks, P] f64, and keeps them after the call:
+ *   recmv_winding_exact_workspace_bytes(P, F) bytes (-1 with a message for negative sizes or more than 65535 chunks), 8-byte
+ *   aligned; it is not needed for F = 0.
+ * The tree route: a dense pyramid over the cube [origin, origin + side)^3 around the mesh.  Level l = 0 .. levels has 2^l
+ *   cells per axis; node (l, i, j, k) is row (8^l - 1) / 7 + (i 2^l + j) 2^l + k of `nodes`, recmv_winding_tree_nodes(levels)
+ *   rows of 16 floats: the area sum, the area-weighted centroid sum (3), the area-vector sum N = sum of (B - A) x (C - A) / 2
+ *   (3), the number of faces (an int32's bits), the low corner of the box of the faces' corners (3), 0, the high corner (3), 0.
+ *   The descriptor lies in HOST memory and its tables in device memory; levels is 1 .. 7.
+ *   recmv_winding_tree_cells: cells [F] int64 = the finest cell (i n + j) n + k, n = 2^levels, of each face's centroid
+ *     ((A + B) + C) / 3, an axis index being floor((x - origin) / (side / n)) clamped to [0, n - 1]; -1 for a face with an index
+ *     outside [0, V) (skipped), -2 for a face with a corner that is not finite (the caller answers NaN).  Reads origin, side
+ *     and levels of the descriptor only.
+ *   recmv_winding_tree_build: the caller sorts the faces with a cell >= 0 by cell, stably (ascending face id within a cell):
+ *     order [n_faces] int64 are their ids and cell_start [8^levels + 1] int64 the first sorted position of every finest cell.
+ *     Fills tris [n_faces, 9] f32 (the sorted faces' corners) and nodes: the finest level by one thread per cell that adds
+ *     its faces in sorted order, each coarser level by one thread per parent that adds its 8 children, x slowest, z fastest;
+ *     f32 sums, no atomics.
+ *   recmv_winding_tree_query: thread t answers query order[t] (order [P] int64, a permutation that puts neighbouring queries
+ *     side by side, or NULL for the identity; an entry outside [0, P) is skipped).  Depth-first from the root in the build's
+ *     child order: a node without faces is skipped; with centre = centroid sum / area sum (the box's centre when the area sum
+ *     is 0), r = the largest distance from the centre to a corner of the node's box and d = centre - q, a node with
+ *     |d|^2 > (beta beta) r^2 contributes N . d / |d|^3 (the first-order, dipole term); any other node is descended into, and at
+ *     the finest level its faces are evaluated with the exact route's function.  f64 accumulation in visiting order, then
+ *     / 4 pi.  beta is finite and at least 1; the larger, the nearer to the exact sum.
+ * Argument errors (negative sizes, NULL pointers with non-zero sizes, levels outside 1 .. 7, a beta that is not finite or
+ * below 1, a short or misaligned workspace, a cube side that is not positive and finite, an origin that is not finite) are
+ * found before any HIP call.  P = 0 is a no-op; F = 0 writes zeros.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct recmv_winding_tree {
+  float origin[3];
+  float side;
+  int32_t levels;
+  int32_t reserved;
+  int64_t n_faces;
+  float* nodes;
+  int64_t* cell_start;
+  float* tris;
+} recmv_winding_tree;
+int64_t recmv_winding_chunk_faces(void);
+int64_t recmv_winding_exact_workspace_bytes(int64_t P, int64_t F);
+int recmv_winding_exact(const float* p, int64_t P, const float* verts, int64_t V, const int64_t* faces, int64_t F, double* w,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int64_t recmv_winding_tree_nodes(int levels);
+int recmv_winding_tree_cells(const float* verts, int64_t V, const int64_t* faces, int64_t F, const recmv_winding_tree* tree,
+                             int64_t* cells, void* stream);
+int recmv_winding_tree_build(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* order,
+                             const recmv_winding_tree* tree, void* stream);
+int recmv_winding_tree_query(const float* p, int64_t P, const int64_t* order, const recmv_winding_tree* tree, float beta,
+                             double* w, void* stream);
 
 #ifdef __cplusplus
 }

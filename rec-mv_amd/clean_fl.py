@@ -22,7 +22,9 @@ lattice BEFORE it is smoothed or simplified (recmv.voxelize.remesh: exact distan
 marching cubes — a watertight manifold mesh of uniform resolution from a CLOSED mesh, whatever its self-intersections);
 topology.json then holds `voxel` per file (lattice, band_nodes, open_columns, sign_conflicts, faces before and after).  A mesh
 that is not closed shows as open_columns > 0 or sign_conflicts > 0 and the command refuses it, writing nothing, unless
-`--voxel-force` is given.  `--solidify T` takes the
+`--voxel-force` is given.  `--voxel-sign winding` takes the sign from the generalized winding number instead
+(recmv.winding, |w| > 1/2 at every node): a mesh with holes is capped coarsely where w = 1/2, overlapping pieces unite, the two
+diagnostics are information only and nothing is refused; `voxel` then holds `sign`.  `--solidify T` takes the
 unsigned route instead (recmv.voxelize.solidify: a closed shell of thickness T around an open garment; the voxel flag gives the
 step).
 `--fill-holes` closes the holes of what is left AFTER the repair and the floaters and BEFORE the voxel remesh, the smoothing and
@@ -44,7 +46,7 @@ loops — an upper garment with four feature lines has four.
         [--smooth taubin|laplacian|bilateral] [--smooth-iters N] [--smooth-lambda L] [--smooth-mu M]
         [--smooth-weights uniform|cotangent] [--smooth-boundary fixed|curve|free] [--smooth-normal-iters N]
         [--smooth-vertex-iters N] [--smooth-sigma-s S] [--repair] [--weld-eps E]
-        [--voxel-remesh STEP | --voxel-resolution N] [--voxel-force] [--solidify T]
+        [--voxel-remesh STEP | --voxel-resolution N] [--voxel-force] [--voxel-sign parity|winding] [--solidify T]
         [--fill-holes] [--fill-max-edges N] [--fill-max-perimeter P] [--fill-keep-largest K] [--fill-refine]
         [--fill-fair-iters N]
 """
@@ -94,6 +96,9 @@ def build_parser():
                         help='the same with the step chosen so that the lattice has N nodes along the longest axis')
     parser.add_argument('--voxel-force', action='store_true',
                         help='write the voxel remesh even when columns of the lattice end inside (the mesh is not closed)')
+    parser.add_argument('--voxel-sign', default='parity', choices=('parity', 'winding'),
+                        help='the sign of the voxel remesh: the crossing parity (closed meshes only), or the generalized winding '
+                             'number, which takes holes and overlapping pieces and never refuses')
     parser.add_argument('--solidify', default=None, type=float, metavar='T',
                         help='instead of the signed remesh: a closed shell of thickness T around every (open) mesh; '
                              '--voxel-remesh or --voxel-resolution gives the step')
@@ -190,6 +195,10 @@ def main(argv=None):
             parser.error("--solidify must be a positive, finite thickness")
     if args.voxel_force and not voxelising:
         parser.error("--voxel-force needs --voxel-remesh or --voxel-resolution")
+    if args.voxel_sign != 'parity' and not voxelising:
+        parser.error("--voxel-sign needs --voxel-remesh or --voxel-resolution")
+    if args.voxel_sign != 'parity' and args.solidify is not None:
+        parser.error("--solidify is unsigned: --voxel-sign does not apply")
     if voxelising and args.report_only:
         parser.error("--report-only writes no mesh: the voxel flags need --out")
     check_fill_flags(parser, args)
@@ -246,10 +255,11 @@ def main(argv=None):
                         kv, kf, vi = voxelize.solidify(kv, kf, args.solidify, step=args.voxel_remesh,
                                                        resolution=args.voxel_resolution)
                     else:
-                        kv, kf, vi = voxelize.remesh(kv, kf, step=args.voxel_remesh, resolution=args.voxel_resolution)
+                        kv, kf, vi = voxelize.remesh(kv, kf, step=args.voxel_remesh, resolution=args.voxel_resolution,
+                                                     sign=args.voxel_sign)
                 except ValueError as e:
                     parser.error("%s: %s" % (name, e))
-                if (vi['open_columns'] > 0 or vi['sign_conflicts'] > 0) and not args.voxel_force:
+                if (vi['open_columns'] > 0 or vi['sign_conflicts'] > 0) and not args.voxel_force and args.voxel_sign == 'parity':
                     parser.error("%s: open_columns = %d, sign_conflicts = %d: columns of the lattice end inside the mesh, or nodes far "
                                  "from the surface disagree about their side, so the mesh is not closed (or a parity was lost) and "
                                  "its voxel remesh is not to be trusted; nothing written.  --solidify is for open surfaces; "
@@ -257,6 +267,8 @@ def main(argv=None):
                 entry['voxel'] = {'mode': 'solidify' if args.solidify is not None else 'remesh', 'lattice': vi['lattice'].json(),
                                   'band': vi['band'], 'band_nodes': vi['band_nodes'], 'open_columns': vi['open_columns'],
                                   'sign_conflicts': vi['sign_conflicts'], 'faces_before': vi['faces_in'], 'faces_after': vi['faces_out']}
+                if args.solidify is None:
+                    entry['voxel']['sign'] = vi['sign']
                 print('%s: voxel %s on %d x %d x %d nodes of step %g: %d -> %d faces, %d band nodes, %d open columns, %d sign '
                       'conflicts' % (name, entry['voxel']['mode'], *vi['lattice'].dims, vi['lattice'].step, vi['faces_in'],
                                      vi['faces_out'], vi['band_nodes'], vi['open_columns'], vi['sign_conflicts']))

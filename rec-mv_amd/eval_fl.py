@@ -20,6 +20,8 @@ pair the faces of the prediction that take part in a crossing of the prediction 
 a directory paired by stem, like `--gt`) the prediction's faces that cross that body (`body_intersecting_faces`,
 `body_intersection_ratio`), and with `--penetration` besides the prediction's vertices inside that body and the largest
 distance of one of them to its surface (`body_inside_vertices`, `body_max_depth`); definitions in INTEGRATION.md §5.
+`--inside-rule winding` judges the vertices by the generalized winding number about the body instead of the crossing parity
+(recmv.winding, |w| > 1/2: the body may have holes or consist of overlapping pieces; `body_inside: {rule}` records it).
 `--drop-floaters FRAC` removes from the prediction, before alignment and metrics, every piece whose area is below FRAC times
 its largest piece's (recmv.topology.keep_components; one floater decides `accuracy_max` and drags the precision down) and
 records what went under `floaters` in the pair's entry; `--topology` adds `topology_pred` and `topology_gt`
@@ -32,14 +34,15 @@ other: a scan exported with one vertex triple per face reads as F pieces until i
 `repair_gt`.  `--volume` adds to every pair the volumetric intersection over union of the two meshes and their volumes
 (`volume_iou`, `volume_pred`, `volume_gt`; recmv.voxelize.volume_iou on one lattice around both, of step `--volume-step` or with
 129 nodes along the longest axis; the counts and the lattice under `volume`).  The sign is a crossing parity, so both meshes must
-be closed: when a diagnostic of either says it is not (`open_columns`, `sign_conflicts`) the three figures are None, `volume`
+be closed (`--voxel-sign winding` takes the sign of the generalized winding number instead, which measures meshes with holes,
+unites overlapping pieces and never withholds a figure): when a diagnostic of either says it is not (`open_columns`, `sign_conflicts`) the three figures are None, `volume`
 holds the `reason`, and they have no `mean`.
 
     python rec-mv_amd/eval_fl.py --gpu-ids 0 --pred <obj|dir> --gt <obj|dir> [--samples N] [--seed S] [--thresholds t ...]
         [--scale s] [--method auto|grid|brute] [--intersections [--body <obj|dir> [--penetration]]] [--out metrics.json]
         [--align none|rigid|similarity [--align-metric plane|point] [--align-trim f] [--align-iters n]
          [--align-from each|first] [--align-out DIR]] [--drop-floaters FRAC] [--topology] [--repair] [--weld-eps E]
-        [--volume [--volume-step S]] [--fill-holes [--fill-max-edges N] [--fill-keep-largest K]]
+        [--volume [--volume-step S] [--voxel-sign parity|winding]] [--inside-rule parity|winding] [--fill-holes [--fill-max-edges N] [--fill-keep-largest K]]
 
 `--fill-holes` closes the holes of the prediction AND the ground truth after `--repair` and before every metric
 (recmv.holes.fill: least-area patches; `--fill-max-edges N` leaves loops of more than N edges open, `--fill-keep-largest K` the
@@ -95,6 +98,11 @@ def build_parser():
     parser.add_argument('--fill-max-edges', default=None, type=int, metavar='N', help='with --fill-holes: longer loops stay open')
     parser.add_argument('--fill-keep-largest', default=None, type=int, metavar='K',
                         help='with --fill-holes: the K loops of longest perimeter stay open')
+    parser.add_argument('--voxel-sign', default='parity', choices=('parity', 'winding'),
+                        help='with --volume: the sign of the lattices; winding (the generalized winding number) measures meshes '
+                             'with holes and unites overlapping pieces, and its figures are never withheld')
+    parser.add_argument('--inside-rule', default='parity', choices=('parity', 'winding'),
+                        help='with --penetration: how a vertex is judged inside the body; winding takes a body with holes')
     parser.add_argument('--volume-step', default=None, type=float, metavar='S',
                         help='with --volume: the lattice step (default: 129 nodes along the longest axis of the pair\'s box)')
     return parser
@@ -152,6 +160,10 @@ def main(argv=None):
     if args.weld_eps is not None and not (0. <= args.weld_eps < float('inf')):
         parser.error("--weld-eps must be finite and not negative")
     repairing = args.repair or args.weld_eps is not None
+    if args.voxel_sign != 'parity' and not args.volume:
+        parser.error("--voxel-sign needs --volume")
+    if args.inside_rule != 'parity' and not args.penetration:
+        parser.error("--inside-rule needs --penetration")
     if args.volume_step is not None and not args.volume:
         parser.error("--volume-step needs --volume")
     if args.volume_step is not None and not (0. < args.volume_step < float('inf')):
@@ -241,13 +253,17 @@ def main(argv=None):
                 per_pair[stem].update({'body_intersecting_faces': int(hit['faces_a'].shape[0]),
                                        'body_intersection_ratio': hit['ratio_a']})
                 if args.penetration:
-                    pen = metrics.penetration(pv.to(device), bv.to(device), bfaces.to(device), method=args.method)
+                    pen = metrics.penetration(pv.to(device), bv.to(device), bfaces.to(device), method=args.method,
+                                              rule=args.inside_rule)
                     per_pair[stem].update({'body_inside_vertices': pen['count'], 'body_max_depth': pen['max_depth']})
+                    if args.inside_rule != 'parity':
+                        per_pair[stem]['body_inside'] = {'rule': args.inside_rule}
         if args.volume:
             from recmv import voxelize
             vol = voxelize.volume_iou(pv.to(device), pfaces.to(device), gv.to(device), gfaces.to(device), step=args.volume_step,
-                                      method=args.method)
-            closed = not (vol['open_columns_a'] or vol['open_columns_b'] or vol['sign_conflicts_a'] or vol['sign_conflicts_b'])
+                                      method=args.method, sign=args.voxel_sign)
+            closed = args.voxel_sign == 'winding' or not (vol['open_columns_a'] or vol['open_columns_b'] or vol['sign_conflicts_a']
+                                                          or vol['sign_conflicts_b'])
             per_pair[stem].update({'volume_iou': vol['iou'] if closed else None, 'volume_pred': vol['volume_a'] if closed else None,
                                    'volume_gt': vol['volume_b'] if closed else None})
             per_pair[stem]['volume'] = {'step': vol['step'], 'lattice': vol['lattice'].json(), 'intersection': vol['intersection'],
@@ -256,6 +272,8 @@ def main(argv=None):
                                         'sign_conflicts_gt': vol['sign_conflicts_b'],
                                         'reason': None if closed else 'a mesh of the pair is not closed (open_columns or sign_conflicts > 0): '
                                                                       'a crossing parity gives it no volume'}
+            if args.voxel_sign != 'parity':
+                per_pair[stem]['volume']['sign'] = args.voxel_sign
         if stem in floaters:
             per_pair[stem]['floaters'] = floaters[stem]
         if stem in repaired:

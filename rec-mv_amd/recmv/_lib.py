@@ -56,6 +56,12 @@ class Lattice(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("step", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32)]
 
 
+class WindingTreeDesc(C.Structure):
+    """recmv_winding_tree of include/recmv_hip.h."""
+    _fields_ = [("origin", C.c_float * 3), ("side", C.c_float), ("levels", C.c_int32), ("reserved", C.c_int32),
+                ("n_faces", C.c_int64), ("nodes", C.c_void_p), ("cell_start", C.c_void_p), ("tris", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -80,7 +86,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
 
 def _declare(lib):
     vp, i64, i32, f32, f64 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double
-    T5, MG, LT = C.POINTER(Tensor5), C.POINTER(MeshGridDesc), C.POINTER(Lattice)
+    T5, MG, LT, WT = C.POINTER(Tensor5), C.POINTER(MeshGridDesc), C.POINTER(Lattice), C.POINTER(WindingTreeDesc)
     sigs = {
         "recmv_abi_version": (C.c_int, []),
         "recmv_no_packed_f32": (C.c_int, []),
@@ -235,6 +241,13 @@ def _declare(lib):
         "recmv_hole_fill_max_edges": (i64, []),
         "recmv_hole_triangulate_workspace_bytes": (i64, [vp, i64, i32]),
         "recmv_hole_triangulate": (C.c_int, [vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, vp]),
+        "recmv_winding_chunk_faces": (i64, []),
+        "recmv_winding_exact_workspace_bytes": (i64, [i64, i64]),
+        "recmv_winding_exact": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, i64, vp]),
+        "recmv_winding_tree_nodes": (i64, [i32]),
+        "recmv_winding_tree_cells": (C.c_int, [vp, i64, vp, i64, WT, vp, vp]),
+        "recmv_winding_tree_build": (C.c_int, [vp, i64, vp, i64, vp, WT, vp]),
+        "recmv_winding_tree_query": (C.c_int, [vp, i64, vp, WT, f32, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)       # AttributeError if the symbol is missing: fail loudly

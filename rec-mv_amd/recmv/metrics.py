@@ -375,14 +375,22 @@ def segment_hits(p, q, verts, faces, count=False, method='auto', lanes=None):
     return _segment_result(p, q, face, t, cnt if count else None)
 
 
+def _check_rule(rule):
+    if rule not in ('parity', 'winding'):
+        raise ValueError("rule must be 'parity' or 'winding' (got %r)" % (rule,))
+
+
 @torch.no_grad()
-def points_inside(points, verts, faces, method='auto'):
+def points_inside(points, verts, faces, method='auto', rule='parity'):
     """Which of the points [P,3] f32 lie inside the mesh verts / faces (CUDA): bool [P].  Every point casts three segments
     along INSIDE_DIRECTIONS, each ending beyond the mesh's bounding box (1.5 box diagonals plus the point's distance to the
     box's centre away), and the result is the majority of the three parities of the number of faces crossed: a ray that
     grazes an edge or a vertex (touching is no hit, so it may count one face too few or too many) is outvoted.  The mesh
     is taken to be closed and free of self-intersections; a mesh that is not closed gives whatever the parities give.  A point
-    that is not finite is outside."""
+    that is not finite is outside.
+    rule='winding' takes recmv.winding.points_inside instead (the exact generalized winding number, |w| > 1/2): sound for a mesh
+    with holes, for overlapping closed pieces (their union) and for either orientation; `method` then only is checked."""
+    _check_rule(rule)
     _check_mesh(verts, faces)
     L.require_cuda(points, "points")
     if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
@@ -393,6 +401,9 @@ def points_inside(points, verts, faces, method='auto'):
     P = points.shape[0]
     if P == 0:
         return torch.zeros(0, dtype=torch.bool, device=points.device)
+    if rule == 'winding':
+        from . import winding
+        return winding.points_inside(points, verts, faces)
     points = points.contiguous()
     lo, hi = verts.amin(0), verts.amax(0)
     reach = 1.5 * (hi - lo).norm() + (points - 0.5 * (lo + hi)).norm(dim=1, keepdim=True)                    # [P,1]
@@ -405,12 +416,13 @@ def points_inside(points, verts, faces, method='auto'):
 
 
 @torch.no_grad()
-def penetration(points, body_v, body_f, method='auto'):
+def penetration(points, body_v, body_f, method='auto', rule='parity'):
     """How deep the points [P,3] f32 (a garment's vertices) lie inside the closed mesh body_v / body_f: a dict with `inside`
     [P] bool (points_inside), `depth` [P] f32 = the distance to the nearest point of the surface for the points inside and 0
     for the others (the closest-point query of this module, unchanged), `count` (points inside), `max_depth` and `mean_depth`
-    (over the points inside; 0 when there are none) — python numbers, one read-back."""
-    inside = points_inside(points, body_v, body_f, method=method)
+    (over the points inside; 0 when there are none) — python numbers, one read-back.  `rule`: points_inside's ('winding' takes a
+    body with holes or of several overlapping pieces)."""
+    inside = points_inside(points, body_v, body_f, method=method, rule=rule)
     if points.shape[0] == 0:
         return {'inside': inside, 'depth': points.new_zeros(0), 'count': 0, 'max_depth': 0., 'mean_depth': 0.}
     _, _, dist2 = _nearest(points.contiguous(), body_v.contiguous(), body_f.contiguous(), method)

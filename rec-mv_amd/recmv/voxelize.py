@@ -28,9 +28,18 @@ has an end within one step of it, so there is none).  A hole that faces along x 
 cylinder of the tests does at some steps — but on the way out through the hole the flag must flip between nodes far from the
 surface, which the second count sees.  remesh's callers should refuse a result where either is not 0.
 
-Out of scope here (none of it is attempted):
+sign='winding' (distance_field, remesh, occupancy, volume, volume_iou; the default stays 'parity') takes the sign from the
+generalized winding number of recmv.winding instead: EVERY node's flag is |w| > 1/2 and the column rule is not used (it is unsound
+through a hole).  w comes from the pyramid (winding_method='tree', recmv.winding.DEFAULT_BETA) by default and from every face with
+winding_method='exact'; the nodes are queried in slices.  sdf = where(inside, -1, 1) * minimum(sqrt(dist2), band) as before.
+`open_columns` and `sign_conflicts` are still reported, but under this sign they are information, not faults: where the mesh has
+a hole the surface w = 1/2 passes between nodes that are clamped to +-band, marching cubes caps the hole there — a COARSE cap, a
+staircase of the lattice's step and no smooth patch — and the cap shows up in both counts.  The result carries 'sign'.
+
+What the first two items below used to say is therefore available through sign='winding':
   * a winding-number sign for meshes with holes;
-  * a per-piece union of overlapping closed pieces;
+  * a per-piece union of overlapping closed pieces (w = 2 inside two pieces is inside).
+Out of scope here (none of it is attempted):
   * cavity filling, or an "outer surface" of a body plus its garments;
   * a GridSamplerMine collision loss on a body TSDF (distance_field's `sdf` is the lattice it would sample);
   * any change to MCGpu, metrics or the existing kernels.
@@ -42,6 +51,7 @@ import torch
 
 from . import _lib as L
 from . import metrics
+from . import winding
 
 MAX_NODES = 1 << 28            # recmv_mc_*'s limit
 DEFAULT_BAND_STEPS = 3.        # a choice, not a measurement: marching cubes needs one step, the rest keeps its interpolation
@@ -49,6 +59,31 @@ DEFAULT_BAND_STEPS = 3.        # a choice, not a measurement: marching cubes nee
 DEFAULT_PAD_STEPS = 4          # the default band and one step: the lattice border is never cut
 MIN_BAND_STEPS = 2.
 DEFAULT_IOU_RESOLUTION = 129   # volume_iou without step and resolution
+SIGNS = ('parity', 'winding')
+DEFAULT_WINDING_METHOD = 'tree'  # measured against 'exact' at lattice sizes (tools/winding_timing.py)
+WINDING_SLICE = 1 << 22        # lattice nodes per winding query
+
+
+def _check_sign(sign, winding_method):
+    if sign not in SIGNS:
+        raise ValueError("sign must be 'parity' or 'winding' (got %r)" % (sign,))
+    if winding_method is not None and winding_method not in winding.METHODS:
+        raise ValueError("winding_method must be 'tree' or 'exact' (got %r)" % (winding_method,))
+    if winding_method is not None and sign != 'winding':
+        raise ValueError("winding_method belongs to sign='winding'")
+
+
+def _winding_inside(verts, faces, lattice, winding_method):
+    """|w| > 1/2 at every node of the lattice, [N] uint8, in slices of WINDING_SLICE nodes in node order."""
+    N, dev = lattice.n_nodes, verts.device
+    method = DEFAULT_WINDING_METHOD if winding_method is None else winding_method
+    tree = winding.WindingTree(verts, faces) if method == 'tree' else None
+    out = torch.empty(N, dtype=torch.uint8, device=dev)
+    for a in range(0, N, WINDING_SLICE):
+        pts = lattice.points(torch.arange(a, min(a + WINDING_SLICE, N), device=dev))
+        w = tree.query(pts) if tree is not None else winding.winding_number(pts, verts, faces)
+        out[a:a + WINDING_SLICE] = winding.inside_from_winding(w)
+    return out
 
 
 def _f32(x):
@@ -175,13 +210,14 @@ def _band_of(lattice, band):
 
 
 @torch.no_grad()
-def distance_field(verts, faces, lattice, band=None, signed=True, method='auto'):
+def distance_field(verts, faces, lattice, band=None, signed=True, method='auto', sign='parity', winding_method=None):
     """The narrow-band distance field of the mesh verts [V,3] f32 / faces [F,3] int64 (CUDA) on `lattice`: a dict with `dist2`
     f32 and `face` int64 (+inf and -1 outside the band), `sdf` f32 = (inside ? -1 : +1) * min(sqrt(dist2), band), `inside` bool
     (each [NX, NY, NZ]), `band` (the float32 the kernels got), `band_nodes`, `open_columns` and `sign_conflicts` (python ints; the
     last two are 0 for a closed mesh well inside the lattice, see the module docstring).  `band`: a length, 3 steps by default,
     at least 2 steps.  `signed=False` skips the segment queries: every node is outside and sdf >= 0.
-    `method`: metrics.points_inside's."""
+    `method`: metrics.points_inside's.  `sign`, `winding_method`: the module docstring; the result carries `sign`."""
+    _check_sign(sign, winding_method)
     band = _band_of(lattice, band)
     metrics.use_grid_for_segments(method, 0, 0)
     metrics._check_mesh(verts, faces)
@@ -207,6 +243,14 @@ def distance_field(verts, faces, lattice, band=None, signed=True, method='auto')
         b = torch.tensor(band, dtype=torch.float32, device=dev)
         in_band = dist2 <= b * b
         inside_band = None
+        if signed and sign == 'winding':
+            inside = _winding_inside(verts, faces, lattice, winding_method)
+            flag = inside.view(torch.bool)
+            sdf = torch.where(flag, -1., 1.).to(torch.float32) * torch.minimum(dist2.sqrt(), b)
+            counts = torch.stack([flag.view(dims)[-1].sum(), _sign_conflicts(flag.view(dims), in_band.view(dims)), in_band.sum()])
+            n_open, n_conflicts, band_nodes = (int(x) for x in counts.cpu().tolist())
+            return {'dist2': dist2.view(dims), 'face': face.view(dims), 'sdf': sdf.view(dims), 'inside': flag.view(dims),
+                    'band': band, 'band_nodes': band_nodes, 'open_columns': n_open, 'sign_conflicts': n_conflicts, 'sign': sign}
         if signed:
             index = torch.nonzero(in_band)[:, 0]                                   # ascending node order (a read-back)
             band_nodes = int(index.shape[0])
@@ -226,7 +270,7 @@ def distance_field(verts, faces, lattice, band=None, signed=True, method='auto')
     else:
         n_open = n_conflicts = 0
     return {'dist2': dist2.view(dims), 'face': face.view(dims), 'sdf': sdf.view(dims), 'inside': inside.view(torch.bool).view(dims),
-            'band': band, 'band_nodes': band_nodes, 'open_columns': n_open, 'sign_conflicts': n_conflicts}
+            'band': band, 'band_nodes': band_nodes, 'open_columns': n_open, 'sign_conflicts': n_conflicts, 'sign': sign}
 
 
 def _sign_conflicts(inside, in_band):
@@ -274,22 +318,24 @@ def _steps_beyond(length):
 
 
 @torch.no_grad()
-def remesh(verts, faces, step=None, resolution=None, band=None, method='auto'):
+def remesh(verts, faces, step=None, resolution=None, band=None, method='auto', sign='parity', winding_method=None):
     """Voxel remeshing of a CLOSED mesh: exact distances on a lattice (`step`, or `resolution` nodes along the longest axis),
     the crossing-parity sign, marching cubes at 0 — a watertight manifold mesh of uniform resolution whatever the input's
     self-intersections (overlapping pieces XOR, see the module docstring).  The lattice is padded by at least band + 1 step, so
     its border is never cut.  Returns (verts, faces, info); info: `lattice`, `band`, `band_nodes`, `open_columns` and
     `sign_conflicts` (either > 0: the input has holes or the parity was lost — the output then is not to be trusted), `faces_in`,
-    `faces_out`."""
+    `faces_out`, `sign`.  sign='winding' takes a mesh with holes (each capped coarsely where w = 1/2) or of overlapping pieces
+    (their union); the two diagnostics then are information only."""
+    _check_sign(sign, winding_method)
     metrics._check_mesh(verts, faces)
     lo, hi = _box(verts)
     length = (lambda s: DEFAULT_BAND_STEPS * s) if band is None else (lambda s: float(band))
     lattice = lattice_from_box(lo, hi, step, resolution, _steps_beyond(length))
-    field = distance_field(verts, faces, lattice, band=band, signed=True, method=method)
+    field = distance_field(verts, faces, lattice, band=band, signed=True, method=method, sign=sign, winding_method=winding_method)
     v, f = extract(field['sdf'], lattice, 0.)
     return v, f, {'lattice': lattice, 'band': field['band'], 'band_nodes': field['band_nodes'],
                   'open_columns': field['open_columns'], 'sign_conflicts': field['sign_conflicts'],
-                  'faces_in': int(faces.shape[0]), 'faces_out': int(f.shape[0])}
+                  'faces_in': int(faces.shape[0]), 'faces_out': int(f.shape[0]), 'sign': sign}
 
 
 @torch.no_grad()
@@ -315,27 +361,30 @@ def solidify(verts, faces, thickness, step=None, resolution=None):
                   'sign_conflicts': 0, 'thickness': thickness, 'faces_in': int(faces.shape[0]), 'faces_out': int(f.shape[0])}
 
 
-def _occupancy(verts, faces, lattice, method='auto'):
-    return distance_field(verts, faces, lattice, band=MIN_BAND_STEPS * lattice.step, signed=True, method=method)
+def _occupancy(verts, faces, lattice, method='auto', sign='parity', winding_method=None):
+    return distance_field(verts, faces, lattice, band=MIN_BAND_STEPS * lattice.step, signed=True, method=method, sign=sign,
+                          winding_method=winding_method)
 
 
-def occupancy(verts, faces, lattice, method='auto'):
-    """Which nodes of `lattice` lie inside the closed mesh: bool [NX, NY, NZ] (distance_field's `inside` at a band of 2 steps)."""
-    return _occupancy(verts, faces, lattice, method)['inside']
+def occupancy(verts, faces, lattice, method='auto', sign='parity', winding_method=None):
+    """Which nodes of `lattice` lie inside the closed mesh: bool [NX, NY, NZ] (distance_field's `inside` at a band of 2 steps).
+    sign='winding': |w| > 1/2, the union of overlapping pieces."""
+    return _occupancy(verts, faces, lattice, method, sign, winding_method)['inside']
 
 
-def volume(verts, faces, lattice, method='auto'):
+def volume(verts, faces, lattice, method='auto', sign='parity', winding_method=None):
     """The volume of the closed mesh as the number of nodes inside times step^3 (a python float; one read-back for the count)."""
-    return int(occupancy(verts, faces, lattice, method).sum().item()) * lattice.step ** 3
+    return int(occupancy(verts, faces, lattice, method, sign, winding_method).sum().item()) * lattice.step ** 3
 
 
 @torch.no_grad()
-def volume_iou(a_v, a_f, b_v, b_f, step=None, resolution=None, method='auto'):
+def volume_iou(a_v, a_f, b_v, b_f, step=None, resolution=None, method='auto', sign='parity', winding_method=None):
     """Volumetric intersection over union of two closed meshes on ONE lattice around both (`step`, or `resolution` nodes along
     the longest axis; 129 nodes when neither is given): {'iou', 'intersection', 'union', 'volume_a', 'volume_b', 'step'} — the
     two counts exact integers (one read-back for all the counts), the volumes count * step^3, iou = 0 for an empty union — and
     `open_columns_a`, `open_columns_b`, `sign_conflicts_a`, `sign_conflicts_b`: not 0 when that mesh is not closed, and the
-    figures then mean nothing."""
+    figures then mean nothing — under sign='parity'; under sign='winding' (`sign` in the result) they are information only."""
+    _check_sign(sign, winding_method)
     metrics._check_mesh(a_v, a_f)
     metrics._check_mesh(b_v, b_f)
     if a_v.device != b_v.device:
@@ -343,10 +392,11 @@ def volume_iou(a_v, a_f, b_v, b_f, step=None, resolution=None, method='auto'):
     if step is None and resolution is None:
         resolution = DEFAULT_IOU_RESOLUTION
     lattice = lattice_for(torch.cat([a_v, b_v]), step, resolution, pad_steps=int(MIN_BAND_STEPS) + 1)
-    fa, fb = _occupancy(a_v, a_f, lattice, method), _occupancy(b_v, b_f, lattice, method)
+    fa, fb = (_occupancy(v, f, lattice, method, sign, winding_method) for v, f in ((a_v, a_f), (b_v, b_f)))
     a, b = fa['inside'], fb['inside']
     n = torch.stack([(a & b).sum(), (a | b).sum(), a.sum(), b.sum()]).cpu().tolist()
     cell = lattice.step ** 3
     return {'iou': n[0] / n[1] if n[1] else 0., 'intersection': int(n[0]), 'union': int(n[1]), 'volume_a': n[2] * cell,
             'volume_b': n[3] * cell, 'step': lattice.step, 'lattice': lattice, 'open_columns_a': fa['open_columns'],
-            'open_columns_b': fb['open_columns'], 'sign_conflicts_a': fa['sign_conflicts'], 'sign_conflicts_b': fb['sign_conflicts']}
+            'open_columns_b': fb['open_columns'], 'sign_conflicts_a': fa['sign_conflicts'], 'sign_conflicts_b': fb['sign_conflicts'],
+            'sign': sign}
