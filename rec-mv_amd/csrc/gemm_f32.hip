@@ -975,12 +975,12 @@ __global__ __launch_bounds__(kBlk) void b3_split_kernel(const float* __restrict_
 // tiles of 64x32 = 3 per CU).  The 4 waves are 2 (row halves) x 2 (halves of every K-tile): each wave owns one 32x32
 // MFMA tile over half of K, the two K-halves are summed through LDS before the epilogue.
 template <bool FAST, bool AMUL, bool BF3>
-__global__ __launch_bounds__(kBlk) void gemm_nt_narrow_kernel(const float* __restrict__ A, int64_t lda,
-                                                              const float* __restrict__ B, int64_t ldb,
-                                                              const float* __restrict__ bias, float* __restrict__ C,
-                                                              int64_t ldc, int M, int N, int K, int act,
-                                                              float act_param, float out_scale, int nbm, int nbn,
-                                                              bool a_vec, bool b_vec, bool c_vec, AMul am) {
+__global__ __launch_bounds__(kBlk) void gemm_nt_narrow_v1_kernel(const float* __restrict__ A, int64_t lda,
+                                                                 const float* __restrict__ B, int64_t ldb,
+                                                                 const float* __restrict__ bias, float* __restrict__ C,
+                                                                 int64_t ldc, int M, int N, int K, int act,
+                                                                 float act_param, float out_scale, int nbm, int nbn,
+                                                                 bool a_vec, bool b_vec, bool c_vec, AMul am) {
   constexpr int TBM = 64, TBN = 32;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* As = smem;                        // [2][64][LDK]
@@ -1088,6 +1088,200 @@ __global__ __launch_bounds__(kBlk) void gemm_nt_narrow_kernel(const float* __res
   }
   __syncthreads();
   const int c4 = tid & 7, r0 = tid >> 3;   // 8 float4 strips per row, 32 rows per pass
+  const int gn = n0 + c4 * 4;
+  if (gn >= N) return;
+  const float inv_p = act_param != 0.f ? 1.f / act_param : 0.f;
+  float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (bias) {
+    bv.x = bias[gn];
+    if (gn + 1 < N) bv.y = bias[gn + 1];
+    if (gn + 2 < N) bv.z = bias[gn + 2];
+    if (gn + 3 < N) bv.w = bias[gn + 3];
+  }
+  const bool full4 = c_vec && gn + 4 <= N;
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    const int row = r0 + 32 * pass;
+    const int gm = m0 + row;
+    if (gm >= M) break;
+    const float4 v0 = *reinterpret_cast<const float4*>(Cs + row * LDC + c4 * 4);
+    const float4 v1 = *reinterpret_cast<const float4*>(Cs + (TBM + row) * LDC + c4 * 4);
+    float4 v = make_float4(v0.x + v1.x + bv.x, v0.y + v1.y + bv.y, v0.z + v1.z + bv.z, v0.w + v1.w + bv.w);
+    switch (act) {
+      case RECMV_ACT_RELU:
+        v.x = apply_act<RECMV_ACT_RELU>(v.x, act_param, inv_p);
+        v.y = apply_act<RECMV_ACT_RELU>(v.y, act_param, inv_p);
+        v.z = apply_act<RECMV_ACT_RELU>(v.z, act_param, inv_p);
+        v.w = apply_act<RECMV_ACT_RELU>(v.w, act_param, inv_p);
+        break;
+      case RECMV_ACT_SOFTPLUS:
+        v.x = apply_act<RECMV_ACT_SOFTPLUS>(v.x, act_param, inv_p);
+        v.y = apply_act<RECMV_ACT_SOFTPLUS>(v.y, act_param, inv_p);
+        v.z = apply_act<RECMV_ACT_SOFTPLUS>(v.z, act_param, inv_p);
+        v.w = apply_act<RECMV_ACT_SOFTPLUS>(v.w, act_param, inv_p);
+        break;
+      case RECMV_ACT_TANH:
+        v.x = apply_act<RECMV_ACT_TANH>(v.x, act_param, inv_p);
+        v.y = apply_act<RECMV_ACT_TANH>(v.y, act_param, inv_p);
+        v.z = apply_act<RECMV_ACT_TANH>(v.z, act_param, inv_p);
+        v.w = apply_act<RECMV_ACT_TANH>(v.w, act_param, inv_p);
+        break;
+      default:
+        break;
+    }
+    v.x *= out_scale;
+    v.y *= out_scale;
+    v.z *= out_scale;
+    v.w *= out_scale;
+    if (!AMUL && am.Y) v = emul4(v, am, gm, gn, N);
+    float* dst = C + (int64_t)gm * ldc + gn;
+    if (full4) {
+      *reinterpret_cast<float4*>(dst) = v;
+    } else {
+      dst[0] = v.x;
+      if (gn + 1 < N) dst[1] = v.y;
+      if (gn + 2 < N) dst[2] = v.z;
+      if (gn + 3 < N) dst[3] = v.w;
+    }
+  }
+}
+
+// The kernel in use (RECMV_GEMM_NARROW=0 selects the one above): the same tile, wave layout, LDS image and epilogue, and for every output
+// element the same sums in the same order — two chains over K (k mod 32 < 16 and the rest) in ascending tile order, within 8 consecutive k
+// the order 0, 4, 1, 5, 2, 6, 3, 7, columns past K exact zeros, chain0 + chain1, then the bias — so its results are the bits of the kernel
+// above.  What differs is the schedule of a K-tile:
+//   - the barrier stands in the MIDDLE of a tile's 8 MFMAs and the fragments are double-buffered by half-tiles: after the barrier a wave
+//     reads the first half-tile of tile kt+1 while the second half of tile kt (already in registers) feeds the pipe, so neither the LDS
+//     read latency nor the other waves' skew at the barrier leaves the wave without an MFMA to issue;
+//   - the staging registers of tile kt+1 go to LDS behind the first 4 MFMAs of tile kt, just in front of the barrier (they were loaded
+//     at the same place of tile kt-1: 8 MFMAs and a barrier wait behind), so the wait for them and for the LDS stores runs under MFMAs
+//     in flight, and the loads of tile kt+2 follow at once; the loads are unconditional at clamped addresses, the K tail is zeroed at
+//     the LDS store and the operand transform is applied there, so nothing waits on a fresh load result;
+//   - the unaligned instantiation loads whole groups of 4 as one dword-aligned access (load4_dword), like the SCAL kernels;
+//   - without the operand transform the kernel is held to 64 registers (8 waves per SIMD), so that a workgroup fits beside resident
+//     waves of the weight-gradient kernel.
+// The bf16x6 mode (BF3) keeps the kernel above.
+template <bool FAST, bool AMUL, bool BF3>
+__global__ __launch_bounds__(kBlk) __attribute__((amdgpu_waves_per_eu(AMUL ? 4 : 8)))
+void gemm_nt_narrow_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
+                           const float* __restrict__ bias, float* __restrict__ C, int64_t ldc, int M, int N, int K, int act,
+                           float act_param, float out_scale, int nbm, int nbn, bool a_vec, bool b_vec, bool c_vec, AMul am) {
+  static_assert(!BF3, "the bf16x6 mode runs gemm_nt_narrow_v1_kernel");
+  constexpr int TBM = 64, TBN = 32;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* As = smem;                        // [2][64][LDK]
+  float* Bs = smem + 2 * TBM * LDK;        // [2][32][LDK]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave & 1, wk = wave >> 1;
+  const int64_t logical = xcd_remap(blockIdx.x, (int64_t)nbm * nbn);
+  const int tile_m = (int)(logical / nbn), tile_n = (int)(logical % nbn);
+  const int m0 = tile_m * TBM, n0 = tile_n * TBN;
+  seg_operands(am, m0, B, bias);
+
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+
+  // staging: A 64 rows x 8 float4 (2 per thread), B 32 rows x 8 float4 (1 per thread); rows past M / N are clamped to the last one (FAST)
+  // or zero (otherwise): they reach no stored element
+  float4 ra[2], ry[2], rb;
+  const float* pa[2];
+  const float* pb;
+  const float* py[2];
+  const int brow_s = tid >> 3, c4s = tid & 7;
+  bool rowok[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    int gm = m0 + brow_s + 32 * r;
+    rowok[r] = gm < M;
+    gm = gm < M ? gm : M - 1;
+    pa[r] = A + (int64_t)gm * lda + c4s * 4;
+    if (AMUL) py[r] = am.Y + (int64_t)gm * am.ldy + c4s * 4;
+  }
+  int gnb = n0 + brow_s;
+  const bool bok = gnb < N;
+  gnb = bok ? gnb : N - 1;
+  pb = B + (int64_t)gnb * ldb + c4s * 4;
+  auto gload = [&](int k0) {
+    const int k = k0 + c4s * 4;
+    if (FAST) {
+      const int ko = k < K ? k0 : K - 4 - c4s * 4;      // K % 4 == 0, K >= 4: the last float4 of the row instead of one past it
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        ra[r] = *reinterpret_cast<const float4*>(pa[r] + ko);
+        if (AMUL) ry[r] = *reinterpret_cast<const float4*>(py[r] + ko);
+      }
+      rb = *reinterpret_cast<const float4*>(pb + ko);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        ra[r] = rowok[r] ? load4_dword(pa[r] + k0, K - k) : make_float4(0, 0, 0, 0);
+        if (AMUL) ry[r] = rowok[r] ? load4_dword(py[r] + k0, K - k) : make_float4(0, 0, 0, 0);
+      }
+      rb = bok ? load4_dword(pb + k0, K - k) : make_float4(0, 0, 0, 0);
+    }
+  };
+  auto lstore = [&](int buf, int k0) {
+    const int keep = (!FAST || k0 + c4s * 4 < K) ? 4 : 0;      // FAST: the staged float4 lies inside K or past it
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      float4 v = ra[r];
+      if (AMUL && (FAST || rowok[r])) v = amul4(v, ry[r], am);
+      *reinterpret_cast<float4*>(As + (buf * TBM + brow_s + 32 * r) * LDK + c4s * 4) = keep4(v, keep);
+    }
+    *reinterpret_cast<float4*>(Bs + (buf * TBN + brow_s) * LDK + c4s * 4) = keep4(rb, keep);
+  };
+
+  const int nk = (K + BK - 1) / BK;
+  gload(0);
+  lstore(0, 0);
+  if (nk > 1) gload(BK);
+  __syncthreads();
+  // fragments: lanes 0-31 hold k = 0..3 and lanes 32-63 k = 4..7 of each group of 8, so the MFMAs of a float4 take k in the order 0, 4, 1, 5, ...
+  const float* as = As + (wm * 32 + (lane & 31)) * LDK + (lane >> 5) * 4 + wk * 16;
+  const float* bs = Bs + (lane & 31) * LDK + (lane >> 5) * 4 + wk * 16;
+  float4 a0 = *reinterpret_cast<const float4*>(as), b0 = *reinterpret_cast<const float4*>(bs);
+  float4 a1 = *reinterpret_cast<const float4*>(as + 8), b1 = *reinterpret_cast<const float4*>(bs + 8);
+  auto mfma4 = [&](const float4& a, const float4& b) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+  };
+  for (int kt = 0; kt < nk; ++kt) {
+    const bool more = kt + 1 < nk;
+    const int nb = (kt + 1) & 1;
+    mfma4(a0, b0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (more) {
+      lstore(nb, (kt + 1) * BK);           // buffer nb held tile kt-1: every wave finished reading it before the barrier of tile kt-1
+      if (kt + 2 < nk) gload((kt + 2) * BK);
+    }
+    __syncthreads();
+    if (more) {
+      a0 = *reinterpret_cast<const float4*>(as + nb * TBM * LDK);
+      b0 = *reinterpret_cast<const float4*>(bs + nb * TBN * LDK);
+    }
+    mfma4(a1, b1);
+    if (more) {
+      a1 = *reinterpret_cast<const float4*>(as + nb * TBM * LDK + 8);
+      b1 = *reinterpret_cast<const float4*>(bs + nb * TBN * LDK + 8);
+    }
+  }
+
+  // the two K-halves -> two LDS planes [64][LDC]; the epilogue adds them.  No wave reads an operand buffer after the last barrier above.
+  constexpr int LDC = TBN + 4;
+  float* Cs = smem;                        // [2][64][LDC] = 18.4 KB <= the operand buffers
+  int te = tid;                            // the epilogue's indices are formed here, not kept in registers across the K loop
+  asm volatile("" : "+v"(te));
+  const int elane = te & 63, ewm = (te >> 6) & 1, ewk = te >> 7;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = ewm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (elane >> 5);
+    Cs[(ewk * TBM + row) * LDC + (elane & 31)] = acc[r];
+  }
+  __syncthreads();
+  const int c4 = te & 7, r0 = te >> 3;     // 8 float4 strips per row, 32 rows per pass
   const int gn = n0 + c4 * 4;
   if (gn >= N) return;
   const float inv_p = act_param != 0.f ? 1.f / act_param : 0.f;
@@ -1268,13 +1462,19 @@ static int launch_nt(const NtCall& c, const NtPlan& p) {
   return check_launch("gemm_nt");
 }
 
-template <bool FAST, bool AMUL, bool BF3>
+// V1: gemm_nt_narrow_v1_kernel (the bf16x6 mode, and every launch under RECMV_GEMM_NARROW=0); otherwise gemm_nt_narrow_kernel: same bits
+template <bool FAST, bool AMUL, bool BF3, bool V1>
 static int launch_nt_narrow(const NtCall& c, const NtPlan& p) {
   const int nbm = (int)ceil_div(c.M, 64), nbn = (int)ceil_div(c.N, 32);
   ScopedLaunchTimer timer(p.slot, (double)c.M, (double)c.N, (double)c.K, c.stream);
-  hipLaunchKernelGGL((gemm_nt_narrow_kernel<FAST, AMUL, BF3>), dim3((unsigned)((int64_t)nbm * nbn)), dim3(kBlk), kNarrowLds, c.stream,
-                     c.A, c.lda, c.B, c.ldb, c.bias, c.C, c.ldc, (int)c.M, (int)c.N, (int)c.K, c.act, c.act_param, c.out_scale, nbm, nbn,
-                     p.a_vec, p.b_vec, c.c_vec, c.am);
+  if constexpr (V1 || BF3)
+    hipLaunchKernelGGL((gemm_nt_narrow_v1_kernel<FAST, AMUL, BF3>), dim3((unsigned)((int64_t)nbm * nbn)), dim3(kBlk), kNarrowLds, c.stream,
+                       c.A, c.lda, c.B, c.ldb, c.bias, c.C, c.ldc, (int)c.M, (int)c.N, (int)c.K, c.act, c.act_param, c.out_scale, nbm, nbn,
+                       p.a_vec, p.b_vec, c.c_vec, c.am);
+  else
+    hipLaunchKernelGGL((gemm_nt_narrow_kernel<FAST, AMUL, BF3>), dim3((unsigned)((int64_t)nbm * nbn)), dim3(kBlk), kNarrowLds, c.stream,
+                       c.A, c.lda, c.B, c.ldb, c.bias, c.C, c.ldc, (int)c.M, (int)c.N, (int)c.K, c.act, c.act_param, c.out_scale, nbm, nbn,
+                       p.a_vec, p.b_vec, c.c_vec, c.am);
   return check_launch("gemm_nt(narrow)");
 }
 
@@ -1366,8 +1566,11 @@ static int launch_nt_tile(const NtCall& c, const NtPlan& p) {
 }
 template <bool AMUL>
 static int launch_nt_narrow_tile(const NtCall& c, const NtPlan& p) {
-  if (p.fast) return p.bf3 ? launch_nt_narrow<true, AMUL, true>(c, p) : launch_nt_narrow<true, AMUL, false>(c, p);
-  return p.bf3 ? launch_nt_narrow<false, AMUL, true>(c, p) : launch_nt_narrow<false, AMUL, false>(c, p);
+  const char* e = getenv("RECMV_GEMM_NARROW");       // =0: the kernel before the half-tile schedule (A/B); read at every launch
+  const bool v1 = e && e[0] == '0';
+  if (p.bf3) return p.fast ? launch_nt_narrow<true, AMUL, true, true>(c, p) : launch_nt_narrow<false, AMUL, true, true>(c, p);
+  if (p.fast) return v1 ? launch_nt_narrow<true, AMUL, false, true>(c, p) : launch_nt_narrow<true, AMUL, false, false>(c, p);
+  return v1 ? launch_nt_narrow<false, AMUL, false, true>(c, p) : launch_nt_narrow<false, AMUL, false, false>(c, p);
 }
 
 // plan (gemm_route.h), log, launch

@@ -4,8 +4,8 @@
 
 Each file is compiled at the base revision (sources and headers from `git archive`) and in the working tree with build.py's flags plus
 `--cuda-device-only -S`, once with the default flag set and once with RECMV_NO_PACKED_F32=1's.  Comment lines and assembler
-directives are dropped (labels and the .amdhsa_* kernel descriptors stay), and so is the __hip_cuid_* symbol, a hash of the source
-text.  A line per file and flag set: `identical`, or the functions whose text differs.
+directives are dropped (labels and the .amdhsa_* kernel descriptors stay; block labels without the index of their function in the
+file), and so is the __hip_cuid_* symbol, a hash of the source text.  A line per file and flag set: `identical`, or the functions whose text differs.
 """
 from __future__ import annotations
 
@@ -42,6 +42,7 @@ def device_asm(tree: Path, name: str, extra: list) -> dict:
             continue
         if s.startswith(".") and not s.endswith(":") and not s.startswith(".amdhsa_"):
             continue
+        s = re.sub(r"\.(LBB|Lfunc_end|Lfunc_begin)\d+", r".\1", s)      # local labels carry the function's index in the file: it moves when a kernel is added
         m = re.fullmatch(r"([A-Za-z_][\w$.]*):", s)
         if m:
             cur = m.group(1)
