@@ -23,6 +23,8 @@ namespace {
 
 #pragma clang fp contract(off)
 
+#include "mesh_device.h"                                   // wave_sum
+
 constexpr int kTubeBlock = 256;
 constexpr int kFitBlock = 256;
 constexpr int64_t kFitLdsBytes = 64 * 1024 - 64;      // dynamic part: a workgroup's 64 KiB less the static reduction slots
@@ -61,8 +63,7 @@ curve_tubes_kernel(const float* __restrict__ curves, const float* __restrict__ n
 }
 
 __device__ __forceinline__ double fit_block_sum(double v, double* red) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+  v = wave_sum(v);
   const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
   __syncthreads();                                     // red may still be read from the previous sum
   if (lane == 0) red[wave] = v;

@@ -4,6 +4,7 @@
 // RECMV_REQUIRE and no HIP calls, so that the host checks of tools/ compile it under tools/mesh_grid_host_check/common.h.
 #pragma once
 #include "closest_tri.h"                                   // Tri, for the triangle table
+#include "mesh_device.h"                                   // index_in
 
 struct Grid {
   float ox, oy, oz, h, inv_h;
@@ -87,7 +88,7 @@ __device__ __forceinline__ void for_each_entry(const GridView& v, int cell, int6
   if ((int64_t)e1 > v.n_entries) e1 = (int)v.n_entries;
   for (int e = e0; e < e1; ++e) {
     const int k = v.entries[e];
-    if ((uint64_t)k >= (uint64_t)F) continue;
+    if (!index_in(k, F)) continue;
     op(k);
   }
 }

@@ -95,7 +95,7 @@ __device__ __forceinline__ void wave_entry(const double* W, const double* WT, co
   for (int off = kWave / 2; off > 0; off >>= 1) {
     const double ob = __shfl_xor(best, off, kWave);
     const int ok = __shfl_xor(bestk, off, kWave);
-    if (ob < best || (ob == best && ok < bestk)) {
+    if (ob < best || (ob == best && ok < bestk)) {          // mesh_device.h's take_min, written out: the call moves this kernel's schedule
       best = ob;
       bestk = ok;
     }

@@ -23,6 +23,7 @@ namespace {
 #pragma clang fp contract(off)
 
 #include "closest_tri.h"                                   // Tri, closest_st_region, load_tri
+#include "mesh_device.h"                                   // finite3, index_in
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;
@@ -33,10 +34,6 @@ constexpr int kPointSums = 19;                             // entries 0 .. 18: w
 struct Centre {
   double x, y, z;
 };
-
-__device__ __forceinline__ bool finite3(float a, float b, float c) {
-  return __builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(c);
-}
 
 template <bool PLANE>
 __global__ void __launch_bounds__(kBlock)
@@ -56,7 +53,7 @@ icp_accumulate_kernel(const float* __restrict__ x, const float* __restrict__ q, 
     const float d2 = dist2[i];
     const float xx = x[3 * i], xy = x[3 * i + 1], xz = x[3 * i + 2];
     const float qx = q[3 * i], qy = q[3 * i + 1], qz = q[3 * i + 2];
-    if ((uint64_t)k >= (uint64_t)F) continue;
+    if (!index_in(k, F)) continue;
     if (!finite3(xx, xy, xz) || !finite3(qx, qy, qz) || !__builtin_isfinite(d2)) continue;
     if (max_dist2 && !(d2 <= limit)) continue;             // (a NaN limit accepts nothing)
     Tri tri;
@@ -109,7 +106,8 @@ icp_accumulate_kernel(const float* __restrict__ x, const float* __restrict__ q, 
       acc[54] += r * r;
     }
   }
-  // the wave: a butterfly, the same tree whatever the data; every lane ends with the wave's sum
+  // the wave: a butterfly, the same tree whatever the data; every lane ends with the wave's sum (mesh_device.h's wave_sum,
+  // written out: the call moves this kernel's schedule)
 #pragma unroll
   for (int k = 0; k < N; ++k) {
 #pragma unroll

@@ -31,6 +31,7 @@ constexpr int kCpTile = 512;                               // faces per LDS tile
 constexpr int kIsoBlock = 256;
 
 #include "closest_tri.h"                                   // Tri, closest_st, load_tri
+#include "mesh_device.h"                                   // csr_range, index_in
 
 __global__ void __launch_bounds__(kCpBlock)
 closest_point_kernel(const float* __restrict__ p, int64_t P, const float* __restrict__ v, int64_t V,
@@ -115,13 +116,6 @@ closest_point_finish_kernel(const unsigned long long* __restrict__ keys, const f
   }
 }
 
-__device__ __forceinline__ void csr_range(const int32_t* off, int64_t i, int64_t nnz, int64_t& k0, int64_t& k1) {
-  k0 = off[i];
-  k1 = off[i + 1];
-  if (k0 < 0) k0 = 0;
-  if (k1 > nnz) k1 = nnz;
-}
-
 __global__ void __launch_bounds__(kIsoBlock)
 iso_relax_kernel(const int32_t* __restrict__ off, const int32_t* __restrict__ nbr, int64_t V, int64_t nnz,
                  const float* __restrict__ x, const float* __restrict__ n, const uint8_t* __restrict__ fixed,
@@ -135,7 +129,7 @@ iso_relax_kernel(const int32_t* __restrict__ off, const int32_t* __restrict__ nb
     int64_t cnt = 0;
     for (int64_t k = k0; k < k1; ++k) {
       const int64_t j = nbr[k];
-      if ((uint64_t)j >= (uint64_t)V) continue;
+      if (!index_in(j, V)) continue;
 #pragma unroll
       for (int c = 0; c < 3; ++c) s[c] += (double)x[3 * j + c];
       ++cnt;
@@ -163,7 +157,7 @@ loop_even_kernel(const int32_t* __restrict__ off, const int32_t* __restrict__ nb
     const double p[3] = {(double)x[3 * i], (double)x[3 * i + 1], (double)x[3 * i + 2]};
     const int64_t b0 = bnbr[2 * i], b1 = bnbr[2 * i + 1];
     if (b0 >= 0 || b1 >= 0) {                              // boundary: 3/4 p + 1/8 each boundary neighbour
-      if ((uint64_t)b0 < (uint64_t)V && (uint64_t)b1 < (uint64_t)V) {
+      if (index_in(b0, V) && index_in(b1, V)) {
 #pragma unroll
         for (int c = 0; c < 3; ++c)
           out[3 * i + c] = (float)(0.75 * p[c] + 0.125 * ((double)x[3 * b0 + c] + (double)x[3 * b1 + c]));
@@ -179,7 +173,7 @@ loop_even_kernel(const int32_t* __restrict__ off, const int32_t* __restrict__ nb
     int64_t cnt = 0;
     for (int64_t k = k0; k < k1; ++k) {
       const int64_t j = nbr[k];
-      if ((uint64_t)j >= (uint64_t)V) continue;
+      if (!index_in(j, V)) continue;
 #pragma unroll
       for (int c = 0; c < 3; ++c) s[c] += (double)x[3 * j + c];
       ++cnt;
@@ -208,7 +202,7 @@ loop_odd_kernel(const int64_t* __restrict__ etab, int64_t E, const float* __rest
       o[0] = o[1] = o[2] = __builtin_nanf("");
       continue;
     }
-    const bool interior = (uint64_t)c < (uint64_t)V && (uint64_t)d < (uint64_t)V;
+    const bool interior = index_in(c, V) && index_in(d, V);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const double ab = (double)x[3 * a + k] + (double)x[3 * b + k];

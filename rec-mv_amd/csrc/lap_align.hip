@@ -31,6 +31,8 @@ namespace {
 
 #pragma clang fp contract(off)
 
+#include "mesh_device.h"                                   // csr_range, index_in, block_partials, reduce_slots
+
 constexpr int kLapBlock = 256;
 constexpr int kLapBatch = 32;                // iterations queued between two reads of the "done" flag
 
@@ -53,64 +55,6 @@ struct LapArgs {
   CgState* st;
 };
 
-__device__ __forceinline__ void csr_range(const LapArgs& a, int64_t i, int64_t& k0, int64_t& k1) {
-  k0 = a.off[i];
-  k1 = a.off[i + 1];
-  if (k0 < 0) k0 = 0;
-  if (k1 > a.nnz) k1 = a.nnz;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
-// Block sums of K doubles per thread to partials[K * blockIdx.x + k], in a fixed order.
-template <int K>
-__device__ __forceinline__ void block_partials(double (&acc)[K], double* __restrict__ partials) {
-  __shared__ double sh[K][kLapBlock / kWave];
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double t = wave_sum_d(acc[k]);
-    if (lane == 0) sh[k][wave] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    double t = 0.;
-    for (int w = 0; w < kLapBlock / kWave; ++w) t += sh[threadIdx.x][w];
-    partials[K * blockIdx.x + threadIdx.x] = t;
-  }
-}
-
-// One workgroup: the K sums over nslots slots, in a fixed order, into out[K] (valid in thread 0).
-template <int K>
-__device__ __forceinline__ void reduce_slots(const double* __restrict__ partials, int nslots, double (&out)[K]) {
-  double acc[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) acc[k] = 0.;
-  for (int s = threadIdx.x; s < nslots; s += kLapBlock) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] += partials[K * s + k];
-  }
-  __shared__ double sh[K][kLapBlock / kWave];
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double t = wave_sum_d(acc[k]);
-    if (lane == 0) sh[k][wave] = t;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) out[k] = 0.;
-  if (threadIdx.x == 0) {
-    for (int w = 0; w < kLapBlock / kWave; ++w)
-#pragma unroll
-      for (int k = 0; k < K; ++k) out[k] += sh[k][w];
-  }
-}
-
 // ---------------------------------------------------------------------------------------------- set-up
 // 1/deg_i, u = v (f64) and t = L v
 __global__ void __launch_bounds__(kLapBlock)
@@ -119,13 +63,13 @@ lap_init_kernel(LapArgs a, const float* __restrict__ v, double* __restrict__ inv
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.V; i += stride) {
     int64_t k0, k1;
-    csr_range(a, i, k0, k1);
+    csr_range(a.off, i, a.nnz, k0, k1);
     const double id = k1 > k0 ? 1. / (double)(k1 - k0) : 0.;
     invdeg[i] = id;
     double s[3] = {0., 0., 0.};
     for (int64_t k = k0; k < k1; ++k) {
       const int64_t j = a.nbr[k];
-      if ((uint64_t)j >= (uint64_t)a.V) continue;
+      if (!index_in(j, a.V)) continue;
 #pragma unroll
       for (int c = 0; c < 3; ++c) s[c] += (double)v[3 * j + c];
     }
@@ -150,11 +94,11 @@ lap_init_residual_kernel(LapArgs a, const float* __restrict__ v, const double* _
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < a.V; j += stride) {
     int64_t k0, k1;
-    csr_range(a, j, k0, k1);
+    csr_range(a.off, j, a.nnz, k0, k1);
     double s[3] = {0., 0., 0.}, d = 1.;
     for (int64_t k = k0; k < k1; ++k) {
       const int64_t i = a.nbr[k];
-      if ((uint64_t)i >= (uint64_t)a.V) continue;
+      if (!index_in(i, a.V)) continue;
       const double w = a.invdeg[i];
       d += w * w;
 #pragma unroll
@@ -177,13 +121,13 @@ lap_init_residual_kernel(LapArgs a, const float* __restrict__ v, const double* _
       acc[6 + c] += rc * rc;
     }
   }
-  block_partials<9>(acc, partials);
+  block_partials<9, kLapBlock>(acc, partials);
 }
 
 __global__ void __launch_bounds__(kLapBlock)
 lap_init_reduce_kernel(const double* __restrict__ partials, int nslots, double tol, int max_iter, CgState* st) {
   double s[9];
-  reduce_slots<9>(partials, nslots, s);
+  reduce_slots<9, kLapBlock>(partials, nslots, s);
   if (threadIdx.x == 0) {
     int any = 0;
 #pragma unroll
@@ -213,11 +157,11 @@ lap_cg_direction_kernel(LapArgs a, const double* __restrict__ z, const double* _
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.V; i += stride) {
     int64_t k0, k1;
-    csr_range(a, i, k0, k1);
+    csr_range(a.off, i, a.nnz, k0, k1);
     double s[3] = {0., 0., 0.};
     for (int64_t k = k0; k < k1; ++k) {
       const int64_t j = a.nbr[k];
-      if ((uint64_t)j >= (uint64_t)a.V) continue;
+      if (!index_in(j, a.V)) continue;
 #pragma unroll
       for (int c = 0; c < 3; ++c) s[c] += z[3 * j + c] + be[c] * pold[3 * j + c];
     }
@@ -240,11 +184,11 @@ lap_cg_apply_kernel(LapArgs a, const double* __restrict__ cw, const double* __re
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < a.V; j += stride) {
     int64_t k0, k1;
-    csr_range(a, j, k0, k1);
+    csr_range(a.off, j, a.nnz, k0, k1);
     double s[3] = {0., 0., 0.};
     for (int64_t k = k0; k < k1; ++k) {
       const int64_t i = a.nbr[k];
-      if ((uint64_t)i >= (uint64_t)a.V) continue;
+      if (!index_in(i, a.V)) continue;
       const double w = a.invdeg[i];
 #pragma unroll
       for (int c = 0; c < 3; ++c) s[c] += t[3 * i + c] * w;
@@ -258,7 +202,7 @@ lap_cg_apply_kernel(LapArgs a, const double* __restrict__ cw, const double* __re
       acc[c] += pc * qc;
     }
   }
-  block_partials<3>(acc, partials);
+  block_partials<3, kLapBlock>(acc, partials);
 }
 
 // (3) alpha = (r.z) / (p.q) per active column; a column whose p.q is not positive and finite freezes
@@ -266,7 +210,7 @@ __global__ void __launch_bounds__(kLapBlock)
 lap_cg_alpha_kernel(const double* __restrict__ partials, int nslots, CgState* st) {
   if (st->done) return;
   double pq[3];
-  reduce_slots<3>(partials, nslots, pq);
+  reduce_slots<3, kLapBlock>(partials, nslots, pq);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -300,7 +244,7 @@ lap_cg_update_kernel(LapArgs a, const double* __restrict__ dinv, const double* _
       acc[3 + c] += rc * rc;
     }
   }
-  block_partials<6>(acc, partials);
+  block_partials<6, kLapBlock>(acc, partials);
 }
 
 // (5) beta, convergence per column, iteration count, "done"
@@ -308,7 +252,7 @@ __global__ void __launch_bounds__(kLapBlock)
 lap_cg_beta_kernel(const double* __restrict__ partials, int nslots, double tol, CgState* st) {
   if (st->done) return;
   double s[6];
-  reduce_slots<6>(partials, nslots, s);
+  reduce_slots<6, kLapBlock>(partials, nslots, s);
   if (threadIdx.x == 0) {
     int any = 0;
 #pragma unroll
@@ -341,13 +285,12 @@ lap_smooth_kernel(const int32_t* __restrict__ off, const int32_t* __restrict__ n
                   const float* __restrict__ u, float* __restrict__ out) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += stride) {
-    int64_t k0 = off[i], k1 = off[i + 1];
-    if (k0 < 0) k0 = 0;
-    if (k1 > nnz) k1 = nnz;
+    int64_t k0, k1;
+    csr_range(off, i, nnz, k0, k1);
     double s[3] = {0., 0., 0.};
     for (int64_t k = k0; k < k1; ++k) {
       const int64_t j = nbr[k];
-      if ((uint64_t)j >= (uint64_t)V) continue;
+      if (!index_in(j, V)) continue;
 #pragma unroll
       for (int c = 0; c < 3; ++c) s[c] += (double)u[3 * j + c];
     }

@@ -25,6 +25,7 @@ namespace {
 #pragma clang fp contract(off)
 
 #include "closest_tri.h"
+#include "mesh_device.h"                                   // wave_sum
 
 constexpr int kNmBlock = 256;
 constexpr int kNmPer = 2;                                  // garment vertices per lane
@@ -106,12 +107,6 @@ mesh_nearest_unpack_kernel(const unsigned long long* __restrict__ keys, int64_t 
   }
 }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
 // grid (x over the vertices, y = frame); p_out may be p (every thread reads and writes its own vertex only).
 __global__ void __launch_bounds__(kPushBlock)
 collision_push_kernel(const float* __restrict__ p, const float* __restrict__ verts, const float* __restrict__ vnormals,
@@ -156,8 +151,8 @@ collision_push_kernel(const float* __restrict__ p, const float* __restrict__ ver
     }
     ob[3 * i] = ox; ob[3 * i + 1] = oy; ob[3 * i + 2] = oz;
   }
-  n_moved = wave_sum_i(n_moved);
-  n_unres = wave_sum_i(n_unres);
+  n_moved = wave_sum(n_moved);
+  n_unres = wave_sum(n_unres);
   if (threadIdx.x % kWave == 0) {
     if (n_moved) atomicAdd(moved + b, n_moved);
     if (n_unres) atomicAdd(unresolved + b, n_unres);

@@ -30,6 +30,7 @@ namespace {
 
 #include "closest_tri.h"                                   // Tri, closest_st, load_tri
 #include "grid_query.h"                                    // Grid, Range, face_range, the table; GridView, for_each_entry
+#include "mesh_device.h"                                   // wave_sum, take_min, index_in
 
 constexpr int kGridBlock = 256;
 constexpr int kBigFace = 256;                              // cells of a face's range above which its wave shares the work
@@ -64,12 +65,6 @@ __device__ __forceinline__ void for_each_cell(const Range& r, bool valid, int fa
   }
 }
 
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
 __global__ void __launch_bounds__(kGridBlock)
 grid_count_kernel(const float* __restrict__ v, int64_t V, const int64_t* __restrict__ f, int64_t F, Grid g,
                   int32_t* __restrict__ counts, unsigned long long* __restrict__ total) {
@@ -82,7 +77,7 @@ grid_count_kernel(const float* __restrict__ v, int64_t V, const int64_t* __restr
     if (valid) mine += range_cells(r);
     for_each_cell(r, valid, (int)k, g, [&](int cell, int) { atomicAdd(counts + cell, 1); });
   }
-  mine = wave_sum_ll(mine);
+  mine = wave_sum(mine);
   if (threadIdx.x % kWave == 0 && mine) atomicAdd(total, (unsigned long long)mine);
 }
 
@@ -206,14 +201,6 @@ __device__ __forceinline__ void shell_cell(int64_t k, int r, int cx, int cy, int
     const int inner = side - 2;
     x = j < inner ? cx - r : cx + r;
     y = cy - r + 1 + (j < inner ? j : j - inner);
-  }
-}
-
-// (best, bidx) <- the smaller of it and (d, k) in the order (distance, face id); NaN never wins.
-__device__ __forceinline__ void take_min(float d, int k, float& best, int& bidx) {
-  if (d < best || (d == best && k < bidx)) {
-    best = d;
-    bidx = k;
   }
 }
 

@@ -31,6 +31,7 @@ namespace {
 
 #include "grid_query.h"                                    // Grid, Range, face_range, range_cell; GridView, for_each_entry
 #include "tri_tri.h"                                       // Pts, load_pts, tri_boxes_meet, tri_tri_cross
+#include "mesh_device.h"                                   // group_sum
 
 constexpr int kBlock = 256;
 
@@ -133,8 +134,7 @@ intersect_grid_kernel(const float* __restrict__ va, int64_t VA, const int64_t* _
       });
     }
   }
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) mine += __shfl_xor(mine, off, G);
+  mine = group_sum<G>(mine);
   if (sub == 0 && counts) {
     counts[i] = mine;
     if (mine) atomicAdd(total, (unsigned long long)mine);

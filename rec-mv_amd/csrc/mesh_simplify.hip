@@ -49,28 +49,11 @@ namespace {
 
 #pragma clang fp contract(off)
 
+#include "mesh_device.h"                                   // tri_valid, index_in, csr_range_ordered, load3, cross3, dot3, finite_positive
+
 constexpr int kSimpBlock = 256;
 constexpr int kQuadric = 11;                               // 10 entries and the weight
 constexpr double kInvalidCost = 1.7976931348623157e308;    // the largest finite float64
-
-__device__ __forceinline__ bool tri_valid(const int64_t* row, int64_t V) {
-  if ((uint64_t)row[0] >= (uint64_t)V || (uint64_t)row[1] >= (uint64_t)V || (uint64_t)row[2] >= (uint64_t)V) return false;
-  return row[0] != row[1] && row[0] != row[2] && row[1] != row[2];
-}
-
-__device__ __forceinline__ bool finite_positive(double x) { return x > 0. && x < __builtin_inf(); }
-
-__device__ __forceinline__ int64_t clamp_index(int64_t x, int64_t lo, int64_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-__device__ __forceinline__ void load3(const float* v, int64_t i, double* out) {
-  out[0] = v[3 * i]; out[1] = v[3 * i + 1]; out[2] = v[3 * i + 2];
-}
-
-__device__ __forceinline__ void cross3(const double* u, const double* w, double* n) {
-  n[0] = u[1] * w[2] - u[2] * w[1];
-  n[1] = u[2] * w[0] - u[0] * w[2];
-  n[2] = u[0] * w[1] - u[1] * w[0];
-}
 
 // (b - a) x (c - a) of face `row`
 __device__ __forceinline__ void face_normal(const float* v, const int64_t* row, double* a, double* n) {
@@ -95,7 +78,7 @@ __device__ __forceinline__ bool face_plane(const float* v, int64_t V, const int6
   if (!tri_valid(row, V)) return false;
   double a[3], n[3];
   face_normal(v, row, a, n);
-  const double len = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+  const double len = sqrt(dot3(n, n));
   if (!finite_positive(len)) return false;                 // no area, or a corner that is not finite
   p[0] = n[0] / len; p[1] = n[1] / len; p[2] = n[2] / len;
   p[3] = -(p[0] * a[0] + p[1] * a[1] + p[2] * a[2]);
@@ -114,7 +97,7 @@ __device__ __forceinline__ bool border_plane(const float* v, int64_t V, const in
   load3(v, a, pa); load3(v, b, pb);
   const double e[3] = {pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2]};
   cross3(n, e, m);
-  const double len = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+  const double len = sqrt(dot3(m, m));
   if (!finite_positive(len)) return false;
   p[0] = m[0] / len; p[1] = m[1] / len; p[2] = m[2] / len;
   p[3] = -(p[0] * pa[0] + p[1] * pa[1] + p[2] * pa[2]);
@@ -138,21 +121,21 @@ vertex_quadrics_kernel(const float* __restrict__ v, int64_t V, const int64_t* __
 #pragma unroll
     for (int t = 0; t < kQuadric; ++t) q[t] = 0.;
     double p[4], w;
-    if (n_vf > 0) {
-      const int64_t end = clamp_index(vf_off[i + 1], 0, n_vf);
-      for (int64_t j = clamp_index(vf_off[i], 0, end); j < end; ++j) {
+    if (n_vf > 0) {                                        // (csr_range_ordered's rows, spelled out: this kernel's loop compare)
+      const int64_t end = clamp_i64(vf_off[i + 1], 0, n_vf);
+      for (int64_t j = clamp_i64(vf_off[i], 0, end); j < end; ++j) {
         const int64_t k = vf_idx[j];
-        if ((uint64_t)k >= (uint64_t)F) continue;
+        if (!index_in(k, F)) continue;
         if (!face_plane(v, V, f + 3 * k, p, &w)) continue;
         add_plane(q, w, p);
         q[10] += w;
       }
     }
     if (B > 0 && n_vb > 0) {
-      const int64_t end = clamp_index(vb_off[i + 1], 0, n_vb);
-      for (int64_t j = clamp_index(vb_off[i], 0, end); j < end; ++j) {
+      const int64_t end = clamp_i64(vb_off[i + 1], 0, n_vb);
+      for (int64_t j = clamp_i64(vb_off[i], 0, end); j < end; ++j) {
         const int64_t r = vb_idx[j];
-        if ((uint64_t)r >= (uint64_t)B) continue;
+        if (!index_in(r, B)) continue;
         if (!border_plane(v, V, f, F, border + 3 * r, p, &w)) continue;
         add_plane(q, boundary_weight * w, p);
       }
@@ -241,10 +224,10 @@ edge_collapse_cost_kernel(const double* __restrict__ Q, const float* __restrict_
 __device__ __forceinline__ bool ring_keeps_its_side(const float* v, int64_t V, const int64_t* f, int64_t F, const int64_t* vf_off,
                                                     const int64_t* vf_idx, int64_t n_vf, int64_t end, int64_t a, int64_t b,
                                                     const double* p) {
-  const int64_t last = clamp_index(vf_off[end + 1], 0, n_vf);
-  for (int64_t j = clamp_index(vf_off[end], 0, last); j < last; ++j) {
+  const CsrRow fan = csr_range_ordered(vf_off, end, n_vf);
+  for (int64_t j = fan.k0; j < fan.k1; ++j) {
     const int64_t k = vf_idx[j];
-    if ((uint64_t)k >= (uint64_t)F) continue;
+    if (!index_in(k, F)) continue;
     const int64_t* row = f + 3 * k;
     if (!tri_valid(row, V)) continue;
     const bool has_a = row[0] == a || row[1] == a || row[2] == a, has_b = row[0] == b || row[1] == b || row[2] == b;

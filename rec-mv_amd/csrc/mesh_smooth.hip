@@ -38,42 +38,21 @@ namespace {
 
 constexpr int kSmoothBlock = 256;
 
-__device__ __forceinline__ bool sm_tri_valid(const int64_t* row, int64_t V) {
-  if ((uint64_t)row[0] >= (uint64_t)V || (uint64_t)row[1] >= (uint64_t)V || (uint64_t)row[2] >= (uint64_t)V) return false;
-  return row[0] != row[1] && row[0] != row[2] && row[1] != row[2];
-}
-
-__device__ __forceinline__ bool sm_finite(double x) { return x > -__builtin_inf() && x < __builtin_inf(); }
-
-__device__ __forceinline__ bool sm_finite_positive(double x) { return x > 0. && x < __builtin_inf(); }
-
-__device__ __forceinline__ int64_t sm_clamp(int64_t x, int64_t lo, int64_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-__device__ __forceinline__ void sm_load3(const float* v, int64_t i, double* out) {
-  out[0] = v[3 * i]; out[1] = v[3 * i + 1]; out[2] = v[3 * i + 2];
-}
-
-__device__ __forceinline__ double sm_dot(const double* u, const double* w) { return u[0] * w[0] + u[1] * w[1] + u[2] * w[2]; }
-
-__device__ __forceinline__ void sm_cross(const double* u, const double* w, double* n) {
-  n[0] = u[1] * w[2] - u[2] * w[1];
-  n[1] = u[2] * w[0] - u[0] * w[2];
-  n[2] = u[0] * w[1] - u[1] * w[0];
-}
+#include "mesh_device.h"                                   // tri_valid, index_in, csr_range_ordered, load3, cross3, dot3, finite, finite_positive
 
 // The three corners of face `row` when it takes part: valid indices, finite corners and a cross product at the first corner
 // whose length is finite and > 0.
 __device__ __forceinline__ bool sm_face_corners(const float* v, int64_t V, const int64_t* row, double p[3][3]) {
-  if (!sm_tri_valid(row, V)) return false;
-  sm_load3(v, row[0], p[0]); sm_load3(v, row[1], p[1]); sm_load3(v, row[2], p[2]);
+  if (!tri_valid(row, V)) return false;
+  load3(v, row[0], p[0]); load3(v, row[1], p[1]); load3(v, row[2], p[2]);
 #pragma unroll
   for (int c = 0; c < 3; ++c)
-    if (!sm_finite(p[c][0]) || !sm_finite(p[c][1]) || !sm_finite(p[c][2])) return false;
+    if (!finite(p[c][0]) || !finite(p[c][1]) || !finite(p[c][2])) return false;
   const double u[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
   const double w[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
   double n[3];
-  sm_cross(u, w, n);
-  return sm_finite_positive(sqrt(sm_dot(n, n)));
+  cross3(u, w, n);
+  return finite_positive(sqrt(dot3(n, n)));
 }
 
 // 1/2 max(0, cot) of the angle at corner c (0..2) of the face with corners p, in the face's cyclic order; 0 when the cross
@@ -83,10 +62,10 @@ __device__ __forceinline__ double sm_half_cot(const double p[3][3], int c) {
   const double e1[3] = {p[a][0] - p[c][0], p[a][1] - p[c][1], p[a][2] - p[c][2]};
   const double e2[3] = {p[b][0] - p[c][0], p[b][1] - p[c][1], p[b][2] - p[c][2]};
   double n[3];
-  sm_cross(e1, e2, n);
-  const double len = sqrt(sm_dot(n, n));
-  if (!sm_finite_positive(len)) return 0.;
-  const double cot = sm_dot(e1, e2) / len;
+  cross3(e1, e2, n);
+  const double len = sqrt(dot3(n, n));
+  if (!finite_positive(len)) return 0.;
+  const double cot = dot3(e1, e2) / len;
   return cot > 0. ? 0.5 * cot : 0.;
 }
 
@@ -111,11 +90,12 @@ cotan_weights_kernel(const float* __restrict__ v, int64_t V, const int64_t* __re
   for (int64_t k = first; k < F; k += stride)
     if (!sm_face_corners(v, V, f + 3 * k, p)) atomicAdd(counts, 1);
   for (int64_t i = first; i < V; i += stride) {
-    const int64_t k1 = sm_clamp(off[i + 1], 0, nnz), k0 = sm_clamp(off[i], 0, k1);
+    const CsrRow nb = csr_range_ordered(off, i, nnz);
+    const int64_t k0 = nb.k0, k1 = nb.k1;
     for (int64_t k = k0; k < k1; ++k) w[k] = 0.;           // the row belongs to this thread alone
     if (n_vs <= 0) continue;
-    const int64_t end = sm_clamp(vs_off[i + 1], 0, n_vs);
-    for (int64_t s = sm_clamp(vs_off[i], 0, end); s < end; ++s) {
+    const CsrRow fan = csr_range_ordered(vs_off, i, n_vs);
+    for (int64_t s = fan.k0; s < fan.k1; ++s) {
       const int64_t slot = vs_idx[s];
       if ((uint64_t)slot >= (uint64_t)(3 * F)) continue;
       const int64_t face = slot / 3;
@@ -142,21 +122,22 @@ laplacian_step_kernel(const int32_t* __restrict__ off, const int32_t* __restrict
     bool move = !(fixed && fixed[i]);
     const int64_t b0 = bnbr ? bnbr[2 * i] : -1, b1 = bnbr ? bnbr[2 * i + 1] : -1;
     if (move && (b0 >= 0 || b1 >= 0)) {                    // boundary: along its own curve, or not at all
-      move = (uint64_t)b0 < (uint64_t)V && (uint64_t)b1 < (uint64_t)V;
+      move = index_in(b0, V) && index_in(b1, V);
       if (move) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) m[c] = 0.5 * ((double)x[3 * b0 + c] + (double)x[3 * b1 + c]);
       }
     } else if (move) {
-      const int64_t k1 = sm_clamp(off[i + 1], 0, nnz), k0 = sm_clamp(off[i], 0, k1);
+      const CsrRow nb = csr_range_ordered(off, i, nnz);
+      const int64_t k0 = nb.k0, k1 = nb.k1;
       double s[3] = {0., 0., 0.}, sum = 0.;
       int64_t cnt = 0;
       for (int64_t k = k0; k < k1; ++k) {
         const int64_t j = nbr[k];
-        if ((uint64_t)j >= (uint64_t)V) continue;
+        if (!index_in(j, V)) continue;
         if (w) {
           const double wk = w[k];
-          if (!sm_finite_positive(wk)) continue;           // (a weight of 0 adds nothing either way)
+          if (!finite_positive(wk)) continue;              // (a weight of 0 adds nothing either way)
 #pragma unroll
           for (int c = 0; c < 3; ++c) s[c] += wk * (double)x[3 * j + c];
           sum += wk;
@@ -167,7 +148,7 @@ laplacian_step_kernel(const int32_t* __restrict__ off, const int32_t* __restrict
         ++cnt;
       }
       if (!w) sum = (double)cnt;
-      move = cnt > 0 && sm_finite_positive(sum);
+      move = cnt > 0 && finite_positive(sum);
       if (move) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) m[c] = s[c] / sum;
@@ -185,24 +166,24 @@ face_normal_filter_kernel(const int32_t* __restrict__ off, const int32_t* __rest
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < F; i += stride) {
     double ni[3], ci[3];
-    sm_load3(n, i, ni);
+    load3(n, i, ni);
     ci[0] = cen[3 * i]; ci[1] = cen[3 * i + 1]; ci[2] = cen[3 * i + 2];
     const double a = area[i];
     double s[3] = {a * ni[0], a * ni[1], a * ni[2]};        // the face itself: both exponentials are 1
-    const int64_t k1 = sm_clamp(off[i + 1], 0, nnz);
-    for (int64_t k = sm_clamp(off[i], 0, k1); k < k1; ++k) {
+    const CsrRow nb = csr_range_ordered(off, i, nnz);
+    for (int64_t k = nb.k0; k < nb.k1; ++k) {
       const int64_t j = nbr[k];
       if ((uint64_t)j >= (uint64_t)F || j == i) continue;
       double nj[3];
-      sm_load3(n, j, nj);
+      load3(n, j, nj);
       const double dc[3] = {ci[0] - cen[3 * j], ci[1] - cen[3 * j + 1], ci[2] - cen[3 * j + 2]};
       const double dn[3] = {ni[0] - nj[0], ni[1] - nj[1], ni[2] - nj[2]};
-      const double wj = area[j] * exp(-(sm_dot(dc, dc) * inv2c)) * exp(-(sm_dot(dn, dn) * inv2s));
+      const double wj = area[j] * exp(-(dot3(dc, dc) * inv2c)) * exp(-(dot3(dn, dn) * inv2s));
 #pragma unroll
       for (int c = 0; c < 3; ++c) s[c] += wj * nj[c];
     }
-    const double len = sqrt(sm_dot(s, s));
-    const bool ok = sm_finite_positive(len);
+    const double len = sqrt(dot3(s, s));
+    const bool ok = finite_positive(len);
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[3 * i + c] = ok ? (float)(s[c] / len) : n[3 * i + c];
   }
@@ -215,25 +196,25 @@ vertex_from_normals_kernel(const float* __restrict__ x, int64_t V, const int64_t
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += stride) {
     double p[3];
-    sm_load3(x, i, p);
+    load3(x, i, p);
     double s[3] = {0., 0., 0.};
     int64_t cnt = 0;
     if (n_vs > 0 && !(fixed && fixed[i])) {
-      const int64_t end = sm_clamp(vs_off[i + 1], 0, n_vs);
-      for (int64_t t = sm_clamp(vs_off[i], 0, end); t < end; ++t) {
+      const CsrRow fan = csr_range_ordered(vs_off, i, n_vs);
+      for (int64_t t = fan.k0; t < fan.k1; ++t) {
         const int64_t slot = vs_idx[t];
-        if ((uint64_t)slot >= (uint64_t)(3 * F)) continue;
+        if (!index_in(slot, 3 * F)) continue;
         const int64_t face = slot / 3;
         const int64_t* row = f + 3 * face;
-        if (row[slot - 3 * face] != i || !sm_tri_valid(row, V)) continue;
+        if (row[slot - 3 * face] != i || !tri_valid(row, V)) continue;
         double nf[3], q[3][3];
-        sm_load3(n, face, nf);
-        sm_load3(x, row[0], q[0]); sm_load3(x, row[1], q[1]); sm_load3(x, row[2], q[2]);
+        load3(n, face, nf);
+        load3(x, row[0], q[0]); load3(x, row[1], q[1]); load3(x, row[2], q[2]);
         double d[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) d[c] = (q[0][c] + q[1][c] + q[2][c]) / 3. - p[c];
-        const double h = sm_dot(nf, d);
-        if (!sm_finite(h) || !sm_finite_positive(sm_dot(nf, nf))) continue;   // a corner or normal that is not finite, or no normal
+        const double h = dot3(nf, d);
+        if (!finite(h) || !finite_positive(dot3(nf, nf))) continue;   // a corner or normal that is not finite, or no normal
 #pragma unroll
         for (int c = 0; c < 3; ++c) s[c] += nf[c] * h;
         ++cnt;

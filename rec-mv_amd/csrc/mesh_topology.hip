@@ -43,6 +43,8 @@ constexpr int kTopoBlock = 256;
 constexpr int kSegChunk = 4096;                            // values of a segment one wave reduces in the first launch
 constexpr int kSegMaxCols = 8;
 
+#include "mesh_device.h"                                   // index_in, clamp_i64, length3
+
 // ---- connected components ----------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int32_t parent_load(const int32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -51,11 +53,12 @@ __device__ __forceinline__ void parent_store(int32_t* p, int32_t v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// K = 2 (a link) or 3 (a face) indices in [0, n), all distinct; for K = 3 mesh_device.h's tri_valid in another order of tests
 template <int K>
 __device__ __forceinline__ bool row_valid(const int64_t* row, int64_t n) {
 #pragma unroll
   for (int k = 0; k < K; ++k)
-    if ((uint64_t)row[k] >= (uint64_t)n) return false;
+    if (!index_in(row[k], n)) return false;
   if (row[0] == row[1]) return false;
   if (K == 3 && (row[0] == row[2] || row[1] == row[2])) return false;
   return true;
@@ -109,7 +112,7 @@ components_compress_kernel(int64_t n, int32_t* __restrict__ label, int32_t* pare
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < n; x += stride) {
     int32_t r = label[x];
-    while ((uint64_t)r < (uint64_t)n) {                    // r strictly decreases: at most r steps
+    while (index_in(r, n)) {                               // r strictly decreases: at most r steps
       const int32_t p = parent_load(parent + r);
       if (p >= r || p < 0) break;                          // a root
       const int32_t g = parent_load(parent + p);
@@ -125,8 +128,6 @@ __device__ __forceinline__ double corner_angle(double ux, double uy, double uz, 
   const double cx = uy * wz - uz * wy, cy = uz * wx - ux * wz, cz = ux * wy - uy * wx;
   return atan2(sqrt(cx * cx + cy * cy + cz * cz), ux * wx + uy * wy + uz * wz);
 }
-
-__device__ __forceinline__ double length3(double x, double y, double z) { return sqrt(x * x + y * y + z * z); }
 
 __global__ void __launch_bounds__(kTopoBlock)
 face_stats_kernel(const float* __restrict__ v, int64_t V, const int64_t* __restrict__ f, int64_t F, double* __restrict__ area,
@@ -192,8 +193,6 @@ __device__ __forceinline__ SegRed wave_reduce(const double* __restrict__ x, int6
   return r;
 }
 
-__device__ __forceinline__ int64_t clamp64(int64_t x, int64_t lo, int64_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
 // one wave per chunk: partial [max_chunks, C, 3] = (sum, min, max) of chunk w's values of column c
 __global__ void __launch_bounds__(kTopoBlock)
 segment_chunks_kernel(const double* __restrict__ values, int64_t N, int32_t C, const int64_t* __restrict__ offsets, int64_t S,
@@ -209,8 +208,8 @@ segment_chunks_kernel(const double* __restrict__ values, int64_t N, int32_t C, c
   const int64_t s = lo;
   const int64_t c = w - chunk_offsets[s];
   if (c < 0 || w >= chunk_offsets[s + 1]) return;          // (a table that is not the one the header describes)
-  const int64_t end = clamp64(offsets[s + 1], 0, N);
-  const int64_t first = clamp64(offsets[s], 0, end);
+  const int64_t end = clamp_i64(offsets[s + 1], 0, N);
+  const int64_t first = clamp_i64(offsets[s], 0, end);
   const int64_t b = c <= (end - first) / kSegChunk ? first + c * kSegChunk : end;
   const int64_t e = end - b > kSegChunk ? b + kSegChunk : end;
   for (int col = 0; col < C; ++col) {
@@ -230,8 +229,8 @@ segment_finish_kernel(const double* __restrict__ partial, int64_t max_chunks, in
   const int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
   const int lane = threadIdx.x % kWave;
   if (s >= S) return;
-  const int64_t e = clamp64(chunk_offsets[s + 1], 0, max_chunks);
-  const int64_t b = clamp64(chunk_offsets[s], 0, e);
+  const int64_t e = clamp_i64(chunk_offsets[s + 1], 0, max_chunks);
+  const int64_t b = clamp_i64(chunk_offsets[s], 0, e);
   for (int col = 0; col < C; ++col) {
     SegRed r{0., __builtin_inf(), -__builtin_inf()};
     for (int64_t i = b + lane; i < e; i += kWave) {

@@ -39,6 +39,7 @@ constexpr int kVoxWaves = kVoxBlock / kWave;               // faces per workgrou
 constexpr int64_t kVoxMaxNodes = 1ll << 28;                // marching cubes' limit
 
 #include "closest_tri.h"                                   // Tri, closest_st, load_tri
+#include "mesh_device.h"                                   // finite3
 
 struct Lat {
   float ox, oy, oz, step;
@@ -62,9 +63,6 @@ __device__ __forceinline__ bool node_range(float lo, float hi, float band, float
 
 __device__ __forceinline__ float min3(float a, float b, float c) { return fminf(a, fminf(b, c)); }
 __device__ __forceinline__ float max3(float a, float b, float c) { return fmaxf(a, fmaxf(b, c)); }
-__device__ __forceinline__ bool finite3(float a, float b, float c) {
-  return fabsf(a) < __builtin_inff() && fabsf(b) < __builtin_inff() && fabsf(c) < __builtin_inff();
-}
 
 __global__ void __launch_bounds__(kVoxBlock)
 voxel_band_kernel(const float* __restrict__ v, int64_t V, const int64_t* __restrict__ f, int64_t F, Lat L, float band,

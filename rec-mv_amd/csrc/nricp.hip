@@ -31,6 +31,7 @@ namespace {
 #pragma clang fp contract(off)
 
 #include "inv3x3_one.h"
+#include "mesh_device.h"                                   // csr_range, index_in, block_partials, reduce_slots
 
 constexpr int kKnnBlock = 256;
 constexpr int kKnnPer = 4;                                 // source points per lane
@@ -127,20 +128,6 @@ __device__ __forceinline__ void position(const EnergyArgs& a, int64_t i, float* 
   for (int r = 0; r < 3; ++r) v[r] = Am[3 * r] * x0 + Am[3 * r + 1] * x1 + Am[3 * r + 2] * x2 + bv[r];
 }
 
-// CSR range [k0, k1) of vertex i, clamped to the list's length
-__device__ __forceinline__ void csr_range(const int32_t* off, int64_t i, int64_t len, int64_t& k0, int64_t& k1) {
-  k0 = off[i];
-  k1 = off[i + 1];
-  if (k0 < 0) k0 = 0;
-  if (k1 > len) k1 = len;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
 // Laplacian row L_i v: (1/deg_i) sum_j v_j - v_i, or -v_i for an isolated vertex (pytorch3d's laplacian_packed)
 __device__ __forceinline__ void laplacian_row(const EnergyArgs& a, int64_t i, const float* vi, float* lv) {
   int64_t k0, k1;
@@ -149,7 +136,7 @@ __device__ __forceinline__ void laplacian_row(const EnergyArgs& a, int64_t i, co
   float s[3] = {0.f, 0.f, 0.f};
   for (int64_t k = k0; k < k1; ++k) {
     const int64_t j = a.nbr_idx[k];
-    if ((uint64_t)j >= (uint64_t)a.N) continue;
+    if (!index_in(j, a.N)) continue;
     float vj[3];
     position(a, j, vj);
 #pragma unroll
@@ -191,7 +178,7 @@ energy_forward_kernel(EnergyArgs a, uint8_t* __restrict__ mask, float* __restric
       const int64_t e = a.inc_edge[k];
       if ((uint64_t)e >= (uint64_t)a.E || a.edges[2 * e] != i) continue;
       const int64_t j = a.edges[2 * e + 1];
-      if ((uint64_t)j >= (uint64_t)a.N) continue;
+      if (!index_in(j, a.N)) continue;
       float s = 0.f;
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
@@ -213,10 +200,11 @@ energy_forward_kernel(EnergyArgs a, uint8_t* __restrict__ mask, float* __restric
 #pragma unroll
     for (int r = 0; r < 3; ++r) u[3 * i + r] = nrm > 0.f ? lv[r] / nrm : 0.f;
   }
+  // block_partials<3, kEnergyBlock> written out, the same sums in the same order: the call moves this kernel's schedule
   __shared__ double sh[3][kEnergyBlock / kWave];
-  acc_v = wave_sum_d(acc_v);
-  acc_s = wave_sum_d(acc_s);
-  acc_l = wave_sum_d(acc_l);
+  acc_v = wave_sum(acc_v);
+  acc_s = wave_sum(acc_s);
+  acc_l = wave_sum(acc_l);
   const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
   if (lane == 0) {
     sh[0][wave] = acc_v;
@@ -235,23 +223,9 @@ energy_forward_kernel(EnergyArgs a, uint8_t* __restrict__ mask, float* __restric
 __global__ void __launch_bounds__(kEnergyBlock)
 energy_reduce_kernel(const double* __restrict__ partials, int nslots, int64_t N, float stiffness_weight,
                      float laplacian_weight, float* __restrict__ scalars, float* __restrict__ factor) {
-  double acc[3] = {0., 0., 0.};
-  for (int s = threadIdx.x; s < nslots; s += kEnergyBlock) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) acc[k] += partials[3 * s + k];
-  }
-  __shared__ double sh[3][kEnergyBlock / kWave];
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double t = wave_sum_d(acc[k]);
-    if (lane == 0) sh[k][wave] = t;
-  }
-  __syncthreads();
+  double t[3];
+  reduce_slots<3, kEnergyBlock>(partials, nslots, t);
   if (threadIdx.x == 0) {
-    double t[3] = {0., 0., 0.};
-    for (int w = 0; w < kEnergyBlock / kWave; ++w)
-      for (int k = 0; k < 3; ++k) t[k] += sh[k][w];
     const float vert = (float)t[0];
     const float stiff = (float)(t[1] * (double)stiffness_weight);
     const float lap = (float)(t[2] / (double)N * (double)laplacian_weight);
@@ -289,7 +263,7 @@ energy_gradient_kernel(EnergyArgs a, const uint8_t* __restrict__ mask, const flo
     float gl[3] = {-u[3 * k], -u[3 * k + 1], -u[3 * k + 2]};
     for (int64_t t = k0; t < k1; ++t) {
       const int64_t i = a.nbr_idx[t];
-      if ((uint64_t)i >= (uint64_t)a.N) continue;
+      if (!index_in(i, a.N)) continue;
       const int32_t di = a.nbr_off[i + 1] - a.nbr_off[i];
       if (di <= 0) continue;
       const float w = 1.f / (float)di;
@@ -307,7 +281,7 @@ energy_gradient_kernel(EnergyArgs a, const uint8_t* __restrict__ mask, const flo
     csr_range(a.inc_off, k, 2 * a.E, k0, k1);
     for (int64_t t = k0; t < k1; ++t) {
       const int64_t e = a.inc_edge[t];
-      if ((uint64_t)e >= (uint64_t)a.E) continue;
+      if (!index_in(e, a.E)) continue;
       const int64_t e0 = a.edges[2 * e], e1 = a.edges[2 * e + 1];
       const int64_t j = e0 == k ? e1 : e0;
       if ((uint64_t)j >= (uint64_t)a.N || (e0 != k && e1 != k)) continue;

@@ -30,6 +30,8 @@ namespace {
 
 #pragma clang fp contract(off)
 
+#include "mesh_device.h"                                   // finite3, index_in, clamp_i64
+
 constexpr int kPointBlock = 256;
 constexpr int64_t kPointMaxCells = 1ll << 24;
 constexpr int32_t kPointMaxAxis = 1 << 20;
@@ -46,11 +48,6 @@ __device__ __forceinline__ int32_t cell_axis(double x, double o, double h, int32
   return (int32_t)t;
 }
 
-__device__ __forceinline__ bool finite3(double x, double y, double z) {
-  const double sum = x + y + z;                            // (a finite sum cannot hide an inf or a NaN; three f32 never overflow)
-  return sum - sum == 0.;
-}
-
 __global__ void __launch_bounds__(kPointBlock)
 points_cells_kernel(const float* __restrict__ v, int64_t V, PointGrid g, int32_t* __restrict__ cell) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -65,8 +62,6 @@ points_cells_kernel(const float* __restrict__ v, int64_t V, PointGrid g, int32_t
   }
 }
 
-__device__ __forceinline__ int64_t clamp_pos(int64_t x, int64_t lo, int64_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
 // kFill = false: out = counts [V]; kFill = true: out = pairs [P,2], offsets [V] the exclusive scan of the counts
 template <bool kFill>
 __global__ void __launch_bounds__(kPointBlock)
@@ -76,7 +71,7 @@ points_within_kernel(const float* __restrict__ pts, const int64_t* __restrict__ 
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) {
     const int64_t i = ids[t];
-    if ((uint64_t)i >= (uint64_t)V) continue;
+    if (!index_in(i, V)) continue;
     const double x = pts[3 * t], y = pts[3 * t + 1], z = pts[3 * t + 2];
     if (!finite3(x, y, z)) {                               // (the caller sorts finite vertices only)
       if (!kFill) out[i] = 0;
@@ -89,8 +84,8 @@ points_within_kernel(const float* __restrict__ pts, const int64_t* __restrict__ 
     for (int32_t zz = cz > 0 ? cz - 1 : 0; zz <= cz + 1 && zz < g.nz; ++zz) {
       for (int32_t yy = cy > 0 ? cy - 1 : 0; yy <= cy + 1 && yy < g.ny; ++yy) {
         const int64_t row = ((int64_t)zz * g.ny + yy) * g.nx;
-        const int64_t e = clamp_pos(cell_start[row + x1 + 1], 0, n);
-        const int64_t b = clamp_pos(cell_start[row + x0], 0, e);
+        const int64_t e = clamp_i64(cell_start[row + x1 + 1], 0, n);
+        const int64_t b = clamp_i64(cell_start[row + x0], 0, e);
         for (int64_t u = b; u < e; ++u) {
           const double dx = (double)pts[3 * u] - x, dy = (double)pts[3 * u + 1] - y, dz = (double)pts[3 * u + 2] - z;
           const double d2 = dx * dx + dy * dy + dz * dz;

@@ -203,6 +203,7 @@ segment_grid_kernel(const float* __restrict__ p, const float* __restrict__ q, in
       }
     }
   }
+  // (the minimum skips an empty lane's index -1, so it is not mesh_device.h's take_min; the count's group_sum stays in its loop)
 #pragma unroll
   for (int off = G / 2; off > 0; off >>= 1) {
     const float ob = __shfl_xor(best, off, G);

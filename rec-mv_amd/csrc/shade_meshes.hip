@@ -24,6 +24,8 @@ namespace {
 
 #pragma clang fp contract(off)
 
+#include "mesh_device.h"                                   // wave_sum, index_in
+
 constexpr float kNormEps = 1e-6f;      // F.normalize(eps=1e-6) of pytorch3d's normals and lighting directions
 constexpr int kShadeBlock = 256;
 
@@ -89,12 +91,6 @@ struct ShadeParams {
   float background[3];
 };
 
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
 // grid (x: pixel blocks of one frame, y: frame n).  pix_to_face [N,H,W] packed (mesh * F + face), bary [N,H,W,3].
 __global__ void __launch_bounds__(kShadeBlock)
 hard_phong_kernel(const int64_t* __restrict__ pix_to_face, const float* __restrict__ bary,
@@ -115,7 +111,7 @@ hard_phong_kernel(const int64_t* __restrict__ pix_to_face, const float* __restri
     if (fg) {
       const int64_t m = face / F, f = face - m * F;
       const int64_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-      if ((uint64_t)i0 < (uint64_t)V && (uint64_t)i1 < (uint64_t)V && (uint64_t)i2 < (uint64_t)V) {
+      if (index_in(i0, V) && index_in(i1, V) && index_in(i2, V)) {
         const float w0 = bary[3 * i], w1 = bary[3 * i + 1], w2 = bary[3 * i + 2];
         const float* vb = verts + m * V * 3;
         const float* nb = normals + m * V * 3;

@@ -36,11 +36,7 @@ constexpr int kMaxLevels = 7;
 constexpr double kFourPi = 12.566370614359172953850573533118;
 
 #include "solid_angle.h"
-
-__device__ __forceinline__ bool finite_query(float x, float y, float z) {
-  const float s = 0.f * x + 0.f * y + 0.f * z;
-  return s == s;
-}
+#include "mesh_device.h"                                   // finite3, index_in
 
 // partial[chunk * P + p] = the sum of the solid angles of the faces [chunk * kChunkFaces, min(F, (chunk + 1) * kChunkFaces))
 // seen from p, added in ascending face order in f64.
@@ -54,7 +50,7 @@ winding_exact_kernel(const float* __restrict__ p, int64_t P, const float* __rest
   float qx = 0.f, qy = 0.f, qz = 0.f;
   if (live) {
     qx = p[3 * q]; qy = p[3 * q + 1]; qz = p[3 * q + 2];
-    if (!finite_query(qx, qy, qz)) qx = qy = qz = __builtin_nanf("");
+    if (!finite3(qx, qy, qz)) qx = qy = qz = __builtin_nanf("");
   }
   const int64_t first = chunk * kChunkFaces;
   const int64_t last = first + kChunkFaces < F ? first + kChunkFaces : F;
@@ -133,7 +129,7 @@ winding_leaves_kernel(const float* __restrict__ v, int64_t V, const int64_t* __r
   for (int64_t i = i0; i < i1; ++i) {
     float t[9];
     const int64_t k = order[i];
-    if ((uint64_t)k >= (uint64_t)F) continue;                // no such face: its row of tris is left alone
+    if (!index_in(k, F)) continue;                           // no such face: its row of tris is left alone
     load_corners(v, f, V, k, t);
     for (int a = 0; a < 9; ++a) tris[9 * i + a] = t[a];
     node_add_face(s, t);
@@ -167,9 +163,9 @@ winding_tree_kernel(const float* __restrict__ p, int64_t P, const int64_t* __res
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= P) return;
   const int64_t q = order ? order[t] : t;
-  if ((uint64_t)q >= (uint64_t)P) return;                    // an order that is no permutation writes nothing out of bounds
+  if (!index_in(q, P)) return;                               // an order that is no permutation writes nothing out of bounds
   const float qx = p[3 * q], qy = p[3 * q + 1], qz = p[3 * q + 2];
-  if (!finite_query(qx, qy, qz)) {
+  if (!finite3(qx, qy, qz)) {
     w[q] = (double)__builtin_nanf("");
     return;
   }

@@ -57,6 +57,7 @@ import torch
 
 from . import _lib as L
 from .connectivity import EdgeTable
+from .topology import valid_faces
 
 MAX_LOOP_EDGES = 4096                                      # csrc/hole_fill.hip: kHoleMaxN
 LDS_MAX_EDGES = 85                                         # csrc/hole_fill.hip: kHoleLdsMaxN (64 KiB of LDS a loop)
@@ -86,15 +87,10 @@ def _check(verts, faces, cuda):
     return verts.contiguous(), faces.contiguous()
 
 
-def _valid(faces, V):
-    a, b, c = faces[:, 0], faces[:, 1], faces[:, 2]
-    return ((faces >= 0) & (faces < V)).all(1) & (a != b) & (b != c) & (a != c)
-
-
 def _find(verts, faces):
     """(loops: lists of vertex ids on the host, table, edge keys V * lo + hi of the valid faces, sorted)."""
     V, dev = verts.shape[0], faces.device
-    vf = faces[_valid(faces, V)].contiguous() if faces.shape[0] else faces
+    vf = faces[valid_faces(faces, V)].contiguous() if faces.shape[0] else faces
     table = EdgeTable(vf, V)
     keys = table.edges[:, 0] * max(V, 1) + table.edges[:, 1]
     if table.E and int(table.count.max()) > 2:

@@ -33,6 +33,7 @@ import torch
 from . import _lib as L
 from .connectivity import EdgeTable, boundary_edges_csr, compact, vertex_slots_csr
 from .iso_remesh import _Topo, _boundary_loop_length, _flip_ok, _independent, _link_ok, _merge, _padded
+from .smooth import _check_mesh
 
 BOUNDARY_WEIGHT = 10.       # a boundary edge's plane counts like 10 |e|^2 of face area
 REACH = 2.                  # the solved optimum must lie within this many edge lengths of the edge's midpoint
@@ -40,19 +41,6 @@ ROUND_SHARE = 0.5           # the share of the remaining face budget whose cheap
 MAX_ROUNDS = 1000
 FREE, STAY_A, STAY_B = 0, 1, 2
 _HINT = "run clean_fl.py or look at recmv.topology.report"
-
-
-def _check_mesh(verts, faces, cuda):
-    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("faces must be int64 of shape [F,3]")
-    if verts.dim() != 2 or verts.shape[1] != 3 or not verts.dtype.is_floating_point:
-        raise ValueError("verts must be floating point of shape [V,3]")
-    if verts.device != faces.device:
-        raise ValueError("verts and faces must be on one device")
-    if cuda:
-        L.require_cuda(verts, "verts")
-        if verts.dtype != torch.float32:
-            raise ValueError("verts must be float32")
 
 
 # ------------------------------------------------------------------------------------------------- kernels and restatements

@@ -205,7 +205,7 @@ def test_host_build_of_the_grid_kernel_equals_the_pair_loop(tmp_path):
         pytest.skip("ROCm's clang++ not present")
     csrc = REPO / "rec-mv_amd" / "csrc"
     for f in (REPO / "tools" / "mesh_grid_host_check" / "common.h", REPO / "tools" / "mesh_intersect_host_check" / "main.cpp",
-              csrc / "closest_tri.h", csrc / "grid_query.h", csrc / "tri_tri.h"):
+              csrc / "closest_tri.h", csrc / "grid_query.h", csrc / "tri_tri.h", csrc / "mesh_device.h"):
         shutil.copy(f, tmp_path)
     for src, dst in (("mesh_grid.hip", "grid.inc"), ("mesh_intersect.hip", "intersect.inc")):
         hip = (csrc / src).read_text()

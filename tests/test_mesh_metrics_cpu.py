@@ -192,7 +192,7 @@ def test_host_build_of_the_grid_kernels_returns_the_brute_force_bits(tmp_path):
         pytest.skip("ROCm's clang++ not present")
     src = REPO / "tools" / "mesh_grid_host_check"
     csrc = REPO / "rec-mv_amd" / "csrc"
-    for f in (src / "common.h", src / "main.cpp", csrc / "closest_tri.h", csrc / "grid_query.h"):
+    for f in (src / "common.h", src / "main.cpp", csrc / "closest_tri.h", csrc / "grid_query.h", csrc / "mesh_device.h"):
         shutil.copy(f, tmp_path)
     hip = (csrc / "mesh_grid.hip").read_text()
     cut = hip.index("\nusing namespace recmv;")

@@ -266,7 +266,8 @@ def test_host_build_of_the_kernels_under_the_sanitizers(tmp_path):
     if not Path(clang).exists():
         pytest.skip("ROCm's clang++ not present")
     tool = REPO / "tools" / "mesh_simplify_host_check"
-    for f in (REPO / "tools" / "mesh_grid_host_check" / "common.h", tool / "main.cpp"):
+    for f in (REPO / "tools" / "mesh_grid_host_check" / "common.h", tool / "main.cpp",
+              REPO / "rec-mv_amd" / "csrc" / "mesh_device.h"):
         shutil.copy(f, tmp_path)
     hip = (REPO / "rec-mv_amd" / "csrc" / "mesh_simplify.hip").read_text()
     (tmp_path / "simplify.inc").write_text(hip[:hip.index("\nusing namespace recmv;") + 1])

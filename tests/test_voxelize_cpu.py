@@ -310,7 +310,7 @@ def test_host_build_of_the_kernels_equals_the_brute_loop(tmp_path):
         pytest.skip("ROCm's clang++ not present")
     csrc = REPO / "rec-mv_amd" / "csrc"
     for src in (REPO / "tools" / "mesh_grid_host_check" / "common.h", REPO / "tools" / "voxelize_host_check" / "main.cpp",
-                csrc / "closest_tri.h", REPO / "include" / "recmv_hip.h"):
+                csrc / "closest_tri.h", csrc / "mesh_device.h", REPO / "include" / "recmv_hip.h"):
         shutil.copy(src, tmp_path)
     hip = (csrc / "mesh_voxelize.hip").read_text()
     (tmp_path / "voxelize.inc").write_text(hip[:hip.index("\nusing namespace recmv;") + 1])

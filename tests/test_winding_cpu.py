@@ -282,7 +282,7 @@ def test_host_build_of_the_kernels_equals_the_brute_loops(tmp_path):
         pytest.skip("ROCm's clang++ not present")
     csrc = REPO / "rec-mv_amd" / "csrc"
     for src in (REPO / "tools" / "mesh_grid_host_check" / "common.h", REPO / "tools" / "winding_host_check" / "main.cpp",
-                csrc / "solid_angle.h", REPO / "include" / "recmv_hip.h"):
+                csrc / "solid_angle.h", csrc / "mesh_device.h", REPO / "include" / "recmv_hip.h"):
         shutil.copy(src, tmp_path)
     hip = (csrc / "winding.hip").read_text()
     (tmp_path / "winding.inc").write_text(hip[:hip.index("\nusing namespace recmv;") + 1])

@@ -188,7 +188,7 @@ static int check(const char* name, const Mesh& m, int levels, float ox, float oy
   for (int64_t t = 0; t < P; ++t) {
     double sum = 0.;
     float qx = q[3 * t], qy = q[3 * t + 1], qz = q[3 * t + 2];
-    if (!finite_query(qx, qy, qz)) qx = qy = qz = NAN;
+    if (!finite3(qx, qy, qz)) qx = qy = qz = NAN;
     for (int64_t k = 0; k < F; ++k) {
       float c[9];
       load_corners(m.v.data(), m.f.data(), V, k, c);
@@ -208,7 +208,7 @@ static int check(const char* name, const Mesh& m, int levels, float ox, float oy
     for (int64_t t = 0; t < P; ++t) {
       Walk walk{levels, nodes.data(), cell_start.data(), tris.data(), q[3 * t], q[3 * t + 1], q[3 * t + 2], beta * beta, 0.};
       double want = NAN;
-      if (finite_query(walk.qx, walk.qy, walk.qz)) {
+      if (finite3(walk.qx, walk.qy, walk.qz)) {
         walk.visit(0, 0, 0, 0);
         want = walk.sum / kFourPi;
       }
@@ -229,7 +229,7 @@ static int check(const char* name, const Mesh& m, int levels, float ox, float oy
   for (blockIdx.x = 0; blockIdx.x < (unsigned)P + 2; ++blockIdx.x) winding_reduce_kernel(partial.data(), chunks, P, w.data());
   for (int64_t t = 0; t < P; ++t) {
     float qx = q[3 * t], qy = q[3 * t + 1], qz = q[3 * t + 2];
-    if (!finite_query(qx, qy, qz)) qx = qy = qz = NAN;
+    if (!finite3(qx, qy, qz)) qx = qy = qz = NAN;
     double total = 0.;
     for (int64_t c = 0; c < chunks; ++c) {
       double sum = 0.;
