@@ -45,7 +45,9 @@ extern "C" {
  *        recmv_hole_fill_auto_max_edges, recmv_hole_fill_max_edges (hole filling: pure additions, still v11);
  *        recmv_winding_chunk_faces, recmv_winding_exact_workspace_bytes, recmv_winding_exact, recmv_winding_tree_nodes,
  *        recmv_winding_tree_cells, recmv_winding_tree_build, recmv_winding_tree_query with the recmv_winding_tree descriptor
- *        (generalized winding numbers: pure additions, still v11).
+ *        (generalized winding numbers: pure additions, still v11); recmv_geodesic_lds_max_vertices,
+ *        recmv_geodesic_auto_max_vertices, recmv_geodesic_workspace_bytes, recmv_geodesic_check_sources, recmv_geodesic_sweeps,
+ *        recmv_geodesic_lds (geodesic distance fields: pure additions, still v11).
  *   v10: recmv_verts_normals, recmv_hard_phong_shade, recmv_hard_phong_params_floats added.  Added since without a bump (no
  *        existing signature changed, and _lib.py rejects a library that lacks them): recmv_knn1, recmv_nricp_energy,
  *        recmv_lap_align_solve, recmv_lap_smooth, recmv_closest_point, recmv_iso_relax, recmv_loop_subdivide,
@@ -1175,6 +1177,55 @@ int recmv_winding_tree_build(const float* verts, int64_t V, const int64_t* faces
                              const recmv_winding_tree* tree, void* stream);
 int recmv_winding_tree_query(const float* p, int64_t P, const int64_t* order, const recmv_winding_tree* tree, float beta,
                              double* w, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Geodesic distance fields (csrc/geodesic.hip; added to ABI v11, no existing signature changed).  Not in the reference.  The
+ * kernels of recmv/geodesic.py: B independent fields D [B, V] f64 over one triangle mesh (verts [V,3] f32, faces [F,3] int64).
+ * Definition.  A face is usable when its three indices lie in [0, V) and are distinct and its nine coordinates are finite.
+ *   For a vertex v in a usable face whose next corner (in the face's row, cyclically) is a and the one after b, with the
+ *   current values Da = D(a), Db = D(b), the first-order Hopf-Lax candidate is
+ *     U(v; a, b) = min over t in [0, 1] of (1 - t) Da + t Db + |v - ((1 - t) a + t b)|
+ *   computed in float64 on the f32 coordinates widened to f64, un-contracted, in exactly this order (x, y, z components; a
+ *   3-sum is (p + q) + r; |x| = sqrt((x0 x0 + x1 x1) + x2 x2); sqrt and / correctly rounded):
+ *     w = v - a,  u = v - b,  la = |w|,  lb = |u|,  ca = Da + la,  cb = Db + lb,  U = cb < ca ? cb : ca
+ *     when Da < inf and Db < inf:   e = b - a,  L2 = (e0 e0 + e1 e1) + e2 e2,  L = sqrt(L2),  delta = Db - Da
+ *       when L > 0 and |delta| < L:   n = w x e = (w1 e2 - w2 e1, w2 e0 - w0 e2, w0 e1 - w1 e0),  h = |n| / L
+ *         (the distance of v from the line ab, by the cross product: it does not cancel as la^2 - t0^2 L2 would)
+ *         when h > 0:   t0 = ((w0 e0 + w1 e1) + w2 e2) / L2,   ts = t0 - (delta h) / (L sqrt(L2 - delta delta))
+ *           when 0 < ts < 1 (false for a ts that is not finite):   r = ts - t0,
+ *             ci = (Da + ts delta) + sqrt(h h + L2 (r r)),   U = ci < U ? ci : U
+ *   D^0 is +inf except at the sources; D^{k+1}(v) = min(D^k(v), min over the usable faces of v of U), every U of sweep k + 1
+ *   reading D^k only (Jacobi: the minimum does not depend on the order of a vertex's faces, and no update is seen early, so
+ *   no bit depends on scheduling).  The answer is D^K for the least K with D^{K+1} = D^K; K is the number of sweeps.  A
+ *   vertex that no usable face reaches from a source stays +inf.  In exact arithmetic K <= V.
+ * The slot table: slot_offsets [V + 1] and slots int64: row v lists the corner slots 3 f + c with faces[f][c] = v (recmv.
+ *   connectivity.vertex_slots_csr).  Every entry is checked against the faces; a wrong table costs wrong values only.
+ * recmv_geodesic_check_sources: sources [S] int64 and values [S] f64 (or NULL: all 0) in HOST memory: RECMV_ERR_ARG with a
+ *   message for a source outside [0, V) or a value that is not finite.  No HIP call at all.
+ * recmv_geodesic_sweeps (any size): the workspace, recmv_geodesic_workspace_bytes(V, F, B) bytes, 8-byte aligned, is
+ *   D [2][B][V] f64 | changed [2][align8(B V)] u8 | last_changed [B] int32 (padded to 8 bytes).  The caller writes D^0 into
+ *   D[0]; a call runs the sweeps k0 + 1 .. k0 + n, one launch each in stream order, sweep k reading D[(k - 1) & 1] and writing
+ *   D[k & 1]; the call with k0 = 0 first marks every vertex changed and clears last_changed.  A thread that lowers a value
+ *   in sweep k stores k into last_changed[b] (every writer of a launch stores the same number).  After sweeps 1 .. m the
+ *   field has converged when last_changed[b] < m, and then K = last_changed[b]; further sweeps change nothing.
+ * recmv_geodesic_lds (V <= recmv_geodesic_lds_max_vertices() = 3640): one workgroup per field runs sweeps until one lowers
+ *   nothing, D0 [B][V] -> D [B][V], sweeps [B] int32 = K, or -1 (D then holds sweep max_sweeps + 1) when sweep
+ *   max_sweeps + 1 still lowered a value.  recmv_geodesic_auto_max_vertices(): up to this V recmv.geodesic's route 'auto'
+ *   takes this route (measured, csrc/geodesic.hip).
+ * Both routes give the bits of the definition and the same K.  Argument errors (negative sizes, sizes of 2^31 or more, NULL
+ * pointers with non-zero sizes, a short or misaligned workspace, V above the lds capacity, k0, n or max_sweeps outside
+ * 0 .. 2^30) return RECMV_ERR_ARG before any HIP call; V = 0 or B = 0 is a no-op.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t recmv_geodesic_lds_max_vertices(void);
+int64_t recmv_geodesic_auto_max_vertices(void);
+int64_t recmv_geodesic_workspace_bytes(int64_t V, int64_t F, int64_t B);
+int recmv_geodesic_check_sources(const int64_t* sources, const double* values, int64_t S, int64_t V);
+int recmv_geodesic_sweeps(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* slot_offsets,
+                          const int64_t* slots, int64_t B, void* workspace, int64_t workspace_bytes, int64_t k0, int64_t n,
+                          void* stream);
+int recmv_geodesic_lds(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* slot_offsets,
+                       const int64_t* slots, int64_t B, const double* D0, double* D, int32_t* sweeps, int64_t max_sweeps,
+                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -43,11 +43,20 @@ holds the `reason`, and they have no `mean`.
         [--align none|rigid|similarity [--align-metric plane|point] [--align-trim f] [--align-iters n]
          [--align-from each|first] [--align-out DIR]] [--drop-floaters FRAC] [--topology] [--repair] [--weld-eps E]
         [--volume [--volume-step S] [--voxel-sign parity|winding]] [--inside-rule parity|winding] [--fill-holes [--fill-max-edges N] [--fill-keep-largest K]]
+        [--boundary-bands W1,W2,...]
 
 `--fill-holes` closes the holes of the prediction AND the ground truth after `--repair` and before every metric
 (recmv.holes.fill: least-area patches; `--fill-max-edges N` leaves loops of more than N edges open, `--fill-keep-largest K` the
 K longest), so that `--volume` has something to measure on scans with missing patches; the two calls' info goes into the pair's
 entry as `holes_pred` and `holes_gt`.
+
+`--boundary-bands W1,W2,...` (ascending, positive, finite widths) reports the error where the method claims to be right: at the
+feature curves.  Every pair gets a `boundary_bands` entry: the prediction's samples (those of surface_distance: same seed, same
+points) are binned by their geodesic distance ALONG the prediction to the prediction's own border (recmv.geodesic.
+boundary_distance, interpolated at each sample on its source face) into [0, W1), [W1, W2), ..., [Wn, inf), and every bin
+reports its `count` and the `mean`, `rms` and `max` of the samples' distance to the ground truth (None for an empty bin); the
+same for the ground truth's samples, binned along the ground truth, against the prediction.  A side whose mesh has no border is
+None with the reason "closed".  Every other key of the pair keeps its value bit for bit.
 """
 import argparse
 import json
@@ -105,7 +114,51 @@ def build_parser():
                         help='with --penetration: how a vertex is judged inside the body; winding takes a body with holes')
     parser.add_argument('--volume-step', default=None, type=float, metavar='S',
                         help='with --volume: the lattice step (default: 129 nodes along the longest axis of the pair\'s box)')
+    parser.add_argument('--boundary-bands', default=None, metavar='W1,W2,...',
+                        help='per pair, the error binned by geodesic distance to the border (ascending widths)')
     return parser
+
+
+def parse_bands(text):
+    """'W1,W2,...' -> the widths as floats: at least one, ascending, positive, finite.  ValueError otherwise."""
+    try:
+        widths = [float(t) for t in text.split(',')]
+    except ValueError:
+        raise ValueError("--boundary-bands takes numbers separated by commas (got %r)" % (text,))
+    if not widths or not all(0. < w < float('inf') for w in widths):
+        raise ValueError("--boundary-bands: the widths must be positive and finite (got %r)" % (text,))
+    if any(b <= a for a, b in zip(widths, widths[1:])):
+        raise ValueError("--boundary-bands: the widths must ascend (got %r)" % (text,))
+    return widths
+
+
+def band_stats(g, d, widths):
+    """The samples with geodesic border distance g [P] and error d [P] (tensors) binned by g into [0, W1), [W1, W2), ...,
+    [Wn, inf): a list of {'lo', 'hi', 'count', 'mean', 'rms', 'max'} (hi None for the last; None figures for an empty bin).
+    A sample whose g is +inf (no border reaches it) falls into the last bin; one whose g is NaN into none."""
+    import torch
+    g, d = g.double(), d.double()
+    edges = [0.] + list(widths) + [float('inf')]
+    out = []
+    for k, (lo, hi) in enumerate(zip(edges, edges[1:])):
+        last = k == len(edges) - 2
+        x = d[(g >= lo) & ((g <= hi) if last else (g < hi))]
+        n = int(x.shape[0])
+        out.append({'lo': lo, 'hi': None if last else hi, 'count': n,
+                    'mean': float(x.mean()) if n else None, 'rms': float((x * x).mean().sqrt()) if n else None,
+                    'max': float(x.max()) if n else None})
+    return out
+
+
+def boundary_bands(side_v, side_f, points, src_face, other_v, other_f, widths, method):
+    """One side of a pair's `boundary_bands`: (bands, reason) — (None, "closed") for a mesh without a border."""
+    from recmv import geodesic, metrics
+    field = geodesic.boundary_distance(side_v, side_f)
+    if not bool((field == 0.).any()):
+        return None, 'closed'
+    g = geodesic.interpolate(field, side_v, side_f, src_face, points)
+    d = metrics._nearest(points, other_v, other_f, method)[2].double().sqrt()
+    return band_stats(g, d, widths), None
 
 
 def _objs(path):
@@ -134,6 +187,12 @@ def pair_files(pred, gt):
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    widths = None
+    if args.boundary_bands is not None:
+        try:
+            widths = parse_bands(args.boundary_bands)
+        except ValueError as e:
+            parser.error(str(e))
     try:
         pairs, only_pred, only_gt = pair_files(args.pred, args.gt)
     except ValueError as e:
@@ -238,7 +297,13 @@ def main(argv=None):
         sequence.append((pv, pfaces))
         per_pair[stem] = metrics.surface_distance(pv.to(device), pfaces.to(device), gv.to(device), gfaces.to(device),
                                                   samples=args.samples, seed=args.seed, thresholds=thresholds,
-                                                  method=args.method)
+                                                  method=args.method, return_samples=widths is not None)
+        if widths is not None:
+            per_pair[stem], drawn = per_pair[stem]
+            dv, df, ev, ef = pv.to(device), pfaces.to(device), gv.to(device), gfaces.to(device)
+            bp, why_p = boundary_bands(dv, df, drawn['pred'][0], drawn['pred'][1], ev, ef, widths, args.method)
+            bg, why_g = boundary_bands(ev, ef, drawn['gt'][0], drawn['gt'][1], dv, df, widths, args.method)
+            per_pair[stem]['boundary_bands'] = {'widths': widths, 'pred': bp, 'pred_reason': why_p, 'gt': bg, 'gt_reason': why_g}
         if args.intersections:
             own = metrics.self_intersections(pv.to(device), pfaces.to(device), method=args.method)
             own_gt = metrics.self_intersections(gv.to(device), gfaces.to(device), method=args.method)

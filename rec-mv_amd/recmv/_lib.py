@@ -248,6 +248,12 @@ def _declare(lib):
         "recmv_winding_tree_cells": (C.c_int, [vp, i64, vp, i64, WT, vp, vp]),
         "recmv_winding_tree_build": (C.c_int, [vp, i64, vp, i64, vp, WT, vp]),
         "recmv_winding_tree_query": (C.c_int, [vp, i64, vp, WT, f32, vp, vp]),
+        "recmv_geodesic_lds_max_vertices": (i64, []),
+        "recmv_geodesic_auto_max_vertices": (i64, []),
+        "recmv_geodesic_workspace_bytes": (i64, [i64, i64, i64]),
+        "recmv_geodesic_check_sources": (C.c_int, [vp, vp, i64, i64]),
+        "recmv_geodesic_sweeps": (C.c_int, [vp, i64, vp, i64, vp, vp, i64, vp, i64, i64, i64, vp]),
+        "recmv_geodesic_lds": (C.c_int, [vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)       # AttributeError if the symbol is missing: fail loudly
