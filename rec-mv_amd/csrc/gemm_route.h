@@ -1,7 +1,7 @@
 // Which kernel a recmv_gemm_nt* / recmv_gemm_tn launch gets: the one place where the routes of gemm_f32.hip and gemm_tn.hip are decided.
 //
-// Pure host code over standard headers only (no HIP): tools/gemm_route_host_check compiles it with a plain C++ compiler and
-// tests/test_gemm_route_cpu.py compares its plans with the census of tests/golden/gemm_routes.json.
+// Pure host code over standard headers only (no HIP): tools/gemm_route_host_check compiles it with a plain C++ compiler
+// (tests/host_check.py) and tests/test_gemm_route_cpu.py compares its plans with the census of tests/golden/gemm_routes.json.
 //
 // The invariant the planner keeps: a launch that one of the later kernels takes (the thin kernels for K <= 4 / N <= 4 / a TN output of
 // <= 4 rows or columns, the SCAL kernels for unaligned operands) keeps the bits and the profile slot of the MFMA kernel that took it

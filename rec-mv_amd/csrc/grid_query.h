@@ -1,7 +1,7 @@
 // The uniform grid over a triangle mesh: what its binning (mesh_grid.hip) and every query on it (mesh_grid.hip's closest
 // point, mesh_intersect.hip's triangle pairs, segment_mesh.hip's segments) must compute alike, and the plumbing the queries
 // share.  Include it inside namespace recmv after `#pragma clang fp contract(off)`, like closest_tri.h.  Device code only: no
-// RECMV_REQUIRE and no HIP calls, so that the host checks of tools/ compile it under tools/mesh_grid_host_check/common.h.
+// RECMV_REQUIRE and no HIP calls, so that the host checks of tools/ compile it under tools/host_check/common.h.
 #pragma once
 #include "closest_tri.h"                                   // Tri, for the triangle table
 #include "mesh_device.h"                                   // index_in

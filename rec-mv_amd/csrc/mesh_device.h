@@ -2,8 +2,8 @@
 // CSR rows, index tests and the f64 3-vector helpers, shared so that every mesh operation compiles the one body.  Include
 // it inside namespace recmv after `#pragma clang fp contract(off)`, like closest_tri.h: a helper defined before the pragma
 // would be compiled with contraction on, and its f64 products would fuse.  Device code only: no RECMV_REQUIRE and no HIP
-// calls, so that the host checks of tools/ compile it under tools/mesh_grid_host_check/common.h (kWave = 1, __shfl_xor the
-// identity).
+// calls, so that the host checks of tools/ compile it under tools/host_check/common.h (kWave = 1, __shfl_xor the identity);
+// tests/host_check.py refuses an includer that breaks the pragma rule.
 #pragma once
 
 // ---- indices ---------------------------------------------------------------------------------------------------------------

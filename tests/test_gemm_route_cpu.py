@@ -14,8 +14,8 @@ HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
 sys.path[:0] = [str(HERE)]
 import gemm_route_cases as GC  # noqa: E402
+import host_check  # noqa: E402
 
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 BM = BN = 128
 BK = 32
 N_CU = 256
@@ -29,16 +29,11 @@ def census():
 @pytest.fixture(scope="module")
 def plans(tmp_path_factory):
     """{setting: {case name: the fields the program printed}}"""
-    if not Path(CLANG).exists():
-        pytest.skip("ROCm's clang++ not present")
-    tmp = tmp_path_factory.mktemp("gemm_route_host_check")
-    subprocess.run([CLANG, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Werror",
-                    "-I" + str(REPO / "rec-mv_amd" / "csrc"), str(REPO / "tools" / "gemm_route_host_check" / "main.cpp"), "-o",
-                    str(tmp / "check")], check=True)
+    check = host_check.build("gemm_route", tmp_path_factory.mktemp("gemm_route_host_check"))
     out = {}
     for setting in GC.SETTINGS:
         text = "".join(GC.host_line(c, setting) + "\n" for c in GC.CASES)
-        r = subprocess.run([str(tmp / "check")], input=text, capture_output=True, text=True)
+        r = subprocess.run([str(check)], input=text, capture_output=True, text=True)
         assert r.returncode == 0, r.stdout + r.stderr
         rows = [ln.split("\t") for ln in r.stdout.splitlines()]
         out[setting] = {row[0]: row[1:] for row in rows}

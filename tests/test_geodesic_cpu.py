@@ -16,6 +16,7 @@ REPO = HERE.parent
 sys.path[:0] = [str(HERE), str(REPO / "rec-mv_amd")]
 import geodesic_cases as GC  # noqa: E402
 import geodesic_reference as GR  # noqa: E402
+import host_check  # noqa: E402
 
 INF = float("inf")
 NAMES = ["recmv_geodesic_lds_max_vertices", "recmv_geodesic_auto_max_vertices", "recmv_geodesic_workspace_bytes",
@@ -318,21 +319,7 @@ def test_boundary_bands_binning():
 def test_host_build_of_the_kernels_equals_the_plain_loops(tmp_path):
     """tools/geodesic_host_check: csrc/geodesic.hip's kernels compiled for the CPU under the address and undefined-behaviour
     sanitizers, both routes against loops that evaluate every face in every sweep, bit for bit, on seven inputs."""
-    import shutil
-    import subprocess
-    clang = "/opt/rocm/lib/llvm/bin/clang++"
-    if not Path(clang).exists():
-        pytest.skip("ROCm's clang++ not present")
-    csrc = REPO / "rec-mv_amd" / "csrc"
-    for src in (REPO / "tools" / "mesh_grid_host_check" / "common.h", REPO / "tools" / "geodesic_host_check" / "main.cpp",
-                csrc / "mesh_device.h", REPO / "include" / "recmv_hip.h"):
-        shutil.copy(src, tmp_path)
-    hip = (csrc / "geodesic.hip").read_text()
-    assert "#pragma clang fp contract(off)\n#include \"mesh_device.h\"" in hip
-    (tmp_path / "geodesic.inc").write_text(hip[:hip.index("\nusing namespace recmv;") + 1])
-    subprocess.run([clang, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-ffp-contract=off", "-I.", "main.cpp", "-o", "check"], cwd=tmp_path, check=True)
-    r = subprocess.run([str(tmp_path / "check")], cwd=tmp_path, capture_output=True, text=True)
+    r = host_check.run("geodesic", tmp_path)
     print(r.stdout)
     assert r.returncode == 0 and "all ok" in r.stdout and r.stdout.count("-> 0 mismatches") == 7, r.stdout + r.stderr
     for name in ("invalid faces and a NaN vertex: 37 vertices, 56 faces, 1 fields, K 9, 36 values finite",

@@ -25,6 +25,7 @@ import torch
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
 sys.path[:0] = [str(HERE), str(REPO / "rec-mv_amd")]
+import host_check  # noqa: E402
 import mesh_intersect_reference as XR  # noqa: E402
 
 EPS32 = 2.0 ** -23
@@ -198,21 +199,7 @@ def test_host_build_of_the_grid_kernel_equals_the_pair_loop(tmp_path):
     """tools/mesh_intersect_host_check: csrc/mesh_intersect.hip's one-lane grid kernel (count, fill, a fill with half the
     capacity) compiled for the CPU under the address and undefined-behaviour sanitizers, against a double loop over the pair
     test of the brute force, on eight meshes and grids."""
-    import shutil
-    import subprocess
-    clang = "/opt/rocm/lib/llvm/bin/clang++"
-    if not Path(clang).exists():
-        pytest.skip("ROCm's clang++ not present")
-    csrc = REPO / "rec-mv_amd" / "csrc"
-    for f in (REPO / "tools" / "mesh_grid_host_check" / "common.h", REPO / "tools" / "mesh_intersect_host_check" / "main.cpp",
-              csrc / "closest_tri.h", csrc / "grid_query.h", csrc / "tri_tri.h", csrc / "mesh_device.h"):
-        shutil.copy(f, tmp_path)
-    for src, dst in (("mesh_grid.hip", "grid.inc"), ("mesh_intersect.hip", "intersect.inc")):
-        hip = (csrc / src).read_text()
-        (tmp_path / dst).write_text(hip[:hip.index("\nusing namespace recmv;") + 1])
-    subprocess.run([clang, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-ffp-contract=off", "-I.", "main.cpp", "-o", "check"], cwd=tmp_path, check=True)
-    r = subprocess.run([str(tmp_path / "check")], cwd=tmp_path, capture_output=True, text=True)
+    r = host_check.run("mesh_intersect", tmp_path)
     print(r.stdout)
     assert r.returncode == 0 and "all ok" in r.stdout and r.stdout.count(" 0 mismatches") == 8, r.stdout + r.stderr
 

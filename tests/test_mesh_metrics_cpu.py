@@ -14,6 +14,7 @@ HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
 sys.path[:0] = [str(HERE), str(REPO / "rec-mv_amd")]
 import collide_reference as CR  # noqa: E402
+import host_check  # noqa: E402
 import mesh_metrics_reference as MR  # noqa: E402
 
 
@@ -183,22 +184,10 @@ def test_one_validator_rejects_a_malformed_descriptor_alike_in_every_entry_point
 
 
 def test_host_build_of_the_grid_kernels_returns_the_brute_force_bits(tmp_path):
-    """tools/mesh_grid_host_check: csrc/mesh_grid.hip's count, fill and one-lane query kernels compiled for the CPU against a
-    brute force with the same closest_tri.h and grid_query.h, bit for bit, on seven meshes and grids."""
-    import shutil
-    import subprocess
-    clang = "/opt/rocm/lib/llvm/bin/clang++"
-    if not Path(clang).exists():
-        pytest.skip("ROCm's clang++ not present")
-    src = REPO / "tools" / "mesh_grid_host_check"
-    csrc = REPO / "rec-mv_amd" / "csrc"
-    for f in (src / "common.h", src / "main.cpp", csrc / "closest_tri.h", csrc / "grid_query.h", csrc / "mesh_device.h"):
-        shutil.copy(f, tmp_path)
-    hip = (csrc / "mesh_grid.hip").read_text()
-    cut = hip.index("\nusing namespace recmv;")
-    (tmp_path / "kernels.inc").write_text(hip[:cut + 1])
-    subprocess.run([clang, "-std=c++17", "-O2", "-ffp-contract=off", "-I.", "main.cpp", "-o", "check"], cwd=tmp_path, check=True)
-    r = subprocess.run([str(tmp_path / "check")], cwd=tmp_path, capture_output=True, text=True)
+    """tools/mesh_grid_host_check: csrc/mesh_grid.hip's count, fill and one-lane query kernels compiled for the CPU under the
+    address and undefined-behaviour sanitizers against a brute force with the same closest_tri.h and grid_query.h, bit for bit,
+    on seven meshes and grids."""
+    r = host_check.run("mesh_grid", tmp_path)
     print(r.stdout)
     assert r.returncode == 0 and "all ok" in r.stdout and r.stdout.count(" 0 mismatches") == 7, r.stdout + r.stderr
 

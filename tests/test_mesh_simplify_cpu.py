@@ -13,6 +13,7 @@ import torch
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
 sys.path[:0] = [str(HERE), str(REPO / "rec-mv_amd")]
+import host_check  # noqa: E402
 import mesh_simplify_cases as SC  # noqa: E402
 import mesh_simplify_reference as SR  # noqa: E402
 import mesh_topology_cases as TC  # noqa: E402
@@ -260,20 +261,7 @@ def test_host_build_of_the_kernels_under_the_sanitizers(tmp_path):
     """tools/mesh_simplify_host_check: csrc/mesh_simplify.hip's kernels compiled for the CPU under the address and
     undefined-behaviour sanitizers, a stand-alone program: rows of 0, 1, 63, 64, 65 and 257 faces at one vertex, E = 0, 1, 255,
     256, 257, quadrics of rank 0 to 3, invalid faces and edges, a NaN corner, and tables filled with random numbers."""
-    import shutil
-    import subprocess
-    clang = "/opt/rocm/lib/llvm/bin/clang++"
-    if not Path(clang).exists():
-        pytest.skip("ROCm's clang++ not present")
-    tool = REPO / "tools" / "mesh_simplify_host_check"
-    for f in (REPO / "tools" / "mesh_grid_host_check" / "common.h", tool / "main.cpp",
-              REPO / "rec-mv_amd" / "csrc" / "mesh_device.h"):
-        shutil.copy(f, tmp_path)
-    hip = (REPO / "rec-mv_amd" / "csrc" / "mesh_simplify.hip").read_text()
-    (tmp_path / "simplify.inc").write_text(hip[:hip.index("\nusing namespace recmv;") + 1])
-    subprocess.run([clang, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-ffp-contract=off", "-I.", "main.cpp", "-o", "check"], cwd=tmp_path, check=True)
-    r = subprocess.run([str(tmp_path / "check")], cwd=tmp_path, capture_output=True, text=True)
+    r = host_check.run("mesh_simplify", tmp_path)
     print(r.stdout)
     assert r.returncode == 0 and "all ok" in r.stdout and "WRONG" not in r.stdout, r.stdout + r.stderr
     assert r.stdout.count(" 0 mismatches") == 30

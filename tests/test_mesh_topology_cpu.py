@@ -13,6 +13,7 @@ import torch
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
 sys.path[:0] = [str(HERE), str(REPO / "rec-mv_amd")]
+import host_check  # noqa: E402
 import mesh_topology_cases as TC  # noqa: E402
 import mesh_topology_reference as TR  # noqa: E402
 
@@ -264,20 +265,7 @@ def test_host_build_of_the_kernels_equals_union_find(tmp_path):
     round counts a plain restatement of the synchronous algorithm and stay within 2 ceil(log2 n) + 2, on the link sets of the
     GPU test, on paths numbered ascending, descending and randomly, and on empty input; the face figures and the segment sums
     equal plain loops, and tables that are not what the header describes stay inside the arrays."""
-    import shutil
-    import subprocess
-    clang = "/opt/rocm/lib/llvm/bin/clang++"
-    if not Path(clang).exists():
-        pytest.skip("ROCm's clang++ not present")
-    tool = REPO / "tools" / "mesh_topology_host_check"
-    for f in (REPO / "tools" / "mesh_grid_host_check" / "common.h", tool / "topology_shims.h", tool / "main.cpp",
-              REPO / "rec-mv_amd" / "csrc" / "mesh_device.h"):
-        shutil.copy(f, tmp_path)
-    hip = (REPO / "rec-mv_amd" / "csrc" / "mesh_topology.hip").read_text()
-    (tmp_path / "topology.inc").write_text(hip[:hip.index("\nusing namespace recmv;") + 1])
-    subprocess.run([clang, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-ffp-contract=off", "-I.", "main.cpp", "-o", "check"], cwd=tmp_path, check=True)
-    r = subprocess.run([str(tmp_path / "check")], cwd=tmp_path, capture_output=True, text=True)
+    r = host_check.run("mesh_topology", tmp_path)
     print(r.stdout)
     assert r.returncode == 0 and "all ok" in r.stdout and "WRONG" not in r.stdout, r.stdout + r.stderr
     assert r.stdout.count(" 0 mismatches") == 33

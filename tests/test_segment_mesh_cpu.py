@@ -20,6 +20,7 @@ import torch
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
 sys.path[:0] = [str(HERE), str(REPO / "rec-mv_amd")]
+import host_check  # noqa: E402
 import segment_mesh_reference as SR  # noqa: E402
 
 EPS32 = SR.EPS32
@@ -264,21 +265,7 @@ def test_host_build_of_the_grid_kernel_equals_the_brute_loop(tmp_path):
     families of scenes the f32 determinants cannot decide: a face that holds the segment's line behind a clean hit (the first
     hit with the early stop must still be the brute loop's), and tiny segments in the plane of a huge face far away (the
     program fails unless the box gate alone refused pairs there that the bare predicate accepts)."""
-    import shutil
-    import subprocess
-    clang = "/opt/rocm/lib/llvm/bin/clang++"
-    if not Path(clang).exists():
-        pytest.skip("ROCm's clang++ not present")
-    csrc = REPO / "rec-mv_amd" / "csrc"
-    for f in (REPO / "tools" / "mesh_grid_host_check" / "common.h", REPO / "tools" / "segment_mesh_host_check" / "main.cpp",
-              csrc / "closest_tri.h", csrc / "grid_query.h", csrc / "tri_tri.h", csrc / "seg_tri.h", csrc / "mesh_device.h"):
-        shutil.copy(f, tmp_path)
-    for src, dst in (("mesh_grid.hip", "grid.inc"), ("segment_mesh.hip", "segment.inc")):
-        hip = (csrc / src).read_text()
-        (tmp_path / dst).write_text(hip[:hip.index("\nusing namespace recmv;") + 1])
-    subprocess.run([clang, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-ffp-contract=off", "-I.", "main.cpp", "-o", "check"], cwd=tmp_path, check=True)
-    r = subprocess.run([str(tmp_path / "check")], cwd=tmp_path, capture_output=True, text=True)
+    r = host_check.run("segment_mesh", tmp_path)
     print(r.stdout)
     assert r.returncode == 0 and "all ok" in r.stdout and r.stdout.count(" 0 mismatches") == 11, r.stdout + r.stderr
     for name in ("single cell", "column 1x1x17", "two faces 40^3", "grid does not cover", "planar", "a face in every cell",

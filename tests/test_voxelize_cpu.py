@@ -17,6 +17,7 @@ import torch
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
 sys.path[:0] = [str(HERE), str(REPO / "rec-mv_amd")]
+import host_check  # noqa: E402
 import mesh_topology_cases as TC  # noqa: E402
 import voxelize_reference as VR  # noqa: E402
 
@@ -303,20 +304,7 @@ def test_host_build_of_the_kernels_equals_the_brute_loop(tmp_path):
     """tools/voxelize_host_check: csrc/mesh_voxelize.hip's kernels compiled for the CPU under the address and undefined-behaviour
     sanitizers; the scatter over the faces' dilated boxes gives the keys of a loop over every (node, face) pair on nine lattices
     and meshes (clipping, single-node axes, faces larger than the lattice, broken faces), and the column walk its restatement."""
-    import shutil
-    import subprocess
-    clang = "/opt/rocm/lib/llvm/bin/clang++"
-    if not Path(clang).exists():
-        pytest.skip("ROCm's clang++ not present")
-    csrc = REPO / "rec-mv_amd" / "csrc"
-    for src in (REPO / "tools" / "mesh_grid_host_check" / "common.h", REPO / "tools" / "voxelize_host_check" / "main.cpp",
-                csrc / "closest_tri.h", csrc / "mesh_device.h", REPO / "include" / "recmv_hip.h"):
-        shutil.copy(src, tmp_path)
-    hip = (csrc / "mesh_voxelize.hip").read_text()
-    (tmp_path / "voxelize.inc").write_text(hip[:hip.index("\nusing namespace recmv;") + 1])
-    subprocess.run([clang, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-ffp-contract=off", "-I.", "main.cpp", "-o", "check"], cwd=tmp_path, check=True)
-    r = subprocess.run([str(tmp_path / "check")], cwd=tmp_path, capture_output=True, text=True)
+    r = host_check.run("voxelize", tmp_path)
     print(r.stdout)
     assert r.returncode == 0 and "all ok" in r.stdout and r.stdout.count(" 0 mismatches") == 9, r.stdout + r.stderr
     for name in ("covers half of it", "faces larger than the lattice", "single-node axes 1x9x70", "broken faces"):

@@ -16,6 +16,7 @@ import torch
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
 sys.path[:0] = [str(HERE), str(REPO / "rec-mv_amd")]
+import host_check  # noqa: E402
 import winding_reference as WR  # noqa: E402
 
 TET_V = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], np.float32)
@@ -275,20 +276,7 @@ def test_host_build_of_the_kernels_equals_the_brute_loops(tmp_path):
     """tools/winding_host_check: csrc/winding.hip's kernels and csrc/solid_angle.h compiled for the CPU under the address and
     undefined-behaviour sanitizers: the binning, the pyramid's sums, the stack-free traversal (against a recursive walk, bit for
     bit, and against the brute sum) and the chunked exact sum, on seven inputs."""
-    import shutil
-    import subprocess
-    clang = "/opt/rocm/lib/llvm/bin/clang++"
-    if not Path(clang).exists():
-        pytest.skip("ROCm's clang++ not present")
-    csrc = REPO / "rec-mv_amd" / "csrc"
-    for src in (REPO / "tools" / "mesh_grid_host_check" / "common.h", REPO / "tools" / "winding_host_check" / "main.cpp",
-                csrc / "solid_angle.h", csrc / "mesh_device.h", REPO / "include" / "recmv_hip.h"):
-        shutil.copy(src, tmp_path)
-    hip = (csrc / "winding.hip").read_text()
-    (tmp_path / "winding.inc").write_text(hip[:hip.index("\nusing namespace recmv;") + 1])
-    subprocess.run([clang, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-ffp-contract=off", "-I.", "main.cpp", "-o", "check"], cwd=tmp_path, check=True)
-    r = subprocess.run([str(tmp_path / "check")], cwd=tmp_path, capture_output=True, text=True)
+    r = host_check.run("winding", tmp_path)
     print(r.stdout)
     assert r.returncode == 0 and "all ok" in r.stdout and r.stdout.count("-> 0 mismatches") == 7, r.stdout + r.stderr
     for name in ("levels 1", "inside one finest cell", "invalid indices and faces without area", "a cube smaller than the mesh",

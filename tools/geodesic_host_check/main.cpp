@@ -9,9 +9,6 @@
 #include <stdlib.h>
 #include <vector>
 
-namespace recmv {
-static void set_error(const char*, ...) {}
-}  // namespace recmv
 #include "geodesic.inc"                                    // csrc/geodesic.hip up to its entry points
 using namespace recmv;
 

@@ -1,7 +1,7 @@
-// Host check of csrc/mesh_grid.hip: the count, fill and one-lane query kernels compiled for the CPU (common.h here stands in for
+// Host check of csrc/mesh_grid.hip: the count, fill and one-lane query kernels compiled for the CPU (tools/host_check/common.h stands in for
 // csrc/common.h: one lane per wave, kernels called as functions) and compared bit for bit with a brute force over the faces,
 // on meshes and grids chosen to reach every branch.  kernels.inc is csrc/mesh_grid.hip up to its `using namespace recmv;` line
-// (README.md has the commands; tests/test_mesh_metrics_cpu.py runs them).
+// (tests/host_check.py builds it; tests/test_mesh_metrics_cpu.py runs it).
 #include "kernels.inc"
 #include <vector>
 #include <random>

@@ -1,7 +1,7 @@
 // Host check of csrc/mesh_intersect.hip: the one-lane grid kernel compiled for the CPU (the stand-in
-// common.h of tools/mesh_grid_host_check: one lane per wave, kernels called as functions), count and fill pass, compared as
+// common.h of tools/host_check: one lane per wave, kernels called as functions), count and fill pass, compared as
 // integers with a double loop over the brute-force kernel's pair test on random triangle soups and grids, under the host's sanitizers.  grid.inc / intersect.inc are csrc/mesh_grid.hip
-// and csrc/mesh_intersect.hip up to their `using namespace recmv;` line (README.md has the commands).
+// and csrc/mesh_intersect.hip up to their `using namespace recmv;` line (tests/host_check.py builds it).
 #define __fmul_rn(a, b) ((float)(a) * (float)(b))
 #define __fsub_rn(a, b) ((float)(a) - (float)(b))
 #include "grid.inc"

@@ -1,7 +1,7 @@
-// Host check of csrc/point_grid.hip: its kernels compiled for the CPU (the stand-in common.h of tools/mesh_grid_host_check:
+// Host check of csrc/point_grid.hip: its kernels compiled for the CPU (the stand-in common.h of tools/host_check:
 // kernels called as functions, one thread after the other) under the host's sanitizers.  point_grid.inc is
-// csrc/point_grid.hip up to its `using namespace recmv;` line (README.md has the commands; tests/test_mesh_repair_cpu.py runs
-// them).
+// csrc/point_grid.hip up to its `using namespace recmv;` line (tests/host_check.py builds it; tests/test_mesh_repair_cpu.py runs
+// it).
 //   * the pair set against the plain O(V^2) loop with the same float64 expression, and the same array from a second run, on
 //     the shapes of tests/test_gpu_mesh_repair.py: V = 0, 1, 2; 255, 256, 257 random points; 300 coincident points; a 6 x 6 x 6
 //     integer lattice with eps = 1, shifted to negative coordinates and to straddle 0; eps = 0 with signed zeros; NaN and inf;

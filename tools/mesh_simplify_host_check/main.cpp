@@ -1,7 +1,7 @@
 // Host check of csrc/mesh_simplify.hip: its three kernels compiled for the CPU (the stand-in common.h of
-// tools/mesh_grid_host_check: kernels called as functions, one thread after the other) under the host's sanitizers.
-// simplify.inc is csrc/mesh_simplify.hip up to its `using namespace recmv;` line (README.md has the commands;
-// tests/test_mesh_simplify_cpu.py runs them).
+// tools/host_check: kernels called as functions, one thread after the other) under the host's sanitizers.
+// simplify.inc is csrc/mesh_simplify.hip up to its `using namespace recmv;` line (tests/host_check.py builds it;
+// tests/test_mesh_simplify_cpu.py runs it).
 //   * quadrics against a plain long-double loop: fans of 0, 1, 63, 64, 65 and 257 faces at one vertex, a bumpy grid with its
 //     border, invalid faces and a NaN corner.
 //   * placement and cost on quadrics of rank 0, 1 (a flat patch), 2 (a straight crease) and 3 built by hand, on E = 0, 1, 255,

@@ -1,12 +1,11 @@
-// Host check of csrc/mesh_topology.hip: its kernels compiled for the CPU (topology_shims.h on top of the stand-in common.h of
-// tools/mesh_grid_host_check: one lane per wave, kernels called as functions, one thread after the other) under the host's
-// sanitizers.  topology.inc is csrc/mesh_topology.hip up to its `using namespace recmv;` line (README.md has the commands;
-// tests/test_mesh_topology_cpu.py runs them).
+// Host check of csrc/mesh_topology.hip: its kernels compiled for the CPU (the stand-in common.h of tools/host_check: one lane
+// per wave, kernels called as functions, one thread after the other; the integer minimum and the relaxed loads and stores of
+// the compression are plain ones there) under the host's sanitizers.  topology.inc is csrc/mesh_topology.hip up to its
+// `using namespace recmv;` line (tests/host_check.py builds it; tests/test_mesh_topology_cpu.py runs it).
 //   * components: the rounds run serially until a round hooks nothing; the labels against a plain union-find (smallest member),
 //     the number of rounds against a plain restatement of the synchronous algorithm (every root takes the smallest root among
 //     its neighbour trees, then every node its tree's root) and against the cap 2 ceil(log2 n) + 2.
 //   * face figures against plain loops; segment sums against plain loops.
-#include "topology_shims.h"
 #include "topology.inc"
 #include <numeric>
 #include <random>

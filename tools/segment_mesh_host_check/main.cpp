@@ -1,9 +1,9 @@
 // Host check of csrc/segment_mesh.hip: the one-lane grid kernel compiled for the CPU (the stand-in common.h of
-// tools/mesh_grid_host_check: one lane per wave, kernels called as functions), in both modes, compared bit for bit (face, the
+// tools/host_check: one lane per wave, kernels called as functions), in both modes, compared bit for bit (face, the
 // bits of t, count) with a loop over seg_face_hit — what the brute-force kernel runs for every face — on nine meshes and
 // grids, with segments chosen to reach every branch of the walk, and on two families of small scenes under random rigid
 // motions that the f32 determinants cannot decide, under the host's sanitizers.  grid.inc / segment.inc are
-// csrc/mesh_grid.hip and csrc/segment_mesh.hip up to their `using namespace recmv;` line (README.md has the commands).
+// csrc/mesh_grid.hip and csrc/segment_mesh.hip up to their `using namespace recmv;` line (tests/host_check.py builds it).
 #define __fmul_rn(a, b) ((float)(a) * (float)(b))
 #define __fsub_rn(a, b) ((float)(a) - (float)(b))
 #define __fadd_rn(a, b) ((float)(a) + (float)(b))

@@ -15,9 +15,6 @@ static inline unsigned long long atomicMin(unsigned long long* p, unsigned long 
   if (v < o) *p = v;
   return o;
 }
-namespace recmv {
-static void set_error(const char*, ...) {}
-}  // namespace recmv
 #include "voxelize.inc"                                    // csrc/mesh_voxelize.hip up to its entry points
 using namespace recmv;
 

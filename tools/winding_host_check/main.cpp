@@ -10,9 +10,6 @@
 #include <stdlib.h>
 #include <vector>
 
-namespace recmv {
-static void set_error(const char*, ...) {}
-}  // namespace recmv
 #include "winding.inc"                                     // csrc/winding.hip up to its entry points
 using namespace recmv;
 
