@@ -47,7 +47,9 @@ extern "C" {
  *        recmv_winding_tree_cells, recmv_winding_tree_build, recmv_winding_tree_query with the recmv_winding_tree descriptor
  *        (generalized winding numbers: pure additions, still v11); recmv_geodesic_lds_max_vertices,
  *        recmv_geodesic_auto_max_vertices, recmv_geodesic_workspace_bytes, recmv_geodesic_check_sources, recmv_geodesic_sweeps,
- *        recmv_geodesic_lds (geodesic distance fields: pure additions, still v11).
+ *        recmv_geodesic_lds (geodesic distance fields: pure additions, still v11); recmv_param_lds_max_vertices,
+ *        recmv_param_auto_max_vertices, recmv_param_solve_workspace_bytes, recmv_param_solve, recmv_param_solve_lds,
+ *        recmv_param_face_frames, recmv_param_arap_rhs, recmv_param_distortion (mesh parameterisation: pure additions, still v11).
  *   v10: recmv_verts_normals, recmv_hard_phong_shade, recmv_hard_phong_params_floats added.  Added since without a bump (no
  *        existing signature changed, and _lib.py rejects a library that lacks them): recmv_knn1, recmv_nricp_energy,
  *        recmv_lap_align_solve, recmv_lap_smooth, recmv_closest_point, recmv_iso_relax, recmv_loop_subdivide,
@@ -1226,6 +1228,68 @@ int recmv_geodesic_sweeps(const float* verts, int64_t V, const int64_t* faces, i
 int recmv_geodesic_lds(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* slot_offsets,
                        const int64_t* slots, int64_t B, const double* D0, double* D, int32_t* sweeps, int64_t max_sweeps,
                        void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Mesh parameterisation (csrc/mesh_param.hip; added to ABI v11, no existing signature changed).  Not in the reference.  The
+ * kernels of recmv/param.py: all arithmetic float64, un-contracted, + - * / sqrt only, gathers over CSR tables, no float atomics.
+ * The system.  Over the neighbour CSR of recmv.connectivity.neighbours_csr (nbr_offsets [V + 1], nbr_idx [nnz] int32) with one
+ *   weight per entry (the layout recmv_cotan_weights writes), an entry k of row i counts when its j = nbr_idx[k] lies in
+ *   [0, V), j != i and weights[k] is finite and > 0.  d_i = the sum of the counted weights in row order.  Vertex i is active
+ *   when fixed[i] == 0 and d_i > 0; a free vertex with d_i = 0 (a zero row) keeps its value and is counted in zero_rows.  For
+ *   the active vertices, two columns at once (u, rhs [V,2]):
+ *       (A x)_i = sum over the counted entries, in row order, of w_k (x_i - x_j)          (x_j = 0 for a j that is not active)
+ *       r_i = rhs_i - sum_k w_k (u_i - u_j),   b_i = rhs_i + sum over the counted entries with fixed[j] of w_k u_j
+ *   and Jacobi-preconditioned conjugate gradients from the u passed in: z = r (1 / d), p = z + beta p (beta = 0 first),
+ *   q = A p, alpha = (r.z) / (p.q), u += alpha p, r -= alpha q, beta = (r.z)' / (r.z), per column; a column is active while
+ *   r.r > tol^2 b.b and freezes (alpha = beta = 0) when it converges or when p.q is not > 0 or alpha / beta is not finite.  The
+ *   solve ends when no column is active or after max_iter iterations.  residuals[c] = sqrt(r.r / b.b) (sqrt(r.r) when b = 0).
+ * The summation order of every dot product (b.b, r.z, r.r, p.q, the zero-row count, the ARAP energy), written once: term i
+ *   belongs to slot i / 256, wave (i % 256) / 64, lane i % 64; terms beyond the end and of vertices that are not active are +0.
+ *   (1) a wave's 64 lanes are summed by the xor butterfly v += v[lane ^ off] for off = 32, 16, 8, 4, 2, 1; (2) a slot is
+ *   ((((0 + wave 0) + wave 1) + wave 2) + wave 3); (3) with T = 256 accumulators, accumulator t adds the slots t, t + 256, ...
+ *   in that order from 0; (4) the 256 accumulators are summed like one slot: butterflies over 64, then the four from 0.
+ *   (mesh_device.h's block_partials and reduce_slots.)  Both routes follow it, so they give the same bits and iteration count.
+ * recmv_param_solve (any V): workspace of recmv_param_solve_workspace_bytes(V) bytes, 256-byte aligned.  Two launches per
+ *   iteration, queued `batch` (<= 0: 32) iterations at a time with one small launch and one read-back of the state per batch;
+ *   the batch size changes no bit.  iterations, residuals [2] and zero_rows are HOST pointers.  The call synchronises.
+ * recmv_param_solve_lds (V <= recmv_param_lds_max_vertices() = (163840 - 4096) / 72 = 2218): the whole solve in one launch by
+ *   one workgroup, u, r, p, q and 1 / d in LDS.  `report`: at least 128 bytes of DEVICE memory, 8-byte aligned.
+ *   recmv_param_auto_max_vertices(): up to this V recmv.param's route 'auto' takes this route.
+ * recmv_param_face_frames: per face the isometric flattening, frames [F,4] = (x1, x2, y2, area): corner 0 at (0, 0), corner 1
+ *   at (x1, 0) with x1 = |e1|, corner 2 at (x2, y2) = (e1.e2 / x1, |e1 x e2| / x1), area = |e1 x e2| / 2 (e1 = p1 - p0,
+ *   e2 = p2 - p0); and cots [F,3]: 1/2 max(0, cot) at each corner, recmv_cotan_weights' expression.  A face is usable when its
+ *   indices are distinct and in [0, V), its corners finite and |e1 x e2| finite and > 0; an unusable face gets zeros.
+ * recmv_param_arap_rhs: with X the flat corners, half-edge k of a face runs from corner a = k + 1 to b = k + 2 (mod 3) with the
+ *   weight c_k = cots[k].  S = sum_k c_k (u_a - u_b)(X_a - X_b)^T, (a, b) = (S00 + S11, S10 - S01) / its length ((1, 0) when the
+ *   length is 0 or not finite) -> rot [F,2], the rotation R = [[a, -b], [b, a]]; the face's energy sum_k c_k |(u_a - u_b) -
+ *   R (X_a - X_b)|^2 -> partials [(F + 255) / 256] in the order above and their sum -> energy [1].  Then per vertex over the
+ *   slot table (slot_offsets [V + 1], slots: recmv.connectivity.vertex_slots_csr, every entry checked against the faces), for
+ *   corner k of a usable face: rhs_i += c_{k+2} R (X_k - X_{k+1}), then rhs_i += c_{k+1} R (X_k - X_{k+2}).  Unusable faces
+ *   (area 0 in frames, or indices that are not valid) add nothing.
+ * recmv_param_distortion: out [F,3] = (s1, s2, det) of the Jacobian J of the map flat triangle -> uv:
+ *   J00 = a0 / x1, J10 = a1 / x1, J01 = (b0 - J00 x2) / y2, J11 = (b1 - J10 x2) / y2 with a = uv1 - uv0, b = uv2 - uv0;
+ *   E = (J00 + J11) / 2, F = (J00 - J11) / 2, G = (J10 + J01) / 2, H = (J10 - J01) / 2, Q = sqrt(E E + H H), R = sqrt(F F + G G),
+ *   s1 = Q + R, s2 = |Q - R|, det = J00 J11 - J01 J10.  An unusable face gives NaN, NaN, 0.
+ * Argument errors (negative sizes, sizes of 2^31 or more, NULL pointers with non-zero sizes, a short or misaligned workspace, V
+ * above the lds capacity, tol < 0 or NaN, max_iter < 0) return RECMV_ERR_ARG before any HIP call; empty inputs are no-ops.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t recmv_param_lds_max_vertices(void);
+int64_t recmv_param_auto_max_vertices(void);
+int64_t recmv_param_solve_workspace_bytes(int64_t V);
+int recmv_param_solve(const int32_t* nbr_offsets, const int32_t* nbr_idx, const double* weights, int64_t V, int64_t nnz,
+                      const uint8_t* fixed, const double* rhs, double* u, double tol, int32_t max_iter, int32_t batch,
+                      int32_t* iterations, double* residuals, int32_t* zero_rows, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+int recmv_param_solve_lds(const int32_t* nbr_offsets, const int32_t* nbr_idx, const double* weights, int64_t V, int64_t nnz,
+                          const uint8_t* fixed, const double* rhs, double* u, double tol, int32_t max_iter,
+                          int32_t* iterations, double* residuals, int32_t* zero_rows, void* report, void* stream);
+int recmv_param_face_frames(const float* verts, int64_t V, const int64_t* faces, int64_t F, double* frames, double* cots,
+                            void* stream);
+int recmv_param_arap_rhs(const int64_t* faces, int64_t F, const double* frames, const double* cots, const double* uv, int64_t V,
+                         const int64_t* slot_offsets, const int64_t* slots, double* rot, double* rhs, double* partials,
+                         double* energy, void* stream);
+int recmv_param_distortion(const int64_t* faces, int64_t F, const double* frames, const double* uv, int64_t V, double* out,
+                           void* stream);
 
 #ifdef __cplusplus
 }

@@ -254,6 +254,14 @@ def _declare(lib):
         "recmv_geodesic_check_sources": (C.c_int, [vp, vp, i64, i64]),
         "recmv_geodesic_sweeps": (C.c_int, [vp, i64, vp, i64, vp, vp, i64, vp, i64, i64, i64, vp]),
         "recmv_geodesic_lds": (C.c_int, [vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp]),
+        "recmv_param_lds_max_vertices": (i64, []),
+        "recmv_param_auto_max_vertices": (i64, []),
+        "recmv_param_solve_workspace_bytes": (i64, [i64]),
+        "recmv_param_solve": (C.c_int, [vp, vp, vp, i64, i64, vp, vp, vp, f64, i32, i32, vp, vp, vp, vp, i64, vp]),
+        "recmv_param_solve_lds": (C.c_int, [vp, vp, vp, i64, i64, vp, vp, vp, f64, i32, vp, vp, vp, vp, vp]),
+        "recmv_param_face_frames": (C.c_int, [vp, i64, vp, i64, vp, vp, vp]),
+        "recmv_param_arap_rhs": (C.c_int, [vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "recmv_param_distortion": (C.c_int, [vp, i64, vp, vp, i64, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)       # AttributeError if the symbol is missing: fail loudly
