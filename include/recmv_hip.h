@@ -681,7 +681,8 @@ int recmv_nricp_energy(const float* A, const float* b, const float* x, const flo
  * recmv_lap_align_solve: u [V,3] f32 = the solution of (L^T L + diag(cw)) u = L^T (L v) + cwt for the three columns, L the
  *   uniform Laplacian of pytorch3d's laplacian_packed, v [V,3] f32, cw [V] f64 (weight x constraints on the vertex), cwt
  *   [V,3] f64 (weight x sum of their targets).  Jacobi-preconditioned CG in f64 from u = v until |r| <= tol |rhs| in every
- *   column or max_iter iterations; the call synchronises `stream` once every 32 iterations and at the end.
+ *   column or max_iter iterations; a column freezes (alpha = beta = 0) when it converges or when p.q is not > 0 or
+ *   alpha / beta is not finite.  The call synchronises `stream` once every 32 iterations and at the end.
  *   iterations (host, 1 int32) and residuals (host, 3 doubles: each column's final relative residual) are written on
  *   return.  V = 0 is a no-op.  Workspace: recmv_lap_align_workspace_bytes(V), 256-byte aligned.
  * recmv_lap_smooth: out [V,3] f32 = (1/deg_i) sum_{j in N(i)} u_j, accumulated in f64 in CSR order and rounded once; an

@@ -19,11 +19,12 @@
 //   (1) p <- z + beta p (into the other p buffer) and t = L p      one thread per vertex; every thread recomputes its
 //                                                                  neighbours' new p from z and the old p, the same f64 ops
 //   (2) q = L^T t + cw p, per-workgroup partials of p.q            fixed slot per workgroup (the grid depends on V only)
-//   (3) one workgroup: alpha = (r.z) / (p.q)
+//   (3) one workgroup: alpha = (r.z) / (p.q), the iteration count
 //   (4) u += alpha p, r -= alpha q, z = r / diag, partials of r.z and r.r
-//   (5) one workgroup: beta, convergence (|r| <= tol |rhs| per column), the iteration count and the "done" flag.
+//   (5) one workgroup: beta, convergence (|r| <= tol |rhs| per column) and the "done" flag.
 // Every launch returns at once when "done" is set, so the host queues iterations in batches and reads the flag once a batch.
-// The reductions add fixed slots in a fixed order: results are bitwise reproducible.
+// The reductions add fixed slots in a fixed order: results are bitwise reproducible.  The CG state, its three steps (begin,
+// alpha, beta with convergence), the residuals and the workspace carve are csrc/mesh_cg.h's, shared with mesh_param.hip.
 #include "common.h"
 
 namespace recmv {
@@ -32,27 +33,16 @@ namespace {
 #pragma clang fp contract(off)
 
 #include "mesh_device.h"                                   // csr_range, index_in, block_partials, reduce_slots
+#include "mesh_cg.h"                                       // CgState, cg_begin, cg_alpha, cg_head, cg_residuals, Carver
 
 constexpr int kLapBlock = 256;
-constexpr int kLapBatch = 32;                // iterations queued between two reads of the "done" flag
-
-struct CgState {
-  double rz[3];                              // r.z of the current residual
-  double bb[3];                              // |rhs|^2
-  double rr[3];                              // |r|^2
-  double alpha[3];
-  double beta[3];
-  int32_t active[3];                         // 1 while the column iterates
-  int32_t done;                              // all columns converged, or max_iter reached
-  int32_t iters;                             // iterations run
-  int32_t max_iter;
-};
+using LapCg = CgState<3>;
 
 struct LapArgs {
   const int32_t *off, *nbr;
   int64_t V, nnz;
   const double* invdeg;
-  CgState* st;
+  LapCg* st;
 };
 
 // ---------------------------------------------------------------------------------------------- set-up
@@ -125,26 +115,10 @@ lap_init_residual_kernel(LapArgs a, const float* __restrict__ v, const double* _
 }
 
 __global__ void __launch_bounds__(kLapBlock)
-lap_init_reduce_kernel(const double* __restrict__ partials, int nslots, double tol, int max_iter, CgState* st) {
+lap_init_reduce_kernel(const double* __restrict__ partials, int nslots, double tol, int max_iter, LapCg* st) {
   double s[9];
   reduce_slots<9, kLapBlock>(partials, nslots, s);
-  if (threadIdx.x == 0) {
-    int any = 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      st->bb[c] = s[c];
-      st->rz[c] = s[3 + c];
-      st->rr[c] = s[6 + c];
-      st->alpha[c] = 0.;
-      st->beta[c] = 0.;                      // the first p = z + 0 * p = z
-      const int act = s[6 + c] > tol * tol * s[c] ? 1 : 0;
-      st->active[c] = act;
-      any |= act;
-    }
-    st->iters = 0;
-    st->max_iter = max_iter;
-    st->done = (any == 0 || max_iter <= 0) ? 1 : 0;
-  }
+  if (threadIdx.x == 0) cg_begin(*st, s, s + 3, s + 6, tol, max_iter);
 }
 
 // ---------------------------------------------------------------------------------------------- one iteration
@@ -205,21 +179,13 @@ lap_cg_apply_kernel(LapArgs a, const double* __restrict__ cw, const double* __re
   block_partials<3, kLapBlock>(acc, partials);
 }
 
-// (3) alpha = (r.z) / (p.q) per active column; a column whose p.q is not positive and finite freezes
+// (3) alpha = (r.z) / (p.q) per active column, the iteration count
 __global__ void __launch_bounds__(kLapBlock)
-lap_cg_alpha_kernel(const double* __restrict__ partials, int nslots, CgState* st) {
+lap_cg_alpha_kernel(const double* __restrict__ partials, int nslots, LapCg* st) {
   if (st->done) return;
   double pq[3];
   reduce_slots<3, kLapBlock>(partials, nslots, pq);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double al = st->rz[c] / pq[c];
-      const bool ok = st->active[c] && pq[c] > 0. && al == al && al < __builtin_inf() && al > -__builtin_inf();
-      st->alpha[c] = ok ? al : 0.;
-      if (!ok) st->active[c] = 0;
-    }
-  }
+  if (threadIdx.x == 0) cg_alpha(*st, pq);
 }
 
 // (4) u += alpha p, r -= alpha q, z = r / diag; partials of r.z and r.r
@@ -247,30 +213,13 @@ lap_cg_update_kernel(LapArgs a, const double* __restrict__ dinv, const double* _
   block_partials<6, kLapBlock>(acc, partials);
 }
 
-// (5) beta, convergence per column, iteration count, "done"
+// (5) beta, convergence per column, "done"
 __global__ void __launch_bounds__(kLapBlock)
-lap_cg_beta_kernel(const double* __restrict__ partials, int nslots, double tol, CgState* st) {
+lap_cg_beta_kernel(const double* __restrict__ partials, int nslots, double tol, LapCg* st) {
   if (st->done) return;
   double s[6];
   reduce_slots<6, kLapBlock>(partials, nslots, s);
-  if (threadIdx.x == 0) {
-    int any = 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      if (st->active[c]) {
-        const double rz = s[c];
-        st->beta[c] = st->rz[c] != 0. ? rz / st->rz[c] : 0.;
-        st->rz[c] = rz;
-        st->rr[c] = s[3 + c];
-        if (!(s[3 + c] > tol * tol * st->bb[c])) st->active[c] = 0;
-      }
-      if (!st->active[c]) st->beta[c] = 0.;
-      any |= st->active[c];
-    }
-    const int it = st->iters + 1;
-    st->iters = it;
-    st->done = (any == 0 || it >= st->max_iter) ? 1 : 0;
-  }
+  if (threadIdx.x == 0) cg_head(*st, s, s + 3, tol);
 }
 
 __global__ void __launch_bounds__(kLapBlock)
@@ -300,37 +249,30 @@ lap_smooth_kernel(const int32_t* __restrict__ off, const int32_t* __restrict__ n
   }
 }
 
-inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 inline int64_t lap_slots(int64_t V) { return stream_grid(V, kLapBlock); }
 
-// Workspace: CgState | partials [slots, 9] | invdeg, dinv [V] | u, r, z, p0, p1, t, q [V,3], all f64, 256-byte aligned pieces.
+// Workspace: LapCg | partials [slots, 9] | invdeg, dinv [V] | u, r, z, p0, p1, t, q [V,3], all f64, 256-byte aligned pieces.
 struct LapWorkspace {
-  CgState* st;
+  LapCg* st;
   double *partials, *invdeg, *dinv, *u, *r, *z, *p[2], *t, *q;
 };
 
 inline int64_t lap_layout(int64_t V, char* base, LapWorkspace* w) {
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) {
-    char* ptr = base ? base + o : nullptr;
-    o += align256(bytes);
-    return ptr;
-  };
-  const int64_t vec = V * 3 * (int64_t)sizeof(double);
+  Carver c{base};
   LapWorkspace x;
-  x.st = (CgState*)take(sizeof(CgState));
-  x.partials = (double*)take(lap_slots(V) * 9 * (int64_t)sizeof(double));
-  x.invdeg = (double*)take(V * (int64_t)sizeof(double));
-  x.dinv = (double*)take(V * (int64_t)sizeof(double));
-  x.u = (double*)take(vec);
-  x.r = (double*)take(vec);
-  x.z = (double*)take(vec);
-  x.p[0] = (double*)take(vec);
-  x.p[1] = (double*)take(vec);
-  x.t = (double*)take(vec);
-  x.q = (double*)take(vec);
+  x.st = c.take<LapCg>(1);
+  x.partials = c.take<double>(lap_slots(V) * 9);
+  x.invdeg = c.take<double>(V);
+  x.dinv = c.take<double>(V);
+  x.u = c.take<double>(3 * V);
+  x.r = c.take<double>(3 * V);
+  x.z = c.take<double>(3 * V);
+  x.p[0] = c.take<double>(3 * V);
+  x.p[1] = c.take<double>(3 * V);
+  x.t = c.take<double>(3 * V);
+  x.q = c.take<double>(3 * V);
   if (w) *w = x;
-  return o;
+  return c.offset;
 }
 
 }  // namespace
@@ -375,12 +317,12 @@ extern "C" int recmv_lap_align_solve(const int32_t* nbr_offsets, const int32_t* 
   lap_init_reduce_kernel<<<1, kLapBlock, 0, s>>>(w.partials, slots, tol, (int)max_iter, w.st);
   rc = check_launch("lap_init_reduce");
   if (rc != RECMV_OK) return rc;
-  CgState host;
-  RECMV_HIP_TRY(hipMemcpyAsync(&host, w.st, sizeof(CgState), hipMemcpyDeviceToHost, s));
+  LapCg host;
+  RECMV_HIP_TRY(hipMemcpyAsync(&host, w.st, sizeof(LapCg), hipMemcpyDeviceToHost, s));
   RECMV_HIP_TRY(hipStreamSynchronize(s));
   int queued = 0;
   while (!host.done && queued < max_iter) {
-    const int n = max_iter - queued < kLapBatch ? max_iter - queued : kLapBatch;
+    const int n = max_iter - queued < kCgBatch ? max_iter - queued : kCgBatch;
     for (int k = 0; k < n; ++k, ++queued) {
       double* pold = w.p[queued & 1];
       double* pnew = w.p[(queued + 1) & 1];
@@ -392,15 +334,14 @@ extern "C" int recmv_lap_align_solve(const int32_t* nbr_offsets, const int32_t* 
     }
     rc = check_launch("lap_cg_iteration");
     if (rc != RECMV_OK) return rc;
-    RECMV_HIP_TRY(hipMemcpyAsync(&host, w.st, sizeof(CgState), hipMemcpyDeviceToHost, s));
+    RECMV_HIP_TRY(hipMemcpyAsync(&host, w.st, sizeof(LapCg), hipMemcpyDeviceToHost, s));
     RECMV_HIP_TRY(hipStreamSynchronize(s));
   }
   lap_output_kernel<<<stream_grid(3 * V, kLapBlock), kLapBlock, 0, s>>>(w.u, 3 * V, u);
   rc = check_launch("lap_output");
   if (rc != RECMV_OK) return rc;
   *iterations = host.iters;
-  for (int c = 0; c < 3; ++c)
-    residuals[c] = host.bb[c] > 0. ? sqrt(host.rr[c] / host.bb[c]) : (host.rr[c] > 0. ? sqrt(host.rr[c]) : 0.);
+  cg_residuals(host, residuals);
   return RECMV_OK;
 }
 

@@ -1,6 +1,6 @@
 // The plumbing under the mesh kernels: lane-group sums, the (value, index) minimum, fixed-order block reductions, clamped
-// CSR rows, index tests and the f64 3-vector helpers, shared so that every mesh operation compiles the one body.  Include
-// it inside namespace recmv after `#pragma clang fp contract(off)`, like closest_tri.h: a helper defined before the pragma
+// CSR rows, index tests and the f64 3-vector helpers with half_cot, shared so that every mesh operation compiles the one
+// body.  Include it inside namespace recmv after `#pragma clang fp contract(off)`, like closest_tri.h: a helper defined before the pragma
 // would be compiled with contraction on, and its f64 products would fuse.  Device code only: no RECMV_REQUIRE and no HIP
 // calls, so that the host checks of tools/ compile it under tools/host_check/common.h (kWave = 1, __shfl_xor the identity);
 // tests/host_check.py refuses an includer that breaks the pragma rule.
@@ -134,4 +134,18 @@ __device__ __forceinline__ bool finite3(float a, float b, float c) {
 __device__ __forceinline__ bool finite3(double x, double y, double z) {   // of three f32 widened to f64
   const double sum = x + y + z;                            // (a finite sum cannot hide an inf or a NaN; three f32 never overflow)
   return sum - sum == 0.;
+}
+
+// 1/2 max(0, cot) of the angle at corner c (0..2) of the face with corners p, in the face's cyclic order; 0 when the cross
+// product at that corner has no finite positive length
+__device__ __forceinline__ double half_cot(const double p[3][3], int c) {
+  const int a = (c + 1) % 3, b = (c + 2) % 3;
+  const double e1[3] = {p[a][0] - p[c][0], p[a][1] - p[c][1], p[a][2] - p[c][2]};
+  const double e2[3] = {p[b][0] - p[c][0], p[b][1] - p[c][1], p[b][2] - p[c][2]};
+  double n[3];
+  cross3(e1, e2, n);
+  const double len = sqrt(dot3(n, n));
+  if (!finite_positive(len)) return 0.;
+  const double cot = dot3(e1, e2) / len;
+  return cot > 0. ? 0.5 * cot : 0.;
 }

@@ -11,6 +11,8 @@
 // reduce_slots<K, 256> adds the slots: accumulator t takes slots t, t + 256, ... from 0, then the 256 accumulators like one
 // slot.  The launch route runs exactly these two (one thread per vertex, a grid of ceil(V / 256) workgroups, so a workgroup
 // IS a slot); the lds route's param_lds_waves / param_lds_total walk the same tree from its own workgroup size.
+// The CG state, its three steps (begin, alpha, head), the residuals and the workspace carve are csrc/mesh_cg.h's, shared with
+// lap_align.hip; both routes call the same steps.
 //
 // How:
 //   * Work: a vertex has about 6 neighbours; an iteration gathers 2 doubles per neighbour and does a dozen flops per
@@ -38,9 +40,9 @@ namespace {
 
 #pragma clang fp contract(off)
 #include "mesh_device.h"
+#include "mesh_cg.h"
 
 constexpr int kParamBlock = 256;
-constexpr int kParamBatch = 32;              // iterations queued between two reads of the state
 // The lds route's capacity: a single workgroup may have all of a CU's 160 KiB of LDS (163 840 bytes), and there is only one.
 // A vertex costs 4 x 16 bytes (u, r, p, q: two f64 columns) + 8 bytes (1 / d) = 72; 4096 bytes stay for the wave sums of the
 // reductions (8 sums x 35 chunks of 64 vertices x 8 bytes = 2240).  (163840 - 4096) / 72 = 2218.
@@ -67,18 +69,7 @@ static_assert(kWave != 64 || kParamLdsTail <= kParamLdsReserve, "the reductions'
 // the launch route's; at 2209 the two are level.  'lds' can be forced up to kParamLdsMaxV.
 constexpr int kParamAutoMaxV = 1600;
 
-struct ParamCg {
-  double rz[2];                              // r.z of the current residual
-  double bb[2];                              // |b|^2
-  double rr[2];                              // |r|^2
-  double alpha[2];
-  double beta[2];
-  int32_t active[2];                         // 1 while the column iterates
-  int32_t done;                              // no column active, or max_iter reached
-  int32_t iters;                             // updates applied
-  int32_t max_iter;
-  int32_t zero_rows;                         // free vertices whose weights sum to 0
-};
+struct ParamCg : CgState<2> {};              // (a name of its own keeps the kernels' symbols)
 
 struct ParamArgs {
   const int32_t *off, *nbr;
@@ -93,54 +84,10 @@ __device__ __forceinline__ bool param_counts(const ParamArgs& a, int64_t i, int6
   return index_in(j, a.V) && j != i && finite_positive(wk);
 }
 
-// ---- the CG state's three steps, the same code on both routes
-// s = (b.b, r.z, r.r) x 2 columns, the zero-row count, unused
+// the state from the set-up's sums s = (b.b, r.z, r.r) x 2 columns, the zero-row count, unused; the same code on both routes
 __device__ __forceinline__ void param_cg_begin(ParamCg& st, const double* s, double tol, int max_iter) {
-  int any = 0;
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    st.bb[c] = s[c];
-    st.rz[c] = s[2 + c];
-    st.rr[c] = s[4 + c];
-    st.alpha[c] = 0.;
-    st.beta[c] = 0.;                         // the first p = z + 0 * p = z
-    st.active[c] = s[4 + c] > tol * tol * s[c] ? 1 : 0;
-    any |= st.active[c];
-  }
+  cg_begin<2>(st, s, s + 2, s + 4, tol, max_iter);
   st.zero_rows = (int32_t)s[6];
-  st.iters = 0;
-  st.max_iter = max_iter;
-  st.done = (any == 0 || max_iter <= 0) ? 1 : 0;
-}
-
-// alpha = (r.z) / (p.q) per active column; a column whose p.q is not positive or whose alpha is not finite freezes
-__device__ __forceinline__ void param_cg_alpha(ParamCg& st, const double* pq) {
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const double al = st.rz[c] / pq[c];
-    const bool ok = st.active[c] && pq[c] > 0. && finite(al);
-    st.alpha[c] = ok ? al : 0.;
-    if (!ok) st.active[c] = 0;
-  }
-  st.iters += 1;
-}
-
-// s = (r.z) x 2, (r.r) x 2 of the updated residual: beta, convergence, "done"
-__device__ __forceinline__ void param_cg_head(ParamCg& st, const double* s, double tol) {
-  int any = 0;
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    if (st.active[c]) {
-      const double be = st.rz[c] != 0. ? s[c] / st.rz[c] : 0.;
-      st.beta[c] = be;
-      st.rz[c] = s[c];
-      st.rr[c] = s[2 + c];
-      if (!(s[2 + c] > tol * tol * st.bb[c]) || !finite(be)) st.active[c] = 0;
-    }
-    if (!st.active[c]) st.beta[c] = 0.;
-    any |= st.active[c];
-  }
-  st.done = (any == 0 || st.iters >= st.max_iter) ? 1 : 0;
 }
 
 // d_i, whether vertex i is active, and for an active vertex r = rhs - A u and b (both columns)
@@ -222,7 +169,7 @@ __device__ __forceinline__ ParamCg param_head_state(int first, const ParamCg* si
   if (!first) reduce_slots<4, kParamBlock>(prz, nslots, s);
   if (threadIdx.x == 0) {
     ParamCg x = *sin;
-    if (!first && !x.done) param_cg_head(x, s, tol);
+    if (!first && !x.done) cg_head<2>(x, s, s + 2, tol);
     sh_state = x;
     if (blockIdx.x == 0) *sout = x;
   }
@@ -278,7 +225,7 @@ param_cg_update_kernel(int64_t V, const ParamCg* sin, ParamCg* sout, const doubl
   if (threadIdx.x == 0) {
     ParamCg x = *sin;
     if (!x.done) {
-      param_cg_alpha(x, pq);
+      cg_alpha<2>(x, pq);
       if (blockIdx.x == 0) *sout = x;
     }
     sh_state = x;
@@ -444,7 +391,7 @@ param_solve_lds_kernel(ParamArgs a, const uint8_t* __restrict__ fixed, const dou
     {
       double pq[2];
       param_lds_total<2>(wsum_pq, nchunks, pq);
-      param_cg_alpha(st, pq);
+      cg_alpha<2>(st, pq);
     }
     // u += alpha p, r -= alpha q, r.z and r.r
     for (int base = 0; base < n; base += step) {
@@ -471,7 +418,7 @@ param_solve_lds_kernel(ParamArgs a, const uint8_t* __restrict__ fixed, const dou
     {
       double s[4];
       param_lds_total<4>(wsum_rz, nchunks, s);
-      param_cg_head(st, s, tol);
+      cg_head<2>(st, s, s + 2, tol);
     }
   }
   for (int i = tid; i < n; i += step) {
@@ -484,19 +431,6 @@ param_solve_lds_kernel(ParamArgs a, const uint8_t* __restrict__ fixed, const dou
 }
 
 // ================================================================================================ frames, ARAP, distortion
-// recmv_cotan_weights' corner expression (csrc/mesh_smooth.hip's sm_half_cot, restated: that file's kernels stay as they are)
-__device__ __forceinline__ double param_half_cot(const double p[3][3], int c) {
-  const int a = (c + 1) % 3, b = (c + 2) % 3;
-  const double e1[3] = {p[a][0] - p[c][0], p[a][1] - p[c][1], p[a][2] - p[c][2]};
-  const double e2[3] = {p[b][0] - p[c][0], p[b][1] - p[c][1], p[b][2] - p[c][2]};
-  double n[3];
-  cross3(e1, e2, n);
-  const double len = sqrt(dot3(n, n));
-  if (!finite_positive(len)) return 0.;
-  const double cot = dot3(e1, e2) / len;
-  return cot > 0. ? 0.5 * cot : 0.;
-}
-
 __global__ void __launch_bounds__(kParamBlock)
 param_face_frames_kernel(const float* __restrict__ v, int64_t V, const int64_t* __restrict__ f, int64_t F,
                          double* __restrict__ frames, double* __restrict__ cots) {
@@ -521,7 +455,7 @@ param_face_frames_kernel(const float* __restrict__ v, int64_t V, const int64_t* 
         fr[2] = len / x1;
         fr[3] = 0.5 * len;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) ct[c] = param_half_cot(p, c);
+        for (int c = 0; c < 3; ++c) ct[c] = half_cot(p, c);                 // recmv_cotan_weights' corner expression
       }
     }
   }
@@ -649,7 +583,6 @@ param_distortion_kernel(const int64_t* __restrict__ f, int64_t F, const double* 
   out[3 * t + 2] = det;
 }
 
-inline int64_t param_align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 inline int64_t param_slots(int64_t n) { return (n + kParamBlock - 1) / kParamBlock; }
 
 // Workspace: state [2], report | slots of the set-up [*, 8], of p.q [*, 2], of r.z and r.r [*, 4] | 1 / d [V] | r, z, q, p0, p1
@@ -660,28 +593,23 @@ struct ParamWorkspace {
 };
 
 inline int64_t param_layout(int64_t V, char* base, ParamWorkspace* w) {
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) {
-    char* ptr = base ? base + o : nullptr;
-    o += param_align256(bytes);
-    return ptr;
-  };
-  const int64_t vec = V * 2 * (int64_t)sizeof(double), slots = param_slots(V);
+  Carver c{base};
+  const int64_t slots = param_slots(V);
   ParamWorkspace x;
-  x.st[0] = (ParamCg*)take(sizeof(ParamCg));
-  x.st[1] = (ParamCg*)take(sizeof(ParamCg));
-  x.report = (ParamCg*)take(sizeof(ParamCg));
-  x.pinit = (double*)take(slots * 8 * (int64_t)sizeof(double));
-  x.ppq = (double*)take(slots * 2 * (int64_t)sizeof(double));
-  x.prz = (double*)take(slots * 4 * (int64_t)sizeof(double));
-  x.dinv = (double*)take(V * (int64_t)sizeof(double));
-  x.r = (double*)take(vec);
-  x.z = (double*)take(vec);
-  x.q = (double*)take(vec);
-  x.p[0] = (double*)take(vec);
-  x.p[1] = (double*)take(vec);
+  x.st[0] = c.take<ParamCg>(1);
+  x.st[1] = c.take<ParamCg>(1);
+  x.report = c.take<ParamCg>(1);
+  x.pinit = c.take<double>(slots * 8);
+  x.ppq = c.take<double>(slots * 2);
+  x.prz = c.take<double>(slots * 4);
+  x.dinv = c.take<double>(V);
+  x.r = c.take<double>(2 * V);
+  x.z = c.take<double>(2 * V);
+  x.q = c.take<double>(2 * V);
+  x.p[0] = c.take<double>(2 * V);
+  x.p[1] = c.take<double>(2 * V);
   if (w) *w = x;
-  return o;
+  return c.offset;
 }
 
 // the arguments both solve routes share; false with a message
@@ -718,8 +646,7 @@ bool param_solve_args(const char* who, const int32_t* off, const int32_t* nbr, c
 void param_results(const ParamCg& st, int32_t* iterations, double* residuals, int32_t* zero_rows) {
   *iterations = st.iters;
   *zero_rows = st.zero_rows;
-  for (int c = 0; c < 2; ++c)
-    residuals[c] = st.bb[c] > 0. ? sqrt(st.rr[c] / st.bb[c]) : (st.rr[c] > 0. ? sqrt(st.rr[c]) : 0.);
+  cg_residuals<2>(st, residuals);
 }
 
 }  // namespace
@@ -760,7 +687,7 @@ extern "C" int recmv_param_solve(const int32_t* nbr_offsets, const int32_t* nbr_
   param_layout(V, (char*)workspace, &w);
   const ParamArgs a{nbr_offsets, nbr_idx, weights, V, nnz};
   const int slots = (int)param_slots(V);
-  const int per_batch = batch > 0 ? batch : kParamBatch;
+  const int per_batch = batch > 0 ? batch : kCgBatch;
   param_init_kernel<<<slots, kParamBlock, 0, s>>>(a, fixed, rhs, u, w.dinv, w.r, w.z, w.p[0], w.p[1], w.pinit);
   int rc = check_launch("param_init");
   if (rc != RECMV_OK) return rc;

@@ -38,7 +38,7 @@ namespace {
 
 constexpr int kSmoothBlock = 256;
 
-#include "mesh_device.h"                                   // tri_valid, index_in, csr_range_ordered, load3, cross3, dot3, finite, finite_positive
+#include "mesh_device.h"                                   // tri_valid, index_in, csr_range_ordered, load3, cross3, dot3, finite, finite_positive, half_cot
 
 // The three corners of face `row` when it takes part: valid indices, finite corners and a cross product at the first corner
 // whose length is finite and > 0.
@@ -53,20 +53,6 @@ __device__ __forceinline__ bool sm_face_corners(const float* v, int64_t V, const
   double n[3];
   cross3(u, w, n);
   return finite_positive(sqrt(dot3(n, n)));
-}
-
-// 1/2 max(0, cot) of the angle at corner c (0..2) of the face with corners p, in the face's cyclic order; 0 when the cross
-// product at that corner has no finite positive length
-__device__ __forceinline__ double sm_half_cot(const double p[3][3], int c) {
-  const int a = (c + 1) % 3, b = (c + 2) % 3;
-  const double e1[3] = {p[a][0] - p[c][0], p[a][1] - p[c][1], p[a][2] - p[c][2]};
-  const double e2[3] = {p[b][0] - p[c][0], p[b][1] - p[c][1], p[b][2] - p[c][2]};
-  double n[3];
-  cross3(e1, e2, n);
-  const double len = sqrt(dot3(n, n));
-  if (!finite_positive(len)) return 0.;
-  const double cot = dot3(e1, e2) / len;
-  return cot > 0. ? 0.5 * cot : 0.;
 }
 
 // where j stands in the ascending row nbr[k0, k1), or -1
@@ -105,8 +91,8 @@ cotan_weights_kernel(const float* __restrict__ v, int64_t V, const int64_t* __re
       if (!sm_face_corners(v, V, row, p)) continue;
       const int cj = (c + 1) % 3, ck = (c + 2) % 3;
       const int64_t kj = sm_find(nbr, k0, k1, row[cj]), kk = sm_find(nbr, k0, k1, row[ck]);
-      if (kj >= 0) w[kj] += sm_half_cot(p, ck);            // the angle opposite the edge (i, j) is at k
-      if (kk >= 0) w[kk] += sm_half_cot(p, cj);
+      if (kj >= 0) w[kj] += half_cot(p, ck);            // the angle opposite the edge (i, j) is at k
+      if (kk >= 0) w[kk] += half_cot(p, cj);
     }
   }
 }

@@ -30,13 +30,14 @@ CHECKS = {
     "voxelize": ((("mesh_voxelize.hip", "voxelize.inc"),), ()),
     "winding": ((("winding.hip", "winding.inc"),), ()),
     "geodesic": ((("geodesic.hip", "geodesic.inc"),), ()),
+    "param": ((("mesh_param.hip", "param.inc"),), ()),
     "gemm_route": ((), ("-Wall", "-Werror")),
 }
 
 MARKER = re.compile(r"^using namespace recmv;", re.M)       # the kernels end here; the entry points with their HIP calls follow
 PRAGMA = re.compile(r"^#pragma clang fp contract\(off\)", re.M)
 # headers whose arithmetic must not contract: a helper defined in front of the pragma would fuse its products on the GPU
-UNCONTRACTED = re.compile(r'^#include "(?:mesh_device|closest_tri|grid_query|tri_tri|seg_tri|solid_angle)\.h"', re.M)
+UNCONTRACTED = re.compile(r'^#include "(?:mesh_device|mesh_cg|closest_tri|grid_query|tri_tri|seg_tri|solid_angle)\.h"', re.M)
 
 
 def cut(hip):

@@ -1,11 +1,10 @@
-"""A numpy float64 restatement of csrc/mesh_param.hip (include/recmv_hip.h has the definitions): the conjugate gradients with the
-canonical summation order (the xor butterfly as array operations, then the waves, then the slots), the flat frames and corner
-weights, the ARAP local step with the right-hand side and the energy, the distortion, the cotangent weights, and a dense solve
-of the same system as the independent answer.  numpy neither fuses nor reorders these operations, so the GPU's bits are
-expected."""
+"""A numpy float64 restatement of csrc/mesh_param.hip (include/recmv_hip.h has the definitions): the system that
+tests/cg_reference.py's conjugate gradients solve in the canonical summation order, the flat frames and corner weights, the ARAP
+local step with the right-hand side and the energy, the distortion, the cotangent weights, and a dense solve of the same system
+as the independent answer.  numpy neither fuses nor reorders these operations, so the GPU's bits are expected."""
 import numpy as np
 
-BLOCK, WAVE = 256, 64
+from cg_reference import canon_partials, canon_sum, cg, padded, rowsum
 
 
 # ---------------------------------------------------------------------------------------------------------- tables
@@ -28,15 +27,6 @@ def slots_csr(faces, V):
     off = np.zeros(V + 1, np.int64)
     off[1:] = np.cumsum(np.bincount(fv, minlength=V))
     return off, order.astype(np.int64)
-
-
-def _padded(off, n):
-    """A CSR's rows as a table: (position [R, D], valid [R, D])."""
-    off = np.asarray(off, np.int64)
-    cnt = off[1:] - off[:-1]
-    D = int(cnt.max()) if cnt.size else 0
-    col = np.arange(D)
-    return np.minimum(off[:-1, None] + col[None, :], max(n - 1, 0)), col[None, :] < cnt[:, None]
 
 
 # ---------------------------------------------------------------------------------------------------------- faces
@@ -118,43 +108,6 @@ def _usable(faces, V, frames):
     return ((f >= 0) & (f < V)).all(1) & (f[:, 0] != f[:, 1]) & (f[:, 0] != f[:, 2]) & (f[:, 1] != f[:, 2]) & (frames[:, 3] > 0)
 
 
-# ---------------------------------------------------------------------------------------------------------- the sums
-def canon_sum(terms):
-    """One dot product's terms [n] (term i of vertex or face i) in the canonical order."""
-    n = terms.shape[0]
-    nslots = max((n + BLOCK - 1) // BLOCK, 1)
-    x = np.zeros(nslots * BLOCK)
-    x[:n] = terms
-    slots = _block(x.reshape(nslots, BLOCK))
-    acc = np.zeros(BLOCK)
-    for s0 in range(0, nslots, BLOCK):                      # accumulator t adds the slots t, t + 256, ...
-        part = slots[s0:s0 + BLOCK]
-        acc[:part.shape[0]] = acc[:part.shape[0]] + part
-    return float(_block(acc[None, :])[0])
-
-
-def canon_partials(terms):
-    n = terms.shape[0]
-    nslots = (n + BLOCK - 1) // BLOCK
-    x = np.zeros(nslots * BLOCK)
-    x[:n] = terms
-    return _block(x.reshape(nslots, BLOCK))
-
-
-def _block(x):
-    """[m, 256] -> [m]: the xor butterfly over each wave's 64 lanes, then the four waves from 0."""
-    x = x.reshape(x.shape[0], BLOCK // WAVE, WAVE)
-    lane = np.arange(WAVE)
-    off = WAVE // 2
-    while off:
-        x = x + x[:, :, lane ^ off]
-        off //= 2
-    t = np.zeros(x.shape[0])
-    for w in range(BLOCK // WAVE):
-        t = t + x[:, w, 0]
-    return t
-
-
 # ---------------------------------------------------------------------------------------------------------- the solve
 class System:
     """The counted entries of the neighbour CSR as a padded table, d, the active vertices."""
@@ -162,7 +115,7 @@ class System:
     def __init__(self, off, nbr, w, fixed):
         V = off.shape[0] - 1
         self.V = V
-        pos, valid = _padded(off, nbr.shape[0])
+        pos, valid = padded(off, nbr.shape[0])
         self.j = nbr.astype(np.int64)[pos] if nbr.size else np.zeros(pos.shape, np.int64)
         wk = np.asarray(w, np.float64)[pos] if nbr.size else np.zeros(pos.shape)
         i = np.arange(V)[:, None]
@@ -171,26 +124,19 @@ class System:
         self.j = np.where(self.counted, self.j, 0)
         self.w = np.where(self.counted, wk, 0.)
         self.fixed = np.asarray(fixed).astype(bool)
-        self.d = self._rowsum(self.w)
+        self.d = rowsum(self.w)
         self.active = ~self.fixed & (self.d > 0)
         self.zero_rows = int((~self.fixed & ~(self.d > 0)).sum())
         self.dinv = np.where(self.active, 1. / np.where(self.active, self.d, 1.), 0.)
 
-    def _rowsum(self, terms):
-        """sum over a row's entries, in row order, from 0 (terms of entries that do not count are +0)"""
-        s = np.zeros(terms.shape[:1] + terms.shape[2:])
-        for k in range(terms.shape[1]):
-            s = s + terms[:, k]
-        return s
-
     def apply(self, x):
         """sum_k w_k (x_i - x_j) for the active vertices, 0 elsewhere; x [V,2]"""
         t = np.where(self.counted[:, :, None], self.w[:, :, None] * (x[:, None, :] - x[self.j]), 0.)
-        return np.where(self.active[:, None], self._rowsum(t), 0.)
+        return np.where(self.active[:, None], rowsum(t), 0.)
 
     def fixed_sum(self, u):
         t = np.where((self.counted & self.fixed[self.j])[:, :, None], self.w[:, :, None] * u[self.j], 0.)
-        return self._rowsum(t)
+        return rowsum(t)
 
     def dense(self, rhs, u):
         """The same system by numpy.linalg.solve: (u with the active rows solved, cond(A))."""
@@ -225,40 +171,7 @@ def solve(off, nbr, w, fixed, rhs, u, tol=1e-12, max_iter=None):
     act = S.active[:, None]
     r = np.where(act, rhs - S.apply(u), 0.)
     b = np.where(act, rhs + S.fixed_sum(u), 0.)
-    z = r * S.dinv[:, None]
-    bb = [canon_sum(b[:, c] * b[:, c]) for c in range(2)]
-    rz = [canon_sum(r[:, c] * z[:, c]) for c in range(2)]
-    rr = [canon_sum(r[:, c] * r[:, c]) for c in range(2)]
-    active = [rr[c] > tol * tol * bb[c] for c in range(2)]
-    alpha, beta = [0., 0.], [0., 0.]
-    p = np.zeros((V, 2))
-    iters = 0
-    done = not any(active) or max_iter <= 0
-    with np.errstate(all="ignore"):
-        while not done:
-            p = np.where(act, z + np.array(beta)[None, :] * p, 0.)
-            q = S.apply(p)
-            for c in range(2):
-                pq = canon_sum(p[:, c] * q[:, c])
-                al = np.float64(rz[c]) / np.float64(pq)
-                ok = active[c] and pq > 0 and np.isfinite(al)
-                alpha[c] = float(al) if ok else 0.
-                active[c] = bool(ok)
-            iters += 1
-            u = np.where(act, u + np.array(alpha)[None, :] * p, u)
-            r = np.where(act, r - np.array(alpha)[None, :] * q, 0.)
-            z = r * S.dinv[:, None]
-            for c in range(2):
-                if active[c]:
-                    nrz, nrr = canon_sum(r[:, c] * z[:, c]), canon_sum(r[:, c] * r[:, c])
-                    be = np.float64(nrz) / np.float64(rz[c]) if rz[c] != 0. else np.float64(0.)
-                    beta[c], rz[c], rr[c] = float(be), nrz, nrr
-                    if not (nrr > tol * tol * bb[c]) or not np.isfinite(be):
-                        active[c] = False
-                if not active[c]:
-                    beta[c] = 0.
-            done = not any(active) or iters >= max_iter
-    res = [float(np.sqrt(rr[c] / bb[c])) if bb[c] > 0 else (float(np.sqrt(rr[c])) if rr[c] > 0 else 0.) for c in range(2)]
+    u, iters, res, _ = cg(S.apply, S.dinv, r, b, u, S.active, tol, max_iter)
     return u, iters, res, S.zero_rows
 
 
@@ -303,7 +216,7 @@ def arap_rhs(faces, V, frames, cots, uv):
     X = _flat(frames)
     inside = np.where((f >= 0) & (f < V), f, V)
     soff, slots = slots_csr(inside, V + 1)
-    pos, valid = _padded(soff[:V + 1], slots.shape[0])
+    pos, valid = padded(soff[:V + 1], slots.shape[0])
     rhs = np.zeros((V, 2))
     for col in range(pos.shape[1]):
         slot = slots[pos[:, col]] if slots.size else np.zeros(V, np.int64)

@@ -1,12 +1,14 @@
-"""Laplacian alignment on the GPU: recmv_lap_align_solve against a float64 dense solve (and bit for bit against itself),
-recmv_lap_smooth against its f64 restatement, Laplacian_Optimizer's kernel path against its torch path and its effect on
+"""Laplacian alignment on the GPU: recmv_lap_align_solve against a float64 dense solve (and bit for bit against itself) and
+against the numpy restatement of its recurrence and summation order (tests/cg_reference.py) bit for bit, recmv_lap_smooth against its f64 restatement, Laplacian_Optimizer's kernel path against its torch path and its effect on
 displaced rings, the 40962-vertex template, and register_fl.py --align-curves end to end on a run trained with curves."""
+import functools
 import os
 import shutil
 import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 import torch
 
@@ -16,6 +18,8 @@ sys.path.insert(0, str(REPO / "rec-mv_amd"))
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 DEV = "cuda:0"
 
+import cg_reference as CR  # noqa: E402
+import param_cases as PC  # noqa: E402
 from test_lap_align_cpu import CAPS, cut_sphere, ring  # noqa: E402
 
 
@@ -65,6 +69,93 @@ def test_constraint_free_component_is_unchanged():
     assert iters > 0
     assert torch.equal(u[V:].cpu(), w)
     assert not torch.equal(u[:V].cpu(), v)
+
+
+# ---------------------------------------------------------------------------------------- the solve against its restatement
+def _lifted(rows, cols):
+    """PC.grid(rows, cols) lifted out of its plane, so that no column of the solve is trivial."""
+    v, f = PC.grid(rows, cols)
+    v[:, 2] = (0.25 * np.sin(0.7 * v[:, 0]) * np.cos(0.4 * v[:, 1])).astype(np.float32)
+    return v, f
+
+
+def _sides(v, rows, cols):
+    """The sides j = 0 and j = cols - 1 of the first `rows` grid rows, drawn apart: (cw [V], cwt [V,3]) with weight 1."""
+    side = np.array([r * cols + c for r in range(rows) for c in (0, cols - 1)])
+    cw, cwt = np.zeros(v.shape[0]), np.zeros((v.shape[0], 3))
+    cw[side] = 1.
+    cwt[side] = v[side].astype(np.float64) + np.array([[0.5, -0.3, 0.2]]) * np.where(v[side][:, 1:2] == 0, 1., -1.)
+    return cw, cwt
+
+
+def _triangle():
+    v = np.array([[0., 0., 0.], [1., 0., 0.25], [0., 1., -0.5]], np.float32)
+    cw, cwt = np.array([0., 1., 0.]), np.array([[0., 0., 0.], [1.5, -0.25, 0.5], [0., 0., 0.]])
+    return v, np.array([[0, 1, 2]], np.int64), cw, cwt
+
+
+def _grid300():
+    """15 x 20 vertices: grid rows 0 .. 11 with two constrained sides, rows 12 .. 14 a component of their own without a
+    constraint, and vertex 299 without a face."""
+    v, f = _lifted(15, 20)
+    f = f[(f // 20 <= 11).all(1) | ((f // 20 >= 12).all(1) & (f != 299).all(1))]
+    return (v, f) + _sides(v, 12, 20)
+
+
+def _grid257():
+    v, f = _lifted(257, 257)
+    return (v, f) + _sides(v, 257, 257)
+
+
+# name -> (mesh and constraints, tol, max_iter): the smallest shapes at which the state machine or the reductions can go wrong
+RESTATED = {
+    "one triangle, one slot, a partly filled wave": (_triangle, 1e-12, 100000),
+    "300 vertices, two slots": (_grid300, 1e-12, 100000),
+    "66049 vertices, 259 slots, stopped at the cap": (_grid257, 1e-12, 6),
+    "300 vertices, a column frozen early": (_grid300, 1e-3, 100000),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def restated(name):
+    """(v, f, cw, cwt, offsets, neighbours, restated u, iterations, residuals, where each column froze); computed once."""
+    from recmv import lap_align as LA
+    build, tol, max_iter = RESTATED[name]
+    v, f, cw, cwt = build()
+    off, nbr = (x.numpy() for x in LA.Topology(torch.from_numpy(f), v.shape[0], "cpu").nbr)
+    out = (v, f, cw, cwt, off, nbr) + CR.lap_solve(off, nbr, v, cw, cwt, tol, max_iter)
+    for a in out[:7]:
+        a.setflags(write=False)                                                 # (the tests copy what they hand to torch)
+    return out
+
+
+@pytest.mark.parametrize("name", list(RESTATED))
+def test_solve_has_the_restatements_bits(name):
+    from recmv import lap_align as LA
+    build, tol, max_iter = RESTATED[name]
+    v, f, cw, cwt, off, nbr, want, it, res, frozen = restated(name)
+    V = v.shape[0]
+    topo = LA.Topology(torch.tensor(f), V, DEV)
+    assert np.array_equal(topo.nbr[0].cpu().numpy(), off) and np.array_equal(topo.nbr[1].cpu().numpy(), nbr)
+    vd, cwd, cwtd = torch.tensor(v, device=DEV), torch.tensor(cw), torch.tensor(cwt)
+    u, iters, residuals = LA.solve(topo, vd, cwd, cwtd, tol=tol, max_iter=max_iter)
+    print(name, "iterations", iters, "residuals", residuals, "restatement", it, res, "frozen at", frozen)
+    assert iters == it and residuals == res
+    assert torch.equal(u.cpu(), torch.tensor(want))
+    assert it > 0 and not np.array_equal(want, v)
+    if build is _triangle:
+        assert V == 3 and it < 10 and max(res) <= tol
+    if build is _grid300:
+        assert V == 300 and off[300] == off[299] and max(res) <= tol
+        assert np.array_equal(want[240:], v[240:]) and not np.array_equal(want[:240], v[:240])       # the free component's bits
+    if build is _grid257:
+        assert (V + 255) // 256 == 259 and it == max_iter == 6 and min(res) > tol             # the cap is what is reported
+    if tol == 1e-3:
+        first = int(np.argmin(frozen))
+        assert 0 < frozen[first] and frozen[first] + 2 <= min(k for c, k in enumerate(frozen) if c != first) and max(frozen) == it
+        early = LA.solve(topo, vd, cwd, cwtd, tol=tol, max_iter=frozen[first])[0]
+        assert torch.equal(early[:, first], u[:, first])                          # frozen: the later iterations left it alone
+        assert not torch.equal(early, u)
 
 
 def test_smooth_matches_an_f64_restatement():

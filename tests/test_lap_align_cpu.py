@@ -166,6 +166,20 @@ def test_solve_torch_equals_the_reference_inverse_and_solves_the_normal_equation
     assert ((u[idx] - tgt).norm(dim=1).mean() < 0.5 * (v[idx] - tgt).norm(dim=1).mean())
 
 
+def test_the_restated_cg_solve_agrees_with_solve_torch():
+    """tests/cg_reference.py's lap_solve, which tests/test_gpu_lap_align.py holds the kernels to bit for bit, against the dense
+    solve, to the tolerance that file uses for the kernel path."""
+    import cg_reference as CR
+    v, f, topo, idx, tgt = _problem(level=3)
+    cw, cwt = LA.constraint_weights(idx, tgt, v.shape[0], 1.)
+    off, nbr = (x.numpy() for x in topo.nbr)
+    u, iters, res, _ = CR.lap_solve(off, nbr, v.numpy(), cw.numpy(), cwt.numpy(), 1e-12, 100000)
+    assert u.dtype == np.float32 and 0 < iters < 100000 and max(res) <= 1e-12
+    diag = float((v.max(0).values - v.min(0).values).norm())
+    assert (torch.from_numpy(u).double() - LA.solve_torch(topo, v, cw, cwt).double()).abs().max() <= 1e-5 * diag
+    assert not np.array_equal(u, v.numpy())
+
+
 def test_solve_torch_refuses_large_templates():
     class T:
         V = LA.DENSE_MAX_V + 1

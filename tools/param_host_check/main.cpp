@@ -76,7 +76,7 @@ static bool valid_row(const Mesh& m, int64_t t) {
   return r[0] != r[1] && r[0] != r[2] && r[1] != r[2];
 }
 
-static double half_cot(const double p[3][3], int c) {
+static double plain_half_cot(const double p[3][3], int c) {
   const int a = (c + 1) % 3, b = (c + 2) % 3;
   double e1[3], e2[3];
   for (int k = 0; k < 3; ++k) { e1[k] = p[a][k] - p[c][k]; e2[k] = p[b][k] - p[c][k]; }
@@ -110,7 +110,7 @@ static void plain_frames(const Mesh& m, std::vector<double>& frames, std::vector
     frames[4 * t + 1] = (e1[0] * e2[0] + e1[1] * e2[1] + e1[2] * e2[2]) / x1;
     frames[4 * t + 2] = len / x1;
     frames[4 * t + 3] = 0.5 * len;
-    for (int c = 0; c < 3; ++c) cots[3 * t + c] = half_cot(p, c);
+    for (int c = 0; c < 3; ++c) cots[3 * t + c] = plain_half_cot(p, c);
   }
 }
 
