@@ -49,7 +49,9 @@ extern "C" {
  *        recmv_geodesic_auto_max_vertices, recmv_geodesic_workspace_bytes, recmv_geodesic_check_sources, recmv_geodesic_sweeps,
  *        recmv_geodesic_lds (geodesic distance fields: pure additions, still v11); recmv_param_lds_max_vertices,
  *        recmv_param_auto_max_vertices, recmv_param_solve_workspace_bytes, recmv_param_solve, recmv_param_solve_lds,
- *        recmv_param_face_frames, recmv_param_arap_rhs, recmv_param_distortion (mesh parameterisation: pure additions, still v11).
+ *        recmv_param_face_frames, recmv_param_arap_rhs, recmv_param_distortion (mesh parameterisation: pure additions, still v11);
+ *        recmv_bake_raster, recmv_bake_gutter, recmv_bake_pad, recmv_bake_interpolate, recmv_bake_transfer,
+ *        recmv_bake_vertex_tangents, recmv_bake_encode_normal (texture baking: pure additions, still v11).
  *   v10: recmv_verts_normals, recmv_hard_phong_shade, recmv_hard_phong_params_floats added.  Added since without a bump (no
  *        existing signature changed, and _lib.py rejects a library that lacks them): recmv_knn1, recmv_nricp_energy,
  *        recmv_lap_align_solve, recmv_lap_smooth, recmv_closest_point, recmv_iso_relax, recmv_loop_subdivide,
@@ -1291,6 +1293,63 @@ int recmv_param_arap_rhs(const int64_t* faces, int64_t F, const double* frames, 
                          double* energy, void* stream);
 int recmv_param_distortion(const int64_t* faces, int64_t F, const double* frames, const double* uv, int64_t V, double* out,
                            void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Texture baking (csrc/texture_bake.hip; added to ABI v11, no existing signature changed).  Not in the reference.  The kernels of
+ * recmv/bake.py.  Coverage and barycentrics are float64, un-contracted; attributes are mixed in float32 in a fixed order; the only
+ * atomics are integer.  Images are row-major [H,W]; uv [V,2] float64, faces [F,3] int64.
+ * The coverage rule.  Texel (row y, column x) has its centre at px = (x + 0.5) / W, py = ((H - y) - 0.5) / H (row 0 is v = 1).
+ *   For a directed edge a -> b with lo = min(a, b), hi = max(a, b) by vertex index:
+ *       E = (u_hi - u_lo) (py - v_lo) - (v_hi - v_lo) (px - u_lo), negated if a > b.
+ *   A = the edge function of i0 -> i1 at vertex i2.  A face whose indices are not distinct and in [0, V), or whose A is 0 or
+ *   not finite, covers nothing; A < 0 (flipped in the UV plane) negates its three E.  A face covers a centre iff E12 >= 0,
+ *   E20 >= 0 and E01 >= 0 (edges i1 -> i2, i2 -> i0, i0 -> i1) AND the texel lies in the face's box: columns
+ *   max(0, floor(umin W - 0.5)) .. min(W - 1, ceil(umax W - 0.5)), rows max(0, floor(H - 0.5 - vmax H)) ..
+ *   min(H - 1, ceil(H - 0.5 - vmin H)), evaluated in float64 as written, left to right.  The owner of a texel is the lowest
+ *   covering face id, count the number of covering faces, S = (E12 + E20) + E01 and bary = (E12 / S, E20 / S, E01 / S) cast to
+ *   float32; a texel without an owner has face -1 and bary 0.
+ * recmv_bake_raster: face [H,W] int32 (also the owner image: preset to INT32_MAX, atomicMin, resolved in place), bary [H,W,3]
+ *   float32, count [H,W] int32 (atomicAdd).  lanes = 8 or 64 threads per face walk its box; the launch shape changes no bit.
+ * recmv_bake_gutter: src [H,W] int32.  A covered texel (face >= 0) maps to its own linear index y W + x.  In pass k = 1 ..
+ *   passes a still-empty texel takes the src of the first neighbour filled before pass k, tried in the order W (x - 1), E
+ *   (x + 1), N (y - 1), S (y + 1), NW, NE, SW, SE; texels still empty afterwards hold -1.  scratch: a second [H,W] int32 image
+ *   (may be NULL when passes = 0).
+ * recmv_bake_pad: out [T,C] = image[src[i]] (zeros where src is not in [0, T)); out must not alias image.
+ * recmv_bake_interpolate: out [T,C] (1 <= C <= 16), out[c] = (b0 a0[c] + b1 a1[c]) + b2 a2[c] in float32 with a_k the attribute
+ *   row of corner k of faces[face[i]]; zeros where face[i] is not a valid face.  normalise (C >= 3): the first three channels
+ *   (x, y, z) widened to float64 and divided by sqrt((x x + y y) + z z), cast back; a vector without a finite positive length
+ *   stays as it is.
+ * recmv_bake_transfer: for hit i = (src_face[i], src_point[i]) on the source mesh, with p0, p1, p2 the face's float32 corners
+ *   widened to float64, e1 = p1 - p0, e2 = p2 - p0, d = p - p0, dots as (x0 y0 + x1 y1) + x2 y2:
+ *       det = (e1.e1)(e2.e2) - (e1.e2)(e1.e2);  b1 = ((e2.e2)(d.e1) - (e1.e2)(d.e2)) / det;  b2 = ((e1.e1)(d.e2) - (e1.e2)(d.e1)) / det;
+ *       b0 = (1 - b1) - b2;   det not finite or not > 0 (a degenerate source face): (1, 0, 0).
+ *   bary [T,3] = the three cast to float32, out [T,C] = the mix above of the source attribute; a src_face that is no valid
+ *   face gives zeros in both.
+ * recmv_bake_vertex_tangents: out [V,4] float32.  Per vertex over the (face, corner) codes of recmv.shading.
+ *   vertex_face_adjacency (adj_offsets [V + 1], adj_codes [3F] int32) in their order, float64: a face with A (above) 0 or not
+ *   finite, or with a 3-D area 1/2 |e1 x e2| that is not finite and > 0, adds nothing; otherwise with w = area / A,
+ *   T += w (e1 dv2 - e2 dv1), B += w (e2 du1 - e1 du2) (du_k, dv_k = uv_k - uv_0).  t = T - n (n.T) with n the vertex normal,
+ *   normalised; handedness = -1 if cross(n, t).B < 0 else +1.  No usable face or no finite positive length: (0, 0, 0, 1).
+ * recmv_bake_encode_normal: out [T,3] = 0.5 + 0.5 (N.t', w N.(n x t'), N.n) with N = normal [T,3], n = frame_n [T,3], (t, w') =
+ *   frame_t [T,4], w = -1 if w' < 0 else +1, t' = (t - n (n.t)) / its length (t itself when that length is not finite and > 0):
+ *   the interpolated tangent made orthogonal to the interpolated normal again; float64 from the float32 inputs, cast back;
+ *   zeros where face[i] < 0.
+ * Argument errors (negative sizes, sizes of 2^31 or more, lanes other than 8 and 64, C outside 1 .. 16, NULL pointers with
+ * non-zero sizes) return RECMV_ERR_ARG before any HIP call; empty inputs are no-ops.
+ * ---------------------------------------------------------------------------------------------- */
+int recmv_bake_raster(const double* uv, int64_t V, const int64_t* faces, int64_t F, int64_t H, int64_t W, int32_t lanes,
+                      int32_t* face, float* bary, int32_t* count, void* stream);
+int recmv_bake_gutter(const int32_t* face, int64_t H, int64_t W, int32_t passes, int32_t* src, int32_t* scratch, void* stream);
+int recmv_bake_pad(const float* image, const int32_t* src, int64_t T, int32_t C, float* out, void* stream);
+int recmv_bake_interpolate(const int32_t* face, const float* bary, int64_t T, const int64_t* faces, int64_t F, const float* attr,
+                           int64_t V, int32_t C, int32_t normalise, float* out, void* stream);
+int recmv_bake_transfer(const int64_t* src_face, const float* src_point, int64_t T, const float* src_verts, int64_t V,
+                        const int64_t* src_faces, int64_t F, const float* attr, int32_t C, int32_t normalise, float* bary,
+                        float* out, void* stream);
+int recmv_bake_vertex_tangents(const float* verts, const double* uv, const float* normals, int64_t V, const int64_t* faces,
+                               int64_t F, const int32_t* adj_offsets, const int32_t* adj_codes, float* out, void* stream);
+int recmv_bake_encode_normal(const int32_t* face, const float* normal, const float* frame_n, const float* frame_t, int64_t T,
+                             float* out, void* stream);
 
 #ifdef __cplusplus
 }

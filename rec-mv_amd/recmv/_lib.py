@@ -262,6 +262,13 @@ def _declare(lib):
         "recmv_param_face_frames": (C.c_int, [vp, i64, vp, i64, vp, vp, vp]),
         "recmv_param_arap_rhs": (C.c_int, [vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "recmv_param_distortion": (C.c_int, [vp, i64, vp, vp, i64, vp, vp]),
+        "recmv_bake_raster": (C.c_int, [vp, i64, vp, i64, i64, i64, i32, vp, vp, vp, vp]),
+        "recmv_bake_gutter": (C.c_int, [vp, i64, i64, i32, vp, vp, vp]),
+        "recmv_bake_pad": (C.c_int, [vp, vp, i64, i32, vp, vp]),
+        "recmv_bake_interpolate": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, i32, i32, vp, vp]),
+        "recmv_bake_transfer": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, i32, i32, vp, vp, vp]),
+        "recmv_bake_vertex_tangents": (C.c_int, [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp]),
+        "recmv_bake_encode_normal": (C.c_int, [vp, vp, vp, vp, i64, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)       # AttributeError if the symbol is missing: fail loudly

@@ -282,6 +282,67 @@ def read_obj(name):
                 fs.append([int(x.split('/')[0]) - 1 for x in parts[1:4]])
     return (torch.tensor(vs, dtype=torch.float32).view(-1, 3), torch.tensor(fs, dtype=torch.int64).view(-1, 3))
 
+
+def read_obj_uv(name):
+    """A triangle OBJ with texture coordinates: a dict with 'verts' float32 [V,3], 'faces' int64 [F,3] (0-based), 'colors'
+    float32 [V,3] (the `r g b` after a `v` line's coordinates; None unless every vertex has them), 'uv' float64 [T,2] (the `vt`
+    lines; None without any), 'faces_uv' int64 [F,3] (the second index of `f v/vt` corners; None unless every corner has one),
+    'mtllib' and 'usemtl' (the last such lines' arguments, or None)."""
+    vs, cs, ts, fs, fts, lib, mtl = [], [], [], [], [], None, None
+    with open(name) as fh:
+        for line in fh:
+            parts = line.split()
+            if not parts:
+                continue
+            if parts[0] == 'v':
+                vs.append([float(x) for x in parts[1:4]])
+                if len(parts) >= 7:
+                    cs.append([float(x) for x in parts[4:7]])
+            elif parts[0] == 'vt':
+                ts.append([float(x) for x in parts[1:3]])
+            elif parts[0] == 'f':
+                corners = [x.split('/') for x in parts[1:4]]
+                fs.append([int(c[0]) - 1 for c in corners])
+                if all(len(c) > 1 and c[1] for c in corners):
+                    fts.append([int(c[1]) - 1 for c in corners])
+            elif parts[0] == 'mtllib' and len(parts) > 1:
+                lib = parts[1]
+            elif parts[0] == 'usemtl' and len(parts) > 1:
+                mtl = parts[1]
+    return {'verts': torch.tensor(vs, dtype=torch.float32).view(-1, 3), 'faces': torch.tensor(fs, dtype=torch.int64).view(-1, 3),
+            'colors': torch.tensor(cs, dtype=torch.float32).view(-1, 3) if vs and len(cs) == len(vs) else None,
+            'uv': torch.tensor(ts, dtype=torch.float64).view(-1, 2) if ts else None,
+            'faces_uv': torch.tensor(fts, dtype=torch.int64).view(-1, 3) if fs and len(fts) == len(fs) else None,
+            'mtllib': lib, 'usemtl': mtl}
+
+
+MTL_KEYS = {'color': 'map_Kd', 'tangent_normal': 'norm'}          # the maps a material file has a statement for
+
+
+def write_obj_uv_mtl(name, verts, uv, faces, maps, colors=None, material='baked'):
+    """`name` (an .obj) with `mtllib <stem>.mtl`, `usemtl <material>`, `v x y z [r g b]`, `vt u v` (one per vertex, %.8f) and
+    `f a/a b/b c/c` lines, and beside it <stem>.mtl naming the baked maps: `maps` is {kind: file name}; 'color' becomes `map_Kd`,
+    'tangent_normal' becomes `norm`, any other kind (object-space normals, positions) a `# <kind> <file>` comment."""
+    import os.path as osp
+    v = torch.as_tensor(verts).detach().cpu().float().tolist()
+    t = torch.as_tensor(uv).detach().cpu().double().tolist()
+    f = (torch.as_tensor(faces).detach().cpu().long() + 1).tolist()
+    c = None if colors is None else torch.as_tensor(colors).detach().cpu().float().tolist()
+    stem = osp.splitext(name)[0]
+    with open(name, 'w') as fh:
+        fh.write("mtllib %s.mtl\nusemtl %s\n" % (osp.basename(stem), material))
+        if c is None:
+            fh.write("".join("v %f %f %f\n" % tuple(r) for r in v))
+        else:
+            fh.write("".join("v %f %f %f %f %f %f\n" % tuple(r + k) for r, k in zip(v, c)))
+        fh.write("".join("vt %.8f %.8f\n" % tuple(r) for r in t))
+        fh.write("".join("f %d/%d %d/%d %d/%d\n" % (a, a, b, b, k, k) for a, b, k in f))
+    with open(stem + '.mtl', 'w') as fh:
+        fh.write("newmtl %s\nKa 1.000000 1.000000 1.000000\nKd 1.000000 1.000000 1.000000\nKs 0.000000 0.000000 0.000000\n" % material)
+        for kind, path in maps.items():
+            fh.write("%s %s\n" % (MTL_KEYS[kind], path) if kind in MTL_KEYS else "# %s %s\n" % (kind, path))
+
+
 def smpl_tmp_Apose(init_pose_type=0):
     """utils/utils.py:68-99 — the canonical pose the skinning volume is baked in: legs spread by 10 / 7 / 15 / 15 degrees, arms
     lowered by 45 / 55 / 55 / 0 degrees for `train.skinner_pose_type` 0..3 (axis-angle [24,3], float32)."""
