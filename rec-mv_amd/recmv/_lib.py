@@ -437,7 +437,7 @@ def make_stream(device):
 
 # ---- RECMV_POISON=1: a detector for reads of memory nobody has written yet -----------------------------------------------------
 # Every workspace / output buffer the wrappers allocate with torch.empty goes through `scratch()`.  With RECMV_POISON=1 it is filled
-# with a signalling pattern (NaN for floats, 0x7f bytes for raw workspaces) on the allocating stream before the kernels that are
+# with a signalling pattern (NaN for floats, 0xff bytes for raw workspaces) on the allocating stream before the kernels that are
 # supposed to write it are enqueued: a kernel that reads a column nobody wrote, a fill that arrives after its reader, or a block
 # handed to another stream without a wait then shows as NaN in the loop's results EVERY run instead of as last-bit differences in
 # one run of four (whether a fresh block holds zeros or an earlier tensor's values depends on the allocator's history).
@@ -459,6 +459,21 @@ def scratch(shape, dtype, device):
 
 def scratch_like(x):
     return scratch(tuple(x.shape), x.dtype, x.device) if poison_on() else torch.empty_like(x)
+
+
+def workspace(nbytes, device, what, *, dtype=torch.uint8, floor=8):
+    """The scratch block behind a recmv_*_workspace_bytes answer: at least `floor` bytes, as elements of `dtype`.  A negative
+    answer is the library's refusal: it raises with its last-error text under the name `what`."""
+    nbytes = int(nbytes)
+    if nbytes < 0:
+        check(-1, what)
+    return scratch((max(nbytes, floor) // dtype.itemsize,), dtype, device)
+
+
+def launch(name, device, *args):
+    """recmv_<name>(*args, stream) on the current stream of `device`, checked."""
+    with device_guard(device):
+        check(getattr(lib(), "recmv_" + name)(*args, stream_ptr(device)), name)
 
 
 def desc5(t) -> Tensor5:

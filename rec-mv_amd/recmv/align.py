@@ -29,6 +29,7 @@ import torch
 from . import _lib as L
 from . import metrics
 from .connectivity import EdgeTable
+from .mesh_args import check_mesh, check_points
 
 N_SUMS = 56                     # RECMV_ICP_SUMS of include/recmv_hip.h
 MODES = ('rigid', 'similarity')
@@ -55,7 +56,7 @@ def icp_sums(x, q, face, dist2, verts, faces, border=None, max_dist2=None, centr
     x [P,3] f32 and its closest points q [P,3] f32 / face [P] int64 / dist2 [P] f32 on the mesh verts [V,3] f32 / faces
     [F,3] int64 (CUDA tensors on one device).  `border`: border_flags of the mesh, uint8 [F] on the device; `max_dist2`: a
     number, or a float32 tensor of one element on the device (no read-back); `centre`: three host numbers."""
-    metrics._check_mesh(verts, faces)
+    verts, faces = check_mesh(verts, faces, allow_empty=False)
     dev = verts.device
     for t, name, dtype, shape in ((x, "x", torch.float32, (-1, 3)), (q, "q", torch.float32, (-1, 3)),
                                   (face, "face", torch.int64, (-1,)), (dist2, "dist2", torch.float32, (-1,))):
@@ -81,15 +82,11 @@ def icp_sums(x, q, face, dist2, verts, faces, border=None, max_dist2=None, centr
         else:
             max_dist2 = torch.tensor([float(max_dist2)], dtype=torch.float32, device=dev)
     c = (C.c_double * 3)(*(float(v) for v in centre))
-    x, q, face, dist2, verts, faces = (t.contiguous() for t in (x, q, face, dist2, verts, faces))
-    lib = L.lib()
+    x, q, face, dist2 = (t.contiguous() for t in (x, q, face, dist2))
     sums = L.scratch((N_SUMS,), torch.float64, dev)
-    nbytes = int(lib.recmv_icp_accumulate_workspace_bytes(P))
-    ws = L.scratch((max(nbytes, 8),), torch.uint8, dev)
-    with L.device_guard(dev):
-        L.check(lib.recmv_icp_accumulate(L.ptr(x), L.ptr(q), L.ptr(face), L.ptr(dist2), P, L.ptr(verts), verts.shape[0],
-                                         L.ptr(faces), faces.shape[0], L.ptr(border), L.ptr(max_dist2), c, int(bool(plane)),
-                                         L.ptr(sums), L.ptr(ws), nbytes, L.stream_ptr(dev)), "icp_accumulate")
+    ws = L.workspace(nbytes := int(L.lib().recmv_icp_accumulate_workspace_bytes(P)), dev, "icp_accumulate_workspace_bytes")
+    L.launch("icp_accumulate", dev, L.ptr(x), L.ptr(q), L.ptr(face), L.ptr(dist2), P, L.ptr(verts), verts.shape[0], L.ptr(faces),
+             faces.shape[0], L.ptr(border), L.ptr(max_dist2), c, int(bool(plane)), L.ptr(sums), L.ptr(ws), nbytes)
     return sums
 
 
@@ -228,16 +225,12 @@ def icp(src_v, src_f, dst_v, dst_f, mode='rigid', metric='plane', samples=20000,
     if int(iters) < 0 or int(samples) < 0:
         raise ValueError("iters and samples must not be negative")
     metrics.use_grid(method, 0, 0)
-    metrics._check_mesh(dst_v, dst_f)
+    dst_v, dst_f = check_mesh(dst_v, dst_f, allow_empty=False)
     dev = dst_v.device
-    dst_v, dst_f = dst_v.contiguous(), dst_f.contiguous()
     if points is not None:
-        L.require_cuda(points, "points")
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError("points must be float32 of shape [P,3]")
-        p = points
+        p = check_points(points, "points", shape="[P,3]")
     else:
-        metrics._check_mesh(src_v, src_f)
+        check_mesh(src_v, src_f, allow_empty=False)
         p = src_v if int(samples) == 0 else metrics.sample_surface(
             src_v, src_f, int(samples), torch.Generator(device=src_v.device).manual_seed(int(seed)))[0]
     if p.device != dev:

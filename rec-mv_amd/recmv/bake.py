@@ -113,9 +113,8 @@ def rasterize_uv(uv, faces, size, lanes=None):
     lanes = default_lanes(uv, faces, (H, W)) if lanes is None else int(lanes)
     face, count = L.scratch((H, W), torch.int32, dev), L.scratch((H, W), torch.int32, dev)
     bary = L.scratch((H, W, 3), torch.float32, dev)
-    with L.device_guard(dev):
-        L.check(L.lib().recmv_bake_raster(L.ptr(uv), uv.shape[0], L.ptr(faces), faces.shape[0], H, W, lanes, L.ptr(face),
-                                          L.ptr(bary), L.ptr(count), L.stream_ptr(dev)), "bake_raster")
+    L.launch("bake_raster", dev, L.ptr(uv), uv.shape[0], L.ptr(faces), faces.shape[0], H, W, lanes, L.ptr(face), L.ptr(bary),
+             L.ptr(count))
     return face, bary, count
 
 
@@ -131,8 +130,7 @@ def gutter(face, passes=4):
     H, W = face.shape
     src = L.scratch((H, W), torch.int32, dev)
     tmp = L.scratch((H, W), torch.int32, dev) if int(passes) else None
-    with L.device_guard(dev):
-        L.check(L.lib().recmv_bake_gutter(L.ptr(face), H, W, int(passes), L.ptr(src), L.ptr(tmp), L.stream_ptr(dev)), "bake_gutter")
+    L.launch("bake_gutter", dev, L.ptr(face), H, W, int(passes), L.ptr(src), L.ptr(tmp))
     return src
 
 
@@ -150,9 +148,7 @@ def pad(image, src):
     image, src = image.contiguous(), src.contiguous()
     out = L.scratch(tuple(image.shape), torch.float32, image.device)
     T = src.numel()
-    with L.device_guard(image.device):
-        L.check(L.lib().recmv_bake_pad(L.ptr(image), L.ptr(src), T, image.numel() // T if T else 0, L.ptr(out),
-                                       L.stream_ptr(image.device)), "bake_pad")
+    L.launch("bake_pad", image.device, L.ptr(image), L.ptr(src), T, image.numel() // T if T else 0, L.ptr(out))
     return out
 
 
@@ -169,10 +165,8 @@ def interpolate(face, bary, faces, attr, normalise=False):
     _cuda((face, "face"), (bary, "bary"), (faces, "faces"), (attr, "attr"))
     face, bary, faces, attr, dev = face.contiguous(), bary.contiguous(), faces.contiguous(), attr.contiguous(), face.device
     out = L.scratch(tuple(face.shape) + (C,), torch.float32, dev)
-    with L.device_guard(dev):
-        L.check(L.lib().recmv_bake_interpolate(L.ptr(face), L.ptr(bary), face.numel(), L.ptr(faces), faces.shape[0], L.ptr(attr),
-                                               attr.shape[0], C, int(bool(normalise)), L.ptr(out), L.stream_ptr(dev)),
-                "bake_interpolate")
+    L.launch("bake_interpolate", dev, L.ptr(face), L.ptr(bary), face.numel(), L.ptr(faces), faces.shape[0], L.ptr(attr),
+             attr.shape[0], C, int(bool(normalise)), L.ptr(out))
     return out
 
 
@@ -191,9 +185,8 @@ def vertex_tangents(verts, faces, uv, normals):
     V, F, dev = verts.shape[0], faces.shape[0], verts.device
     off, codes = shading.vertex_face_adjacency(faces, V)
     out = L.scratch((V, 4), torch.float32, dev)
-    with L.device_guard(dev):
-        L.check(L.lib().recmv_bake_vertex_tangents(L.ptr(verts), L.ptr(uv), L.ptr(normals), V, L.ptr(faces), F, L.ptr(off),
-                                                   L.ptr(codes), L.ptr(out), L.stream_ptr(dev)), "bake_vertex_tangents")
+    L.launch("bake_vertex_tangents", dev, L.ptr(verts), L.ptr(uv), L.ptr(normals), V, L.ptr(faces), F, L.ptr(off), L.ptr(codes),
+             L.ptr(out))
     return out
 
 
@@ -208,10 +201,8 @@ def encode_normal(face, normal, frame_n, frame_t):
     _cuda((face, "face"), (normal, "normal"), (frame_n, "frame_n"), (frame_t, "frame_t"))
     dev = face.device
     out = L.scratch(tuple(face.shape) + (3,), torch.float32, dev)
-    with L.device_guard(dev):
-        L.check(L.lib().recmv_bake_encode_normal(L.ptr(face.contiguous()), L.ptr(normal.contiguous()), L.ptr(frame_n.contiguous()),
-                                                 L.ptr(frame_t.contiguous()), face.numel(), L.ptr(out), L.stream_ptr(dev)),
-                "bake_encode_normal")
+    L.launch("bake_encode_normal", dev, L.ptr(face.contiguous()), L.ptr(normal.contiguous()), L.ptr(frame_n.contiguous()),
+             L.ptr(frame_t.contiguous()), face.numel(), L.ptr(out))
     return out
 
 
@@ -279,11 +270,9 @@ def transfer(src_face, src_point, src_verts, src_faces, src_attr, normalise=Fals
     _cuda((src_face, "src_face"), (src_point, "src_point"), (src_verts, "src_verts"), (src_faces, "src_faces"), (src_attr, "src_attr"))
     T, dev = src_face.shape[0], src_face.device
     bary, out = L.scratch((T, 3), torch.float32, dev), L.scratch((T, C), torch.float32, dev)
-    with L.device_guard(dev):
-        L.check(L.lib().recmv_bake_transfer(L.ptr(src_face.contiguous()), L.ptr(src_point.contiguous()), T, L.ptr(src_verts.contiguous()),
-                                            src_verts.shape[0], L.ptr(src_faces.contiguous()), src_faces.shape[0],
-                                            L.ptr(src_attr.contiguous()), C, int(bool(normalise)), L.ptr(bary), L.ptr(out),
-                                            L.stream_ptr(dev)), "bake_transfer")
+    L.launch("bake_transfer", dev, L.ptr(src_face.contiguous()), L.ptr(src_point.contiguous()), T, L.ptr(src_verts.contiguous()),
+             src_verts.shape[0], L.ptr(src_faces.contiguous()), src_faces.shape[0], L.ptr(src_attr.contiguous()), C,
+             int(bool(normalise)), L.ptr(bary), L.ptr(out))
     return (out, bary) if return_bary else out
 
 

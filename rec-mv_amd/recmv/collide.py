@@ -50,18 +50,14 @@ def point_mesh_nearest(p, verts, faces):
     p [B,N,3] f32: (face [B,N] int64, squared distance [B,N] f32); ties go to the lowest face id."""
     _check(p, verts, faces)
     p, verts, faces = p.contiguous(), verts.contiguous(), faces.contiguous()
-    B, N = p.shape[0], p.shape[1]
-    face = torch.empty(B, N, dtype=torch.int64, device=p.device)
-    sqdist = torch.empty(B, N, dtype=torch.float32, device=p.device)
+    B, N, dev = p.shape[0], p.shape[1], p.device
+    face = L.scratch((B, N), torch.int64, dev)
+    sqdist = L.scratch((B, N), torch.float32, dev)
     if B == 0 or N == 0:
         return face, sqdist
-    lib = L.lib()
-    nbytes = int(lib.recmv_point_mesh_nearest_workspace_bytes(B, N))
-    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=p.device)
-    with L.device_guard(p.device):
-        L.check(lib.recmv_point_mesh_nearest(L.ptr(p), L.ptr(verts), L.ptr(faces), B, N, verts.shape[1], faces.shape[0],
-                                             L.ptr(face), L.ptr(sqdist), L.ptr(ws), nbytes, L.stream_ptr(p.device)),
-                "point_mesh_nearest")
+    ws = L.workspace(nbytes := int(L.lib().recmv_point_mesh_nearest_workspace_bytes(B, N)), dev, "point_mesh_nearest_workspace_bytes")
+    L.launch("point_mesh_nearest", dev, L.ptr(p), L.ptr(verts), L.ptr(faces), B, N, verts.shape[1], faces.shape[0], L.ptr(face),
+             L.ptr(sqdist), L.ptr(ws), nbytes)
     return face, sqdist
 
 
@@ -81,15 +77,13 @@ def collision_push(p, verts, vnormals, faces, face, eps=COLLISION_EPS, max_depth
         raise ValueError("eps and max_depth must not be negative")
     p, verts, vnormals, faces, face = (t.contiguous() for t in (p, verts, vnormals, faces, face))
     B, N = p.shape[0], p.shape[1]
-    out = torch.empty_like(p)
+    out = L.scratch_like(p)
     moved = torch.zeros(B, dtype=torch.int32, device=p.device)
     unresolved = torch.zeros(B, dtype=torch.int32, device=p.device)
     if B == 0:
         return out, moved, unresolved
-    with L.device_guard(p.device):
-        L.check(L.lib().recmv_collision_push(L.ptr(p), L.ptr(verts), L.ptr(vnormals), L.ptr(faces), L.ptr(face), B, N,
-                                             verts.shape[1], faces.shape[0], float(eps), float(max_depth), L.ptr(out),
-                                             L.ptr(moved), L.ptr(unresolved), L.stream_ptr(p.device)), "collision_push")
+    L.launch("collision_push", p.device, L.ptr(p), L.ptr(verts), L.ptr(vnormals), L.ptr(faces), L.ptr(face), B, N, verts.shape[1],
+             faces.shape[0], float(eps), float(max_depth), L.ptr(out), L.ptr(moved), L.ptr(unresolved))
     return out, moved, unresolved
 
 

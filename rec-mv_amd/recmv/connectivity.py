@@ -95,6 +95,15 @@ def vertex_slots_csr(faces, V):
     return off, o
 
 
+def filed_slots_csr(faces, V):
+    """vertex_slots_csr of faces that may hold indices outside [0, V): such corners are filed under a row of their own, V,
+    which no vertex reads — (offsets int64 [V+1], slots int64 [3F]), both contiguous."""
+    if faces.shape[0] == 0:
+        return (torch.zeros(V + 1, dtype=torch.int64, device=faces.device), torch.zeros(0, dtype=torch.int64, device=faces.device))
+    off, slots = vertex_slots_csr(torch.where((faces >= 0) & (faces < V), faces, V), V + 1)
+    return off[:V + 1].contiguous(), slots.contiguous()
+
+
 def boundary_edges_csr(table):
     """The border of an EdgeTable as the quadric kernel reads it: (border [B,3] int64 = (v0, v1, the one face that uses the edge),
     in edge order; offsets int64 [V+1], rows int64 [2B]: vertex -> its rows of border, ascending)."""

@@ -17,6 +17,7 @@ import torch
 
 from . import _lib as L
 from . import connectivity
+from .mesh_args import check_mesh
 
 ROUTES = ('auto', 'sweeps', 'lds')
 DEFAULT_CHECK_EVERY = 32         # sweeps between two read-backs of last_changed on the sweeps route
@@ -32,37 +33,14 @@ def auto_max_vertices():
     return int(L.lib().recmv_geodesic_auto_max_vertices())
 
 
-def _check_mesh(verts, faces, cuda=True):
-    """Shapes and dtypes first (ValueError), then the device (RuntimeError): the argument errors do not need a GPU."""
-    if not (isinstance(verts, torch.Tensor) and isinstance(faces, torch.Tensor)):
-        raise ValueError("verts and faces must be tensors")
-    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError("verts must be float32 of shape [V,3]")
-    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("faces must be int64 of shape [F,3]")
-    if verts.device != faces.device:
-        raise ValueError("verts and faces must be on one device")
-    if cuda:
-        L.require_cuda(verts, "verts")
-        L.require_cuda(faces, "faces")
-
-
 class _Mesh:
     """The tables a solve reads, built once per mesh: contiguous verts and faces and the vertex -> corner-slot CSR of
     connectivity.vertex_slots_csr.  Corners outside [0, V) are filed under a row of their own, V, which no vertex reads."""
 
     def __init__(self, verts, faces):
-        _check_mesh(verts, faces)
-        self.verts, self.faces = verts.contiguous(), faces.contiguous()
+        self.verts, self.faces = check_mesh(verts, faces)
         self.V, self.F, self.device = verts.shape[0], faces.shape[0], verts.device
-        V = self.V
-        if self.F:
-            filed = torch.where((self.faces >= 0) & (self.faces < V), self.faces, V)
-            off, slots = connectivity.vertex_slots_csr(filed, V + 1)
-            self.off, self.slots = off[:V + 1].contiguous(), slots.contiguous()
-        else:
-            self.off = torch.zeros(V + 1, dtype=torch.int64, device=self.device)
-            self.slots = torch.zeros(0, dtype=torch.int64, device=self.device)
+        self.off, self.slots = connectivity.filed_slots_csr(self.faces, self.V)
 
     def args(self):
         return (L.ptr(self.verts), self.V, L.ptr(self.faces), self.F, L.ptr(self.off), L.ptr(self.slots))
@@ -107,31 +85,25 @@ def _initial(V, B, idx, val, device):
 
 def _solve(mesh, D0, route, max_sweeps, check_every):
     """(D [B, V], sweeps [B] int64 on the host) of the initial fields D0 on one route."""
-    lib = L.lib()
     B, V, dev = D0.shape[0], mesh.V, mesh.device
     if V == 0 or B == 0:
         return D0, torch.zeros(B, dtype=torch.int64)
     if route == 'lds':
         D = L.scratch((B, V), torch.float64, dev)
         sweeps = L.scratch((B,), torch.int32, dev)
-        with L.device_guard(dev):
-            L.check(lib.recmv_geodesic_lds(*mesh.args(), B, L.ptr(D0), L.ptr(D), L.ptr(sweeps), max_sweeps, L.stream_ptr(dev)),
-                    "geodesic_lds")
+        L.launch("geodesic_lds", dev, *mesh.args(), B, L.ptr(D0), L.ptr(D), L.ptr(sweeps), max_sweeps)
         sweeps = sweeps.cpu().to(torch.int64)
         if bool((sweeps < 0).any()):
             raise RuntimeError("geodesic distance: not converged within max_sweeps=%d sweeps" % max_sweeps)
         return D, sweeps
-    nbytes = int(lib.recmv_geodesic_workspace_bytes(V, mesh.F, B))
-    if nbytes < 0:
-        L.check(-1, "geodesic_workspace_bytes")
-    ws = L.scratch((nbytes // 8,), torch.float64, dev)
+    ws = L.workspace(nbytes := int(L.lib().recmv_geodesic_workspace_bytes(V, mesh.F, B)), dev, "geodesic_workspace_bytes",
+                     dtype=torch.float64)
     ws[:B * V].copy_(D0.view(-1))
     last = ws[nbytes // 8 - (4 * B + 7) // 8:].view(torch.int32)[:B]
     done = 0
     while True:
         n = min(check_every, max_sweeps + 1 - done)
-        with L.device_guard(dev):
-            L.check(lib.recmv_geodesic_sweeps(*mesh.args(), B, L.ptr(ws), nbytes, done, n, L.stream_ptr(dev)), "geodesic_sweeps")
+        L.launch("geodesic_sweeps", dev, *mesh.args(), B, L.ptr(ws), nbytes, done, n)
         done += n
         sweeps = last.cpu().to(torch.int64)                # (the one read-back per interval)
         if int(sweeps.max()) < done:                       # the last sweep lowered nothing anywhere
@@ -145,7 +117,7 @@ def _distance(verts, faces, sources, values, route, max_sweeps, check_every, mes
     """(D [B, V], sweeps [B]) of a list of source tensors.  Every argument error is raised before the device is touched."""
     if route not in ROUTES:
         raise ValueError("route must be one of %r (got %r)" % (ROUTES, route))
-    _check_mesh(verts, faces, cuda=False)
+    check_mesh(verts, faces, cuda=False)
     V = verts.shape[0]
     max_sweeps = V + 1 if max_sweeps is None else int(max_sweeps)
     if not (0 <= max_sweeps <= 1 << 30):
@@ -240,7 +212,7 @@ def farthest_points(verts, faces, k, first=0, route='auto'):
     """Farthest-point sampling by geodesic distance: (ids, the running minimum field [V]).  ids[0] = first; each further id is
     the argmax of the running minimum over its finite entries, the lowest id among equal maxima.  Every field is solved
     afresh and folded in by an elementwise minimum.  Fewer than k ids come back when only +inf and 0 remain."""
-    _check_mesh(verts, faces, cuda=False)
+    check_mesh(verts, faces, cuda=False)
     V, k, first = verts.shape[0], int(k), int(first)
     if route not in ROUTES:
         raise ValueError("route must be one of %r (got %r)" % (ROUTES, route))

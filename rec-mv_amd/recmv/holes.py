@@ -57,6 +57,7 @@ import torch
 
 from . import _lib as L
 from .connectivity import EdgeTable
+from .mesh_args import check_mesh, check_points, info_json  # noqa: F401  (info_json: the JSON-able part of fill's info)
 from .topology import valid_faces
 
 MAX_LOOP_EDGES = 4096                                      # csrc/hole_fill.hip: kHoleMaxN
@@ -68,23 +69,6 @@ REFINE_RATIO = 4. / 3.
 ROUTES = {'auto': 0, 'lds': 1, 'global': 2}
 STATUSES = ('filled', 'nonsimple', 'duplicate', 'max_edges', 'max_perimeter', 'keep_largest', 'too_large', 'nonfinite',
             'chord_conflict')
-
-
-def _check(verts, faces, cuda):
-    if not isinstance(verts, torch.Tensor) or not isinstance(faces, torch.Tensor):
-        raise ValueError("verts and faces must be tensors")
-    if cuda:
-        L.require_cuda(verts, "verts")
-        L.require_cuda(faces, "faces")
-    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError("verts must be float32 of shape [V,3]")
-    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("faces must be int64 of shape [F,3]")
-    if verts.device != faces.device:
-        raise ValueError("verts and faces must be on one device")
-    if verts.shape[0] >= 1 << 31 or faces.shape[0] >= 1 << 31:
-        raise ValueError("at most 2^31 - 1 vertices and faces")
-    return verts.contiguous(), faces.contiguous()
 
 
 def _find(verts, faces):
@@ -160,7 +144,7 @@ def find_loops(verts, faces):
     boundary loops, flat, on the mesh's device, and per loop table['edges'], table['perimeter'] (float64) and table['status']
     ('open' | 'nonsimple' | 'duplicate') before any selection; the module docstring has the definitions.  Plain torch and one
     read-back: it runs where the tensors live.  ValueError for a mesh that is not edge-manifold or not consistently oriented."""
-    verts, faces = _check(verts, faces, cuda=False)
+    verts, faces = check_mesh(verts, faces, cuda=False, cap31=True)
     loops, table, _ = _find(verts, faces)
     lv, lo = _flat(loops, faces.device)
     return lv, lo.to(faces.device), table
@@ -174,16 +158,14 @@ def triangulate_loops(verts, loop_verts, loop_offsets, route='auto'):
     vertices in LDS, 'lds' refuses a loop of more than LDS_MAX_EDGES."""
     if route not in ROUTES:
         raise ValueError("route must be one of %s" % (sorted(ROUTES),))
-    L.require_cuda(verts, "verts")
+    verts = check_points(verts, "verts", shape="[V,3]")
     L.require_cuda(loop_verts, "loop_verts")
-    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError("verts must be float32 of shape [V,3]")
     if loop_verts.dtype != torch.int64 or loop_verts.dim() != 1 or loop_offsets.dtype != torch.int64 or loop_offsets.dim() != 1:
         raise ValueError("loop_verts and loop_offsets must be int64 vectors")
     if loop_offsets.shape[0] < 1:
         raise ValueError("loop_offsets must have L + 1 entries")
     dev = verts.device
-    verts, loop_verts = verts.contiguous(), loop_verts.contiguous()
+    loop_verts = loop_verts.contiguous()
     host = loop_offsets.cpu().contiguous()
     n_loops = host.shape[0] - 1
     if int(host[0]) != 0 or int(host[-1]) != loop_verts.shape[0]:
@@ -197,12 +179,10 @@ def triangulate_loops(verts, loop_verts, loop_offsets, route='auto'):
     ws_bytes = lib.recmv_hole_triangulate_workspace_bytes(hp, n_loops, ROUTES[route])
     if ws_bytes < 0:
         raise ValueError("triangulate_loops: " + lib.recmv_last_error().decode())
-    ws = L.scratch((ws_bytes,), torch.uint8, dev) if ws_bytes else None
+    ws = L.workspace(ws_bytes, dev, "hole_triangulate_workspace_bytes") if ws_bytes else None
     offsets_dev = host.to(dev) if not loop_offsets.is_cuda else loop_offsets.contiguous()
-    with L.device_guard(dev):
-        L.check(lib.recmv_hole_triangulate(L.ptr(verts), verts.shape[0], L.ptr(loop_verts), hp, L.ptr(offsets_dev), n_loops,
-                                           L.ptr(faces), L.ptr(weight), L.ptr(ws), ws_bytes, ROUTES[route], L.stream_ptr(dev)),
-                "hole_triangulate")
+    L.launch("hole_triangulate", dev, L.ptr(verts), verts.shape[0], L.ptr(loop_verts), hp, L.ptr(offsets_dev), n_loops,
+             L.ptr(faces), L.ptr(weight), L.ptr(ws), ws_bytes, ROUTES[route])
     return faces, weight
 
 
@@ -360,7 +340,7 @@ def fill(verts, faces, max_edges=None, max_perimeter=None, keep_largest=0, refin
     'perimeter', 'status', 'patch_area' (None unless filled), 'faces_added', 'verts_added', 'face_start' (-1 unless filled);
     'refine_rounds', 'refine_capped'.  RuntimeError for CPU tensors, ValueError for a mesh that is not edge-manifold or not
     consistently oriented, and for fair_iterations without refine (there is no new vertex to move)."""
-    verts, faces = _check(verts, faces, cuda=True)
+    verts, faces = check_mesh(verts, faces, cap31=True)
     if route not in ROUTES:
         raise ValueError("route must be one of %s" % (sorted(ROUTES),))
     if max_edges is not None and int(max_edges) < 0 or int(keep_largest) < 0 or int(fair_iterations) < 0:
@@ -441,10 +421,3 @@ def fill(verts, faces, max_edges=None, max_perimeter=None, keep_largest=0, refin
                                   boundary='fixed', fixed=fixed)
         out_v = torch.cat([verts, faired[V:].to(torch.float32)]).contiguous()
     return out_v, out_f, info
-
-
-def info_json(info):
-    """The JSON-able part of fill's info: numbers, strings and lists of them."""
-    plain = (bool, int, float, str, type(None))
-    return {k: (list(x) if isinstance(x, (list, tuple)) else x) for k, x in info.items()
-            if isinstance(x, plain) or (isinstance(x, (list, tuple)) and all(isinstance(y, plain) for y in x))}

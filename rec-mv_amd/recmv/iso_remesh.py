@@ -19,6 +19,7 @@ import torch
 from . import _lib as L
 from . import nricp
 from .connectivity import EdgeTable, compact, neighbours_csr, vertex_slots_csr
+from .mesh_args import check_mesh, check_points
 
 MAX_PASSES = 16                    # split passes, collapse rounds and flip rounds per iteration
 
@@ -27,27 +28,17 @@ MAX_PASSES = 16                    # split passes, collapse rounds and flip roun
 def closest_point(p, verts, faces):
     """Exact closest point on the mesh (verts [V,3] f32, faces [F,3] int64, CUDA) of every row of p [P,3] f32:
     (face [P] int64, point [P,3] f32, squared distance [P] f32); ties go to the lowest face id."""
-    nricp._check_points(p, "p")
-    nricp._check_points(verts, "verts")
-    L.require_cuda(faces, "faces")
-    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("faces must be int64 of shape [F,3]")
-    if faces.shape[0] == 0 or verts.shape[0] == 0:
-        raise ValueError("closest_point: the surface is empty")
-    p, verts, faces = p.contiguous(), verts.contiguous(), faces.contiguous()
-    P = p.shape[0]
-    face = torch.empty(P, dtype=torch.int64, device=p.device)
-    point = torch.empty(P, 3, dtype=torch.float32, device=p.device)
-    dist2 = torch.empty(P, dtype=torch.float32, device=p.device)
+    p = check_points(p, "p")
+    verts, faces = check_mesh(verts, faces, allow_empty=False)
+    P, dev = p.shape[0], p.device
+    face = L.scratch((P,), torch.int64, dev)
+    point = L.scratch((P, 3), torch.float32, dev)
+    dist2 = L.scratch((P,), torch.float32, dev)
     if P == 0:
         return face, point, dist2
-    lib = L.lib()
-    nbytes = int(lib.recmv_closest_point_workspace_bytes(P))
-    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=p.device)
-    with L.device_guard(p.device):
-        L.check(lib.recmv_closest_point(L.ptr(p), P, L.ptr(verts), verts.shape[0], L.ptr(faces), faces.shape[0],
-                                        L.ptr(face), L.ptr(point), L.ptr(dist2), L.ptr(ws), nbytes,
-                                        L.stream_ptr(p.device)), "closest_point")
+    ws = L.workspace(nbytes := int(L.lib().recmv_closest_point_workspace_bytes(P)), dev, "closest_point_workspace_bytes")
+    L.launch("closest_point", dev, L.ptr(p), P, L.ptr(verts), verts.shape[0], L.ptr(faces), faces.shape[0], L.ptr(face),
+             L.ptr(point), L.ptr(dist2), L.ptr(ws), nbytes)
     return face, point, dist2
 
 
@@ -121,18 +112,14 @@ def _gather_sum(x, nbr):
 
 def iso_relax(verts, normals, fixed, nbr_csr):
     """recmv_iso_relax: p + (I - n n^T)(c - p) for the free vertices (verts / normals [V,3] f32 CUDA, fixed [V] bool)."""
-    nricp._check_points(verts, "verts")
-    nricp._check_points(normals, "normals")
+    verts, normals = check_points(verts, "verts"), check_points(normals, "normals")
     V = verts.shape[0]
     off, idx = nbr_csr
     if normals.shape[0] != V or fixed.shape[0] != V or off.numel() != V + 1:
         raise ValueError("iso_relax: normals, fixed and the neighbour list must have %d rows" % V)
-    verts, normals = verts.contiguous(), normals.contiguous()
     fx = fixed.to(torch.uint8).contiguous()
-    out = torch.empty_like(verts)
-    with L.device_guard(verts.device):
-        L.check(L.lib().recmv_iso_relax(L.ptr(off), L.ptr(idx), V, idx.numel(), L.ptr(verts), L.ptr(normals), L.ptr(fx),
-                                        L.ptr(out), L.stream_ptr(verts.device)), "iso_relax")
+    out = L.scratch_like(verts)
+    L.launch("iso_relax", verts.device, L.ptr(off), L.ptr(idx), V, idx.numel(), L.ptr(verts), L.ptr(normals), L.ptr(fx), L.ptr(out))
     return out
 
 
@@ -625,14 +612,12 @@ def _loop_once_torch(verts, etab, bn, nbr_csr):
 
 
 def _loop_once_kernel(verts, etab, bn, nbr_csr):
-    nricp._check_points(verts, "verts")
+    verts = check_points(verts, "verts")
     V, E = verts.shape[0], etab.shape[0]
     off, idx = nbr_csr
-    verts = verts.contiguous()
-    out = torch.empty(V + E, 3, dtype=torch.float32, device=verts.device)
-    with L.device_guard(verts.device):
-        L.check(L.lib().recmv_loop_subdivide(L.ptr(off), L.ptr(idx), V, idx.numel(), L.ptr(verts), L.ptr(bn), L.ptr(etab),
-                                             E, L.ptr(out), L.stream_ptr(verts.device)), "loop_subdivide")
+    out = L.scratch((V + E, 3), torch.float32, verts.device)
+    L.launch("loop_subdivide", verts.device, L.ptr(off), L.ptr(idx), V, idx.numel(), L.ptr(verts), L.ptr(bn), L.ptr(etab), E,
+             L.ptr(out))
     return out
 
 

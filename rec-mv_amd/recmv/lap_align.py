@@ -157,17 +157,13 @@ def solve(topo, v, cw, cwt, tol=TOL, max_iter=MAX_ITER):
     cwt = torch.as_tensor(cwt).to(device=v.device, dtype=torch.float64).contiguous()
     if cw.shape != (V,) or cwt.shape != (V, 3):
         raise ValueError("lap_align_solve: cw must be [%d] and cwt [%d,3]" % (V, V))
-    u = torch.empty_like(v)
+    u = L.scratch_like(v)
     iters = C.c_int32(0)
     res = (C.c_double * 3)()
-    lib = L.lib()
-    nbytes = int(lib.recmv_lap_align_workspace_bytes(V))
-    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=v.device)
+    ws = L.workspace(nbytes := int(L.lib().recmv_lap_align_workspace_bytes(V)), v.device, "lap_align_workspace_bytes", floor=256)
     off, nbr = topo.nbr
-    with L.device_guard(v.device):
-        L.check(lib.recmv_lap_align_solve(L.ptr(off), L.ptr(nbr), V, nbr.shape[0], L.ptr(v), L.ptr(cw), L.ptr(cwt),
-                                          float(tol), int(max_iter), L.ptr(u), C.byref(iters), res, L.ptr(ws), nbytes,
-                                          L.stream_ptr(v.device)), "lap_align_solve")
+    L.launch("lap_align_solve", v.device, L.ptr(off), L.ptr(nbr), V, nbr.shape[0], L.ptr(v), L.ptr(cw), L.ptr(cwt), float(tol),
+             int(max_iter), L.ptr(u), C.byref(iters), res, L.ptr(ws), nbytes)
     return u, int(iters.value), [float(r) for r in res]
 
 
@@ -178,11 +174,9 @@ def smooth(topo, u):
     if u.dtype != torch.float32 or u.shape != (V, 3):
         raise ValueError("lap_smooth: u must be float32 [%d,3]" % V)
     u = u.contiguous()
-    out = torch.empty_like(u)
+    out = L.scratch_like(u)
     off, nbr = topo.nbr
-    with L.device_guard(u.device):
-        L.check(L.lib().recmv_lap_smooth(L.ptr(off), L.ptr(nbr), V, nbr.shape[0], L.ptr(u), L.ptr(out),
-                                         L.stream_ptr(u.device)), "lap_smooth")
+    L.launch("lap_smooth", u.device, L.ptr(off), L.ptr(nbr), V, nbr.shape[0], L.ptr(u), L.ptr(out))
     return out
 
 

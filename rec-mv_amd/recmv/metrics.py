@@ -41,6 +41,7 @@ import math
 import torch
 
 from . import _lib as L
+from .mesh_args import check_mesh, check_points
 
 FACES_PER_CELL = 3.0           # the cell size aims at this many faces per occupied cell (h about 1.5 mean edges on a closed surface)
 MAX_CELLS = 1 << 22            # offsets table of 16 MiB
@@ -99,25 +100,13 @@ def choose_grid(lo, hi, n_faces, faces_per_cell=FACES_PER_CELL, max_cells=MAX_CE
         h *= 1.02 * (cells / max_cells) ** (1. / max(sum(d > 1 for d in dims), 1))
 
 
-def _check_mesh(verts, faces, allow_empty=False):
-    L.require_cuda(verts, "verts")
-    L.require_cuda(faces, "faces")
-    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError("verts must be float32 of shape [V,3]")
-    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("faces must be int64 of shape [F,3]")
-    if not allow_empty and (faces.shape[0] == 0 or verts.shape[0] == 0):
-        raise ValueError("the surface is empty")
-
-
 class MeshGrid:
     """A uniform grid over the mesh verts [V,3] f32 / faces [F,3] int64 (CUDA).  The bounding box and the number of
     (cell, face) entries are read back: two host synchronisations per build.  `dims` (and optionally `cell_size`) force a
     grid instead of choose_grid's (tests, tools)."""
 
     def __init__(self, verts, faces, dims=None, cell_size=None, faces_per_cell=FACES_PER_CELL):
-        _check_mesh(verts, faces)
-        self.verts, self.faces = verts.contiguous(), faces.contiguous()
+        self.verts, self.faces = check_mesh(verts, faces, allow_empty=False)
         dev = verts.device
         box = torch.stack([self.verts.amin(0), self.verts.amax(0)]).cpu()
         if not bool(torch.isfinite(box).all()):
@@ -131,7 +120,6 @@ class MeshGrid:
             h = float(torch.tensor(float(cell_size), dtype=torch.float32))
         else:
             h, dims = choose_grid(lo, hi, faces.shape[0], faces_per_cell)
-        lib = L.lib()
         self._mesh = mesh = (L.ptr(self.verts), self.verts.shape[0], L.ptr(self.faces), self.faces.shape[0])
         self.desc = desc = L.MeshGridDesc()                 # recmv_mesh_grid: points into offsets, entries and tris below
         self.origin = desc.origin
@@ -141,9 +129,7 @@ class MeshGrid:
             cells = dims[0] * dims[1] * dims[2]
             counts = L.scratch((cells,), torch.int32, dev)
             total = L.scratch((1,), torch.int64, dev)
-            with L.device_guard(dev):
-                L.check(lib.recmv_mesh_grid_count(*mesh, C.byref(desc), L.ptr(counts), L.ptr(total), L.stream_ptr(dev)),
-                        "mesh_grid_count")
+            L.launch("mesh_grid_count", dev, *mesh, C.byref(desc), L.ptr(counts), L.ptr(total))
             n = int(total.item())
             if n <= MAX_ENTRIES:
                 break
@@ -156,11 +142,8 @@ class MeshGrid:
         self.tris = L.scratch((self.faces.shape[0], 12), torch.float32, dev)
         desc.offsets, desc.entries, desc.tris = self.offsets.data_ptr(), self.entries.data_ptr(), self.tris.data_ptr()
         desc.n_entries = n
-        nbytes = int(lib.recmv_mesh_grid_workspace_bytes(cells))
-        ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
-        with L.device_guard(dev):
-            L.check(lib.recmv_mesh_grid_fill(*mesh, C.byref(desc), L.ptr(counts), L.ptr(ws), nbytes, L.stream_ptr(dev)),
-                    "mesh_grid_fill")
+        ws = L.workspace(nbytes := int(L.lib().recmv_mesh_grid_workspace_bytes(cells)), dev, "mesh_grid_workspace_bytes")
+        L.launch("mesh_grid_fill", dev, *mesh, C.byref(desc), L.ptr(counts), L.ptr(ws), nbytes)
         self.counts = counts
 
     def cell_of(self, p):
@@ -174,12 +157,9 @@ class MeshGrid:
         """iso_remesh.closest_point(p, verts, faces) through the grid: (face [P] int64, point [P,3] f32, squared distance
         [P] f32), ties to the lowest face id, the same bits.  `lanes` (1, 8 or 64 lanes per query) and `sort` (queries
         ordered by cell) choose the launch shape; they do not change the result."""
-        L.require_cuda(p, "p")
-        if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
-            raise ValueError("p must be float32 of shape [P,3]")
+        p = check_points(p, "p", shape="[P,3]")
         if p.device != self.verts.device:
             raise ValueError("p and the mesh must be on one device")
-        p = p.contiguous()
         P, dev = p.shape[0], p.device
         face = L.scratch((P,), torch.int64, dev)
         point = L.scratch((P, 3), torch.float32, dev)
@@ -188,10 +168,8 @@ class MeshGrid:
             return face, point, dist2
         lanes = QUERY_LANES if lanes is None else int(lanes)
         order = torch.sort(self.cell_of(p))[1].contiguous() if (QUERY_SORTED if sort is None else sort) else None
-        with L.device_guard(dev):
-            L.check(L.lib().recmv_closest_point_grid(L.ptr(p), P, L.ptr(order), self.faces.shape[0], C.byref(self.desc),
-                                                     lanes, L.ptr(face), L.ptr(point), L.ptr(dist2), L.stream_ptr(dev)),
-                    "closest_point_grid")
+        L.launch("closest_point_grid", dev, L.ptr(p), P, L.ptr(order), self.faces.shape[0], C.byref(self.desc), lanes,
+                 L.ptr(face), L.ptr(point), L.ptr(dist2))
         return face, point, dist2
 
     def segment_hits(self, p, q, count=False, lanes=None):
@@ -208,10 +186,8 @@ class MeshGrid:
         if lanes not in (1, 8, 64):
             raise ValueError("lanes must be 1, 8 or 64 (got %r)" % (lanes,))
         if S:
-            with L.device_guard(dev):
-                L.check(L.lib().recmv_segment_mesh_grid(L.ptr(p), L.ptr(q), S, *self._mesh, C.byref(self.desc), lanes,
-                                                        int(bool(count)), L.ptr(face), L.ptr(t), L.ptr(cnt),
-                                                        L.stream_ptr(dev)), "segment_mesh_grid")
+            L.launch("segment_mesh_grid", dev, L.ptr(p), L.ptr(q), S, *self._mesh, C.byref(self.desc), lanes, int(bool(count)),
+                     L.ptr(face), L.ptr(t), L.ptr(cnt))
         return _segment_result(p, q, face, t, cnt)
 
     def _crossings(self, verts, faces, self_mode, lanes):
@@ -235,10 +211,10 @@ class MeshGrid:
         """The faces of the mesh verts [V,3] f32 / faces [F,3] int64 (mesh A) that cross faces of the grid's mesh (B): (pairs
         [K,2] int64 of (face of A, face of B) sorted by (i, j), counts [F] int32 of pairs per face of A).  One read-back, for
         K.  `lanes` (1, 8 or 64 lanes per face of A) chooses the launch shape; it does not change the result."""
-        _check_mesh(verts, faces, allow_empty=True)
+        verts, faces = check_mesh(verts, faces)
         if verts.device != self.verts.device:
             raise ValueError("the two meshes must be on one device")
-        return self._crossings(verts.contiguous(), faces.contiguous(), False, lanes)
+        return self._crossings(verts, faces, False, lanes)
 
     def self_intersections(self, lanes=None):
         """The pairs i < j of the grid's own faces that cross and share no vertex index: (pairs [K,2] int64 sorted, counts
@@ -303,11 +279,10 @@ def mesh_intersections(a_v, a_f, b_v, b_f, method='auto', lanes=None):
     [K,2] int64 (face of A, face of B) sorted by (i, j), `n_pairs`, `faces_a` / `faces_b` (the distinct faces involved,
     sorted) and `ratio_a` / `ratio_b` (their number over the mesh's face count).  'grid': a MeshGrid over B; 'brute': every
     pair of faces; 'auto': by the number of face pairs.  The same integers either way."""
-    _check_mesh(a_v, a_f)
-    _check_mesh(b_v, b_f)
+    a_v, a_f = check_mesh(a_v, a_f, allow_empty=False)
+    b_v, b_f = check_mesh(b_v, b_f, allow_empty=False)
     if a_v.device != b_v.device:
         raise ValueError("the two meshes must be on one device")
-    a_v, a_f, b_v, b_f = (t.contiguous() for t in (a_v, a_f, b_v, b_f))
     if use_grid_for_pairs(method, a_f.shape[0], b_f.shape[0]):
         pairs, _ = MeshGrid(b_v, b_f).intersections(a_v, a_f, lanes=lanes)
     else:
@@ -321,8 +296,7 @@ def mesh_intersections(a_v, a_f, b_v, b_f, method='auto', lanes=None):
 def self_intersections(v, f, method='auto', lanes=None):
     """The crossings of a mesh with itself: pairs i < j of faces that cross and share no vertex index.  A dict with `pairs`
     [K,2] int64 sorted, `n_pairs`, `faces` (the distinct faces involved) and `ratio` (their number over the face count)."""
-    _check_mesh(v, f)
-    v, f = v.contiguous(), f.contiguous()
+    v, f = check_mesh(v, f, allow_empty=False)
     if use_grid_for_pairs(method, f.shape[0], f.shape[0]):
         pairs, _ = MeshGrid(v, f).self_intersections(lanes=lanes)
     else:
@@ -332,15 +306,12 @@ def self_intersections(v, f, method='auto', lanes=None):
 
 
 def _check_segments(p, q, device=None):
-    for x, name in ((p, "p"), (q, "q")):
-        L.require_cuda(x, name)
-        if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 3:
-            raise ValueError("%s must be float32 of shape [S,3]" % name)
+    p, q = check_points(p, "p", shape="[S,3]"), check_points(q, "q", shape="[S,3]")
     if p.shape != q.shape:
         raise ValueError("p and q must have the same shape (got %s and %s)" % (tuple(p.shape), tuple(q.shape)))
     if p.device != q.device or (device is not None and p.device != device):
         raise ValueError("the segments and the mesh must be on one device")
-    return p.contiguous(), q.contiguous()
+    return p, q
 
 
 def _segment_result(p, q, face, t, count):
@@ -358,20 +329,17 @@ def segment_hits(p, q, verts, faces, count=False, method='auto', lanes=None):
     """MeshGrid.segment_hits for the mesh verts [V,3] f32 / faces [F,3] int64 (CUDA tensors on one device).  'grid': through a
     MeshGrid; 'brute': every face (it always counts; `count` only decides whether the counts are returned); 'auto': by the
     number of segment-face tests.  The same bits either way."""
-    _check_mesh(verts, faces)
+    verts, faces = check_mesh(verts, faces, allow_empty=False)
     p, q = _check_segments(p, q, verts.device)
     if use_grid_for_segments(method, p.shape[0], faces.shape[0]):
         return MeshGrid(verts, faces).segment_hits(p, q, count=count, lanes=lanes)
-    verts, faces = verts.contiguous(), faces.contiguous()
     S, dev = p.shape[0], p.device
     face = L.scratch((S,), torch.int64, dev)
     t = L.scratch((S,), torch.float32, dev)
     cnt = L.scratch((S,), torch.int32, dev)
     if S:
-        with L.device_guard(dev):
-            L.check(L.lib().recmv_segment_mesh_brute(L.ptr(p), L.ptr(q), S, L.ptr(verts), verts.shape[0], L.ptr(faces),
-                                                     faces.shape[0], L.ptr(face), L.ptr(t), L.ptr(cnt), L.stream_ptr(dev)),
-                    "segment_mesh_brute")
+        L.launch("segment_mesh_brute", dev, L.ptr(p), L.ptr(q), S, L.ptr(verts), verts.shape[0], L.ptr(faces), faces.shape[0],
+                 L.ptr(face), L.ptr(t), L.ptr(cnt))
     return _segment_result(p, q, face, t, cnt if count else None)
 
 
@@ -391,10 +359,8 @@ def points_inside(points, verts, faces, method='auto', rule='parity'):
     rule='winding' takes recmv.winding.points_inside instead (the exact generalized winding number, |w| > 1/2): sound for a mesh
     with holes, for overlapping closed pieces (their union) and for either orientation; `method` then only is checked."""
     _check_rule(rule)
-    _check_mesh(verts, faces)
-    L.require_cuda(points, "points")
-    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError("points must be float32 of shape [P,3]")
+    check_mesh(verts, faces, allow_empty=False)
+    points = check_points(points, "points", shape="[P,3]")
     if points.device != verts.device:
         raise ValueError("the points and the mesh must be on one device")
     use_grid_for_segments(method, 0, 0)
@@ -404,7 +370,6 @@ def points_inside(points, verts, faces, method='auto', rule='parity'):
     if rule == 'winding':
         from . import winding
         return winding.points_inside(points, verts, faces)
-    points = points.contiguous()
     lo, hi = verts.amin(0), verts.amax(0)
     reach = 1.5 * (hi - lo).norm() + (points - 0.5 * (lo + hi)).norm(dim=1, keepdim=True)                    # [P,1]
     dirs = torch.tensor(INSIDE_DIRECTIONS, dtype=torch.float32, device=points.device)                        # [3,3]
@@ -485,12 +450,11 @@ def surface_distance(pred_v, pred_f, gt_v, gt_f, samples=100000, seed=0, thresho
     (CUDA tensors on one device): a dict of python floats.  `samples` surface samples per direction from a generator seeded
     with `seed` (the prediction's first).  `return_samples`: also {'pred': (points, source face, nearest face of the ground
     truth), 'gt': (…)}."""
-    _check_mesh(pred_v, pred_f)
-    _check_mesh(gt_v, gt_f)
+    pred_v, pred_f = check_mesh(pred_v, pred_f, allow_empty=False)
+    gt_v, gt_f = check_mesh(gt_v, gt_f, allow_empty=False)
     use_grid(method, 0, 0)
     if samples < 1:
         raise ValueError("surface_distance: at least one sample")
-    pred_v, pred_f, gt_v, gt_f = (t.contiguous() for t in (pred_v, pred_f, gt_v, gt_f))
     gen = torch.Generator(device=pred_v.device).manual_seed(int(seed))
     thresholds = tuple(float(t) for t in thresholds)
     pp, pf = sample_surface(pred_v, pred_f, samples, gen)

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib as L
 from .connectivity import EdgeTable, edges_packed, incident_edges_csr, neighbours_csr  # noqa: F401  (callers say K.edges_packed)
+from .mesh_args import check_points
 
 
 class TriMesh:
@@ -78,31 +79,19 @@ def verts_normals(verts, faces):
 
 
 # ------------------------------------------------------------------------------------------------- kernels
-def _check_points(t, name):
-    L.require_cuda(t, name)
-    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError("%s must be float32 [n,3]" % name)
-
-
 def knn1(p, q):
     """Exact 1-NN of every row of p [N,3] among q [M,3] (float32 CUDA): (idx [N] int64, squared distance [N] f32);
     ties go to the lowest index of q."""
-    _check_points(p, "p")
-    _check_points(q, "q")
+    p, q = check_points(p, "p"), check_points(q, "q")
     if q.shape[0] == 0:
         raise ValueError("knn1: the target cloud is empty")
-    p, q = p.contiguous(), q.contiguous()
-    N = p.shape[0]
-    idx = torch.empty(N, dtype=torch.int64, device=p.device)
-    dist = torch.empty(N, dtype=torch.float32, device=p.device)
+    N, dev = p.shape[0], p.device
+    idx = L.scratch((N,), torch.int64, dev)
+    dist = L.scratch((N,), torch.float32, dev)
     if N == 0:
         return idx, dist
-    lib = L.lib()
-    nbytes = int(lib.recmv_knn1_workspace_bytes(N))
-    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=p.device)
-    with L.device_guard(p.device):
-        L.check(lib.recmv_knn1(L.ptr(p), N, L.ptr(q), q.shape[0], L.ptr(idx), L.ptr(dist), L.ptr(ws), nbytes,
-                               L.stream_ptr(p.device)), "knn1")
+    ws = L.workspace(nbytes := int(L.lib().recmv_knn1_workspace_bytes(N)), dev, "knn1_workspace_bytes")
+    L.launch("knn1", dev, L.ptr(p), N, L.ptr(q), q.shape[0], L.ptr(idx), L.ptr(dist), L.ptr(ws), nbytes)
     return idx, dist
 
 
@@ -142,13 +131,13 @@ class NricpEnergy:
         self.topo = topo
         N = topo.V
         self.N = N
-        lib = L.lib()
-        self.ws_bytes = int(lib.recmv_nricp_energy_workspace_bytes(N))
-        self.ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=device)
-        self.scalars = torch.empty(4, dtype=torch.float32, device=device)
-        self.mask = torch.empty(N, dtype=torch.uint8, device=device)
-        self.dA = torch.empty(N, 3, 3, dtype=torch.float32, device=device)
-        self.db = torch.empty(N, 3, dtype=torch.float32, device=device)
+        self.ws = L.workspace(nbytes := int(L.lib().recmv_nricp_energy_workspace_bytes(N)), device, "nricp_energy_workspace_bytes",
+                              floor=16)
+        self.ws_bytes = nbytes
+        self.scalars = L.scratch((4,), torch.float32, device)
+        self.mask = L.scratch((N,), torch.uint8, device)
+        self.dA = L.scratch((N, 3, 3), torch.float32, device)
+        self.db = L.scratch((N, 3), torch.float32, device)
         self.interior = topo.interior.to(torch.uint8).contiguous()
 
     def __call__(self, A, b, x, c, nc, nx, gamma, stiffness_weight, laplacian_weight, threshold):
@@ -160,10 +149,8 @@ class NricpEnergy:
                 raise ValueError("nricp_energy: %s must be float32 with %d rows" % (name, N))
         topo = self.topo
         E = topo.edges.shape[0]
-        with L.device_guard(A.device):
-            L.check(L.lib().recmv_nricp_energy(
-                L.ptr(A), L.ptr(b), L.ptr(x), L.ptr(c), L.ptr(nc), L.ptr(nx), L.ptr(self.interior), L.ptr(topo.edges), E,
-                L.ptr(topo.inc[0]), L.ptr(topo.inc[1]), L.ptr(topo.nbr[0]), L.ptr(topo.nbr[1]), N, float(gamma),
-                float(stiffness_weight), float(laplacian_weight), float(threshold), L.ptr(self.scalars), L.ptr(self.mask),
-                L.ptr(self.dA), L.ptr(self.db), L.ptr(self.ws), self.ws_bytes, L.stream_ptr(A.device)), "nricp_energy")
+        L.launch("nricp_energy", A.device, L.ptr(A), L.ptr(b), L.ptr(x), L.ptr(c), L.ptr(nc), L.ptr(nx), L.ptr(self.interior),
+                 L.ptr(topo.edges), E, L.ptr(topo.inc[0]), L.ptr(topo.inc[1]), L.ptr(topo.nbr[0]), L.ptr(topo.nbr[1]), N,
+                 float(gamma), float(stiffness_weight), float(laplacian_weight), float(threshold), L.ptr(self.scalars),
+                 L.ptr(self.mask), L.ptr(self.dA), L.ptr(self.db), L.ptr(self.ws), self.ws_bytes)
         return self.scalars, self.mask

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib as L
 from . import connectivity
+from .mesh_args import check_csr, check_mesh
 
 ROUTES = ('auto', 'launch', 'lds')
 WEIGHTS = ('cotangent', 'uniform')
@@ -34,21 +35,6 @@ def lds_max_vertices():
 def auto_max_vertices():
     """recmv_param_auto_max_vertices(): route='auto' takes the lds route up to this many vertices."""
     return int(L.lib().recmv_param_auto_max_vertices())
-
-
-def _check_mesh(verts, faces, cuda=True):
-    """Shapes and dtypes first (ValueError), then the device (RuntimeError): the argument errors do not need a GPU."""
-    if not (isinstance(verts, torch.Tensor) and isinstance(faces, torch.Tensor)):
-        raise ValueError("verts and faces must be tensors")
-    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError("verts must be float32 of shape [V,3]")
-    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("faces must be int64 of shape [F,3]")
-    if verts.device != faces.device:
-        raise ValueError("verts and faces must be on one device")
-    if cuda:
-        L.require_cuda(verts, "verts")
-        L.require_cuda(faces, "faces")
 
 
 def _check_route(route):
@@ -85,7 +71,7 @@ def cut_to_disk(verts, faces):
     class of the lowest face keeps the vertex, the others get copies V, V + 1, ... (by vertex, then class): verts'[k] ==
     verts[origin[k]].  seams: [{'vertices': original ids, 'length': float}].  ValueError names why a mesh is refused: closed,
     several pieces, genus > 0, non-manifold."""
-    _check_mesh(verts, faces, cuda=False)
+    check_mesh(verts, faces, cuda=False)
     V, dev = verts.shape[0], verts.device
     f = faces.detach().cpu()
     if f.shape[0] == 0:
@@ -226,19 +212,13 @@ class _Mesh:
     [0, V) filed under a row of their own), and on demand the frames and the weights."""
 
     def __init__(self, verts, faces):
-        _check_mesh(verts, faces)
-        self.verts, self.faces = verts.contiguous(), faces.contiguous()
+        self.verts, self.faces = check_mesh(verts, faces)
         self.V, self.F, self.device = verts.shape[0], faces.shape[0], verts.device
-        V, dev = self.V, self.device
+        V = self.V
         inside = ((self.faces >= 0) & (self.faces < V)).all(1)
         table = connectivity.EdgeTable(self.faces[inside], V)
         self.nbr = connectivity.neighbours_csr(table.edges, V)
-        if self.F:
-            filed = torch.where((self.faces >= 0) & (self.faces < V), self.faces, V)
-            off, slots = connectivity.vertex_slots_csr(filed, V + 1)
-            self.slots = (off[:V + 1].contiguous(), slots.contiguous())
-        else:
-            self.slots = (torch.zeros(V + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev))
+        self.slots = connectivity.filed_slots_csr(self.faces, V)
         self._frames = None
 
     def frames(self):
@@ -256,13 +236,10 @@ class _Mesh:
 @torch.no_grad()
 def face_frames(verts, faces):
     """recmv_param_face_frames: (frames [F,4] = (x1, x2, y2, area), cots [F,3]) float64; zeros for unusable faces."""
-    _check_mesh(verts, faces)
-    verts, faces = verts.contiguous(), faces.contiguous()
+    verts, faces = check_mesh(verts, faces)
     V, F, dev = verts.shape[0], faces.shape[0], verts.device
     frames, cots = L.scratch((F, 4), torch.float64, dev), L.scratch((F, 3), torch.float64, dev)
-    with L.device_guard(dev):
-        L.check(L.lib().recmv_param_face_frames(L.ptr(verts), V, L.ptr(faces), F, L.ptr(frames), L.ptr(cots), L.stream_ptr(dev)),
-                "param_face_frames")
+    L.launch("param_face_frames", dev, L.ptr(verts), V, L.ptr(faces), F, L.ptr(frames), L.ptr(cots))
     return frames, cots
 
 
@@ -274,10 +251,9 @@ def solve(nbr_csr, weights, fixed, rhs, u, route='auto', tol=1e-12, max_iter=Non
     between two read-backs on the launch route; it changes no bit."""
     _check_route(route)
     tol, max_iter = _check_solver(tol, max_iter)
-    off, nbr = nbr_csr
-    if off.dtype != torch.int32 or nbr.dtype != torch.int32 or off.dim() != 1 or nbr.dim() != 1 or off.numel() < 1:
-        raise ValueError("nbr_csr must be (offsets [V+1], neighbours) of int32")
-    V, nnz = off.numel() - 1, nbr.numel()
+    V = max(nbr_csr[0].numel() - 1, 0)                     # (an empty offsets table fails the check: it wants V + 1 entries)
+    off, nbr = check_csr(nbr_csr, V, torch.int32, "nbr_csr")
+    nnz = nbr.numel()
     if weights.dtype != torch.float64 or weights.shape != (nnz,):
         raise ValueError("weights must be float64 of shape [%d]" % nnz)
     if fixed.dim() != 1 or fixed.shape[0] != V or fixed.dtype not in (torch.uint8, torch.bool):
@@ -294,7 +270,7 @@ def solve(nbr_csr, weights, fixed, rhs, u, route='auto', tol=1e-12, max_iter=Non
         route = 'lds' if V <= auto_max_vertices() else 'launch'
     max_iter = 10 * V + 100 if max_iter is None else max_iter
     dev = u.device
-    off, nbr, weights, rhs = off.contiguous(), nbr.contiguous(), weights.contiguous(), rhs.contiguous()
+    weights, rhs = weights.contiguous(), rhs.contiguous()
     fixed = fixed.to(torch.uint8).contiguous()
     out = u.clone(memory_format=torch.contiguous_format)
     lib = L.lib()
@@ -307,10 +283,8 @@ def solve(nbr_csr, weights, fixed, rhs, u, route='auto', tol=1e-12, max_iter=Non
             L.check(lib.recmv_param_solve_lds(*head, L.C.byref(iters), res, L.C.byref(zero), L.ptr(report), L.stream_ptr(dev)),
                     "param_solve_lds")
         else:
-            nbytes = int(lib.recmv_param_solve_workspace_bytes(V))
-            if nbytes < 0:
-                L.check(-1, "param_solve_workspace_bytes")
-            ws = L.scratch((nbytes // 8 + 32,), torch.float64, dev)
+            ws = L.workspace(nbytes := int(lib.recmv_param_solve_workspace_bytes(V)), dev, "param_solve_workspace_bytes",
+                             dtype=torch.float64, floor=nbytes + 256)      # 256 bytes more: room for the alignment skip
             skip = (-ws.data_ptr() % 256) // 8
             L.check(lib.recmv_param_solve(*head, 0 if batch is None else int(batch), L.C.byref(iters), res, L.C.byref(zero),
                                           L.ptr(ws[skip:]), nbytes, L.stream_ptr(dev)), "param_solve")
@@ -330,10 +304,8 @@ def arap_rhs(faces, frames, cots, uv, slots_csr):
     soff, slots = slots_csr
     rot, rhs = L.scratch((F, 2), torch.float64, dev), L.scratch((V, 2), torch.float64, dev)
     partials, energy = L.scratch(((F + SLOT - 1) // SLOT,), torch.float64, dev), L.scratch((1,), torch.float64, dev)
-    with L.device_guard(dev):
-        L.check(L.lib().recmv_param_arap_rhs(L.ptr(faces.contiguous()), F, L.ptr(frames.contiguous()), L.ptr(cots.contiguous()),
-                                             L.ptr(uv.contiguous()), V, L.ptr(soff), L.ptr(slots), L.ptr(rot), L.ptr(rhs),
-                                             L.ptr(partials), L.ptr(energy), L.stream_ptr(dev)), "param_arap_rhs")
+    L.launch("param_arap_rhs", dev, L.ptr(faces.contiguous()), F, L.ptr(frames.contiguous()), L.ptr(cots.contiguous()),
+             L.ptr(uv.contiguous()), V, L.ptr(soff), L.ptr(slots), L.ptr(rot), L.ptr(rhs), L.ptr(partials), L.ptr(energy))
     return rot, rhs, partials, energy
 
 
@@ -370,7 +342,7 @@ def harmonic(verts, faces, weights='cotangent', route='auto', tol=1e-12, max_ite
         raise ValueError("weights must be one of %r (got %r)" % (WEIGHTS, weights))
     _check_route(route)
     tol, max_iter = _check_solver(tol, max_iter)
-    _check_mesh(verts, faces, cuda=False)
+    check_mesh(verts, faces, cuda=False)
     if route == 'lds' and verts.shape[0] > lds_max_vertices():
         raise ValueError("route='lds' takes at most %d vertices (got %d)" % (lds_max_vertices(), verts.shape[0]))
     uv, info = _harmonic(_Mesh(verts, faces), weights, route, tol, max_iter)
@@ -405,7 +377,7 @@ def arap(verts, faces, uv0=None, iterations=20, route='auto', tol=1e-12, return_
     tol, _ = _check_solver(tol, None)
     if int(iterations) < 0:
         raise ValueError("iterations must not be negative (got %r)" % (iterations,))
-    _check_mesh(verts, faces, cuda=False)
+    check_mesh(verts, faces, cuda=False)
     if uv0 is not None:
         _check_uv(uv0, verts.shape[0], "uv0")
     if route == 'lds' and verts.shape[0] > lds_max_vertices():
@@ -427,9 +399,9 @@ def distortion(verts, faces, uv):
     faces with det <= 0, 'conformal' and 'area' the area-weighted means of s1 / s2 and s1 s2, 'isometric' and 'isometric_max' the
     area-weighted mean and the maximum of max(s1, 1 / s2), 'area_3d' and 'area_2d' the total areas (None where no face is
     usable)."""
-    _check_mesh(verts, faces, cuda=False)
+    check_mesh(verts, faces, cuda=False)
     _check_uv(uv, verts.shape[0])
-    _check_mesh(verts, faces)
+    check_mesh(verts, faces)
     L.require_cuda(uv, "uv")
     frames, _ = face_frames(verts, faces)
     return _distortion(faces.contiguous(), frames, uv.contiguous())
@@ -438,9 +410,7 @@ def distortion(verts, faces, uv):
 def _distortion(faces, frames, uv):
     F, V, dev = faces.shape[0], uv.shape[0], uv.device
     out = L.scratch((F, 3), torch.float64, dev)
-    with L.device_guard(dev):
-        L.check(L.lib().recmv_param_distortion(L.ptr(faces), F, L.ptr(frames), L.ptr(uv), V, L.ptr(out), L.stream_ptr(dev)),
-                "param_distortion")
+    L.launch("param_distortion", dev, L.ptr(faces), F, L.ptr(frames), L.ptr(uv), V, L.ptr(out))
     s1, s2, det = out[:, 0], out[:, 1], out[:, 2]
     usable = ~torch.isnan(s1)
     a = frames[:, 3][usable]
@@ -475,7 +445,7 @@ def flatten(verts, faces, method='arap', normalise=True, weights='cotangent', it
     tol, _ = _check_solver(tol, None)
     if int(iterations) < 0:
         raise ValueError("iterations must not be negative (got %r)" % (iterations,))
-    _check_mesh(verts, faces)
+    check_mesh(verts, faces)
     cv, cf, origin, seams = cut_to_disk(verts, faces)
     if route == 'lds' and cv.shape[0] > lds_max_vertices():
         raise ValueError("route='lds' takes at most %d vertices (the cut mesh has %d)" % (lds_max_vertices(), cv.shape[0]))

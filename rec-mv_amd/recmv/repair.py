@@ -57,7 +57,7 @@ import torch
 
 from . import _lib as L
 from .connectivity import EdgeTable, compact
-from .metrics import _check_mesh
+from .mesh_args import check_mesh, check_points, info_json  # noqa: F401  (info_json: the JSON-able part of an info dict)
 from .topology import face_stats, graph_components, valid_faces
 
 MAX_AXIS_CELLS = 1 << 20                                   # csrc/point_grid.hip checks both
@@ -84,14 +84,6 @@ def grid_layout(lo, hi, eps, n):
         cell *= 2.
 
 
-def _check_verts(verts):
-    if not isinstance(verts, torch.Tensor) or verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError("verts must be float32 of shape [V,3]")
-    if verts.shape[0] >= 1 << 31:
-        raise ValueError("at most 2^31 - 1 vertices")
-    L.require_cuda(verts, "verts")
-
-
 def _check_eps(eps, name="eps"):
     eps = float(eps)
     if not (0. <= eps < math.inf):
@@ -108,10 +100,12 @@ def points_within(verts, eps, max_pairs=None, return_info=False):
     eps = _check_eps(eps)
     if max_pairs is not None and int(max_pairs) < 0:
         raise ValueError("max_pairs must not be negative")
-    _check_verts(verts)
+    verts = check_points(verts, "verts", cuda=False, shape="[V,3]")
+    if verts.shape[0] >= 1 << 31:
+        raise ValueError("at most 2^31 - 1 vertices")
+    L.require_cuda(verts, "verts")
     V, dev = verts.shape[0], verts.device
     max_pairs = 64 * V if max_pairs is None else int(max_pairs)
-    verts = verts.contiguous()
     empty = torch.zeros((0, 2), dtype=torch.int64, device=dev)
     finite = torch.isfinite(verts).all(1)
     n_finite = int(finite.sum().item()) if V else 0
@@ -123,10 +117,8 @@ def points_within(verts, eps, max_pairs=None, return_info=False):
     info['cell'], info['dims'] = cell, dims
     grid = (origin[0], origin[1], origin[2], cell, dims[0], dims[1], dims[2])
     cells = dims[0] * dims[1] * dims[2]
-    lib, stream = L.lib(), L.stream_ptr(dev)
     cell_of = L.scratch((V,), torch.int32, dev)
-    with L.device_guard(dev):
-        L.check(lib.recmv_points_within_cells(L.ptr(verts), V, *grid, L.ptr(cell_of), stream), "points_within_cells")
+    L.launch("points_within_cells", dev, L.ptr(verts), V, *grid, L.ptr(cell_of))
     ids = (cell_of >= 0).nonzero().squeeze(1)
     key, perm = torch.sort(cell_of[ids].long(), stable=True)                      # by cell, by id inside a cell
     ids = ids[perm].contiguous()
@@ -135,9 +127,7 @@ def points_within(verts, eps, max_pairs=None, return_info=False):
     cell_start = torch.zeros(cells + 1, dtype=torch.int32, device=dev)
     cell_start[1:] = torch.cumsum(torch.bincount(key, minlength=cells), 0)
     counts = L.scratch((V,), torch.int64, dev)
-    with L.device_guard(dev):
-        L.check(lib.recmv_points_within_count(L.ptr(pts), L.ptr(ids), n, V, eps, *grid, L.ptr(cell_start), L.ptr(counts), stream),
-                "points_within_count")
+    L.launch("points_within_count", dev, L.ptr(pts), L.ptr(ids), n, V, eps, *grid, L.ptr(cell_start), L.ptr(counts))
     ends = torch.cumsum(counts, 0)
     total = int(ends[-1].item())                                                   # the read-back
     if total > max_pairs:
@@ -148,20 +138,9 @@ def points_within(verts, eps, max_pairs=None, return_info=False):
         return (empty, info) if return_info else empty
     offsets = (ends - counts).contiguous()
     pairs = L.scratch((total, 2), torch.int64, dev)
-    with L.device_guard(dev):
-        L.check(lib.recmv_points_within_fill(L.ptr(pts), L.ptr(ids), n, V, eps, *grid, L.ptr(cell_start), L.ptr(offsets),
-                                             L.ptr(pairs), total, stream), "points_within_fill")
+    L.launch("points_within_fill", dev, L.ptr(pts), L.ptr(ids), n, V, eps, *grid, L.ptr(cell_start), L.ptr(offsets), L.ptr(pairs),
+             total)
     return (pairs, info) if return_info else pairs
-
-
-def _check(verts, faces):
-    _check_verts(verts)
-    _check_mesh(verts, faces, allow_empty=True)
-    if verts.device != faces.device:
-        raise ValueError("verts and faces must be on one device")
-    if verts.shape[0] >= 1 << 31 or faces.shape[0] >= 1 << 31:
-        raise ValueError("at most 2^31 - 1 vertices and faces")
-    return verts.contiguous(), faces.contiguous()
 
 
 @torch.no_grad()
@@ -170,7 +149,7 @@ def weld(verts, faces, eps=0., max_pairs=None):
     definition.  info: pairs, merged_vertices (vertices that are no longer their own representative), clusters (representatives
     of more than one vertex), vertex_map [V] int64 (old -> representative), nonfinite_vertices, cluster_radius_max."""
     eps = _check_eps(eps)
-    verts, faces = _check(verts, faces)
+    verts, faces = check_mesh(verts, faces, cap31=True)
     V, dev = verts.shape[0], verts.device
     pairs, pinfo = points_within(verts, eps, max_pairs=max_pairs, return_info=True)
     label = graph_components(V, pairs)
@@ -196,7 +175,7 @@ def weld(verts, faces, eps=0., max_pairs=None):
 def drop_degenerate(verts, faces):
     """The mesh without its invalid, zero-area, non-finite and duplicate faces — (verts, faces', info); the module docstring
     has the definition.  info: invalid_faces, zero_area_faces, nonfinite_faces, duplicate_faces, kept_faces [F'] int64."""
-    verts, faces = _check(verts, faces)
+    verts, faces = check_mesh(verts, faces, cap31=True)
     V, F, dev = verts.shape[0], faces.shape[0], faces.device
     valid = valid_faces(faces, V)
     area = face_stats(verts, faces)[0]
@@ -237,7 +216,7 @@ def split_nonmanifold(verts, faces):
     the module docstring has the definition and the argument that one pass suffices.  Raises ValueError on invalid faces.
     info: split_vertices (old vertices that became several), added_vertices, nonmanifold_edges_before, origin [V'] int64 (the
     old id of every vertex)."""
-    verts, faces = _check(verts, faces)
+    verts, faces = check_mesh(verts, faces, cap31=True)
     V, F, dev = verts.shape[0], faces.shape[0], faces.device
     _require_valid(faces, V, "split_nonmanifold")
     if 3 * F >= 1 << 31:
@@ -272,7 +251,7 @@ def orient(verts, faces):
     """Every orientable piece consistently oriented — (verts, faces', info); the module docstring has the definition.
     info: flipped_faces, conflicts_before (edges of exactly two faces that both traverse in one direction),
     non_orientable_pieces, flipped [F] bool."""
-    verts, faces = _check(verts, faces)
+    verts, faces = check_mesh(verts, faces, cap31=True)
     V, F, dev = verts.shape[0], faces.shape[0], faces.device
     if F >= 1 << 30:
         raise ValueError("orient: at most 2^30 - 1 faces")
@@ -313,7 +292,7 @@ def repair(verts, faces, weld_eps=None, degenerate=True, split=True, orientation
     on invalid faces, so `degenerate=False` is for meshes that have none."""
     if weld_eps is not None:
         weld_eps = _check_eps(weld_eps, "weld_eps")
-    v, f = _check(verts, faces)
+    v, f = check_mesh(verts, faces, cap31=True)
     V, F, dev = v.shape[0], f.shape[0], v.device
     info = {}
     vmap = torch.arange(V, dtype=torch.int64, device=dev)
@@ -335,16 +314,3 @@ def repair(verts, faces, weld_eps=None, degenerate=True, split=True, orientation
     info['kept_faces'] = kept
     info['origin'] = origin[cmap >= 0]
     return v.contiguous(), f.contiguous(), info
-
-
-def info_json(info):
-    """The JSON-able part of an info dict of this module: the numbers, with the tensors left out (nested dicts likewise)."""
-    out = {}
-    for k, x in info.items():
-        if isinstance(x, dict):
-            out[k] = info_json(x)
-        elif isinstance(x, (bool, int, float, str)) or x is None:
-            out[k] = x
-        elif isinstance(x, (tuple, list)) and all(isinstance(y, (int, float)) for y in x):
-            out[k] = list(x)
-    return out

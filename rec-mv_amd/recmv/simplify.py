@@ -33,7 +33,7 @@ import torch
 from . import _lib as L
 from .connectivity import EdgeTable, boundary_edges_csr, compact, vertex_slots_csr
 from .iso_remesh import _Topo, _boundary_loop_length, _flip_ok, _independent, _link_ok, _merge, _padded
-from .smooth import _check_mesh
+from .mesh_args import check_mesh
 
 BOUNDARY_WEIGHT = 10.       # a boundary edge's plane counts like 10 |e|^2 of face area
 REACH = 2.                  # the solved optimum must lie within this many edge lengths of the edge's midpoint
@@ -48,8 +48,7 @@ def vertex_quadrics(verts, faces, table=None, boundary_weight=BOUNDARY_WEIGHT, r
     """recmv_vertex_quadrics: Q [V,11] float64 (xx xy xz xw yy yz yw zz zw ww, weight) of verts [V,3] f32 / faces [F,3] int64
     (CUDA); `table`: the mesh's EdgeTable, built when absent (the faces must then be valid).  `return_counts`: also the number
     of invalid faces."""
-    _check_mesh(verts, faces, True)
-    verts, faces = verts.contiguous(), faces.contiguous()
+    verts, faces = check_mesh(verts, faces)
     V, F, dev = verts.shape[0], faces.shape[0], verts.device
     Q = L.scratch((V, 11), torch.float64, dev)
     counts = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -58,11 +57,8 @@ def vertex_quadrics(verts, faces, table=None, boundary_weight=BOUNDARY_WEIGHT, r
         off, slots = vertex_slots_csr(faces, V)
         vf = (slots // 3).contiguous()
         border, boff, brows = boundary_edges_csr(table)
-        with L.device_guard(dev):
-            L.check(L.lib().recmv_vertex_quadrics(L.ptr(verts), V, L.ptr(faces), F, L.ptr(off), L.ptr(vf), vf.numel(),
-                                                  L.ptr(border), border.shape[0], L.ptr(boff), L.ptr(brows), brows.numel(),
-                                                  float(boundary_weight), L.ptr(Q), L.ptr(counts), L.stream_ptr(dev)),
-                    "vertex_quadrics")
+        L.launch("vertex_quadrics", dev, L.ptr(verts), V, L.ptr(faces), F, L.ptr(off), L.ptr(vf), vf.numel(), L.ptr(border),
+                 border.shape[0], L.ptr(boff), L.ptr(brows), brows.numel(), float(boundary_weight), L.ptr(Q), L.ptr(counts))
     return (Q, int(counts.item())) if return_counts else Q
 
 
@@ -145,10 +141,8 @@ def edge_collapse_cost(Q, verts, edges, code, reach=REACH):
     cost, weight = L.scratch((E,), torch.float64, dev), L.scratch((E,), torch.float64, dev)
     if E:
         counts = torch.zeros(1, dtype=torch.int32, device=dev)
-        with L.device_guard(dev):
-            L.check(L.lib().recmv_edge_collapse_cost(L.ptr(Q), L.ptr(verts), verts.shape[0], L.ptr(edges), E, L.ptr(code),
-                                                     float(reach), L.ptr(pos), L.ptr(cost), L.ptr(weight), L.ptr(counts),
-                                                     L.stream_ptr(dev)), "edge_collapse_cost")
+        L.launch("edge_collapse_cost", dev, L.ptr(Q), L.ptr(verts), verts.shape[0], L.ptr(edges), E, L.ptr(code), float(reach),
+                 L.ptr(pos), L.ptr(cost), L.ptr(weight), L.ptr(counts))
     return pos, cost, weight
 
 
@@ -195,11 +189,11 @@ def edge_collapse_cost_torch(Q, verts, edges, code, reach=REACH):
 def collapse_flip_check(verts, faces, edges, pos, vf=None):
     """recmv_collapse_flip_check: ok [E] bool of the collapses of edges [E,2] int64 to pos [E,3] f32 on verts [V,3] f32 /
     faces [F,3] int64 (CUDA); vf: (offsets, faces) int64 of the vertex -> face table, built when absent."""
-    _check_mesh(verts, faces, True)
+    verts, faces = check_mesh(verts, faces)
     L.require_cuda(edges, "edges")
     L.require_cuda(pos, "pos")
     _check_edges(None, verts, edges, pos=pos)
-    verts, faces, edges, pos = verts.contiguous(), faces.contiguous(), edges.contiguous(), pos.contiguous()
+    edges, pos = edges.contiguous(), pos.contiguous()
     V, F, E, dev = verts.shape[0], faces.shape[0], edges.shape[0], verts.device
     ok = L.scratch((E,), torch.uint8, dev)
     if E:
@@ -207,10 +201,8 @@ def collapse_flip_check(verts, faces, edges, pos, vf=None):
             off, slots = vertex_slots_csr(faces, V)
             vf = (off, slots // 3)
         off, idx = vf[0].contiguous(), vf[1].contiguous()
-        with L.device_guard(dev):
-            L.check(L.lib().recmv_collapse_flip_check(L.ptr(verts), V, L.ptr(faces), F, L.ptr(off), L.ptr(idx), idx.numel(),
-                                                      L.ptr(edges), E, L.ptr(pos), L.ptr(ok), L.stream_ptr(dev)),
-                    "collapse_flip_check")
+        L.launch("collapse_flip_check", dev, L.ptr(verts), V, L.ptr(faces), F, L.ptr(off), L.ptr(idx), idx.numel(), L.ptr(edges), E,
+                 L.ptr(pos), L.ptr(ok))
     return ok.bool()
 
 
@@ -239,10 +231,8 @@ def simplify(verts, faces, target_faces=None, ratio=None, max_error=None, bounda
         raise ValueError("simplify: max_error must be finite and not negative")
     if not (float(boundary_weight) >= 0. and math.isfinite(float(boundary_weight))):
         raise ValueError("simplify: boundary_weight must be finite and not negative")
-    _check_mesh(verts, faces, False)
-    if use_kernels:
-        L.require_cuda(verts, "verts")
-    verts, faces = verts.float().contiguous(), faces.contiguous()
+    verts, faces = check_mesh(verts, faces, cuda=use_kernels, float_verts=True)
+    verts = verts.float()
     V, dev = verts.shape[0], faces.device
     if faces.shape[0]:
         lo, hi = (int(x) for x in torch.aminmax(faces))

@@ -31,32 +31,13 @@ import torch
 
 from . import _lib as L
 from .connectivity import EdgeTable, boundary_neighbours, face_neighbours_csr, neighbours_csr, vertex_slots_csr
+from .mesh_args import check_csr, check_mesh, check_points
 from .topology import valid_faces
 
 PASS_BAND = 0.1             # Taubin's k_PB
 METHODS = ('taubin', 'laplacian', 'bilateral')
 WEIGHTS = ('uniform', 'cotangent')
 BOUNDARIES = ('fixed', 'curve', 'free')
-
-
-def _check_mesh(verts, faces, cuda):
-    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("faces must be int64 of shape [F,3]")
-    if verts.dim() != 2 or verts.shape[1] != 3 or not verts.dtype.is_floating_point:
-        raise ValueError("verts must be floating point of shape [V,3]")
-    if verts.device != faces.device:
-        raise ValueError("verts and faces must be on one device")
-    if cuda:
-        L.require_cuda(verts, "verts")
-        if verts.dtype != torch.float32:
-            raise ValueError("verts must be float32")
-
-
-def _check_csr(csr, rows, dtype, name):
-    off, idx = csr
-    if off.dtype != dtype or idx.dtype != dtype or off.dim() != 1 or idx.dim() != 1 or off.numel() != rows + 1:
-        raise ValueError("%s must be (offsets [%d], entries) of %s" % (name, rows + 1, dtype))
-    return off.contiguous(), idx.contiguous()
 
 
 def _mask(fixed, V, dev):
@@ -118,23 +99,19 @@ def cotangent_weights(verts, faces, nbr_csr=None, slots_csr=None, return_counts=
     """recmv_cotan_weights: w [nnz] float64, one weight per entry of nbr_csr = connectivity.neighbours_csr, of verts [V,3] f32 /
     faces [F,3] int64 (CUDA); slots_csr = connectivity.vertex_slots_csr.  Tables that are absent are built (the faces must then
     be valid).  `return_counts`: also the number of faces that added nothing."""
-    _check_mesh(verts, faces, True)
-    L.require_cuda(faces, "faces")
-    verts, faces = verts.contiguous(), faces.contiguous()
+    verts, faces = check_mesh(verts, faces)
     V, F, dev = verts.shape[0], faces.shape[0], verts.device
     if nbr_csr is None or slots_csr is None:
         _, nbr, slots = _tables(faces, V)
         nbr_csr = nbr if nbr_csr is None else nbr_csr
         slots_csr = slots if slots_csr is None else slots_csr
-    off, idx = _check_csr(nbr_csr, V, torch.int32, "nbr_csr")
-    soff, sidx = _check_csr(slots_csr, V, torch.int64, "slots_csr")
+    off, idx = check_csr(nbr_csr, V, torch.int32, "nbr_csr")
+    soff, sidx = check_csr(slots_csr, V, torch.int64, "slots_csr")
     w = L.scratch((idx.numel(),), torch.float64, dev)
     counts = torch.zeros(1, dtype=torch.int32, device=dev)
     if V:
-        with L.device_guard(dev):
-            L.check(L.lib().recmv_cotan_weights(L.ptr(verts), V, L.ptr(faces), F, L.ptr(soff), L.ptr(sidx), sidx.numel(),
-                                                L.ptr(off), L.ptr(idx), idx.numel(), L.ptr(w), L.ptr(counts), L.stream_ptr(dev)),
-                    "cotan_weights")
+        L.launch("cotan_weights", dev, L.ptr(verts), V, L.ptr(faces), F, L.ptr(soff), L.ptr(sidx), sidx.numel(), L.ptr(off),
+                 L.ptr(idx), idx.numel(), L.ptr(w), L.ptr(counts))
     return (w, int(counts.item())) if return_counts else w
 
 
@@ -183,14 +160,11 @@ def cotangent_weights_torch(verts, faces, nbr_csr=None, slots_csr=None, return_c
 def laplacian_step(verts, nbr_csr, lam, weights=None, fixed=None, bnbr=None, out=None):
     """recmv_laplacian_step: x + lam (weighted mean of the neighbours - x) of verts [V,3] f32 (CUDA) over nbr_csr; weights [nnz]
     float64 or None (uniform); fixed [V] bool or None; bnbr [V,2] int64 = connectivity.boundary_neighbours or None."""
-    L.require_cuda(verts, "verts")
-    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError("verts must be float32 of shape [V,3]")
+    verts = check_points(verts, "verts", shape="[V,3]")
     if not math.isfinite(float(lam)):
         raise ValueError("laplacian_step: lam must be finite")
-    verts = verts.contiguous()
     V, dev = verts.shape[0], verts.device
-    off, idx = _check_csr(nbr_csr, V, torch.int32, "nbr_csr")
+    off, idx = check_csr(nbr_csr, V, torch.int32, "nbr_csr")
     L.require_cuda(off, "nbr_csr")
     if weights is not None:
         L.require_cuda(weights, "weights")
@@ -205,9 +179,8 @@ def laplacian_step(verts, nbr_csr, lam, weights=None, fixed=None, bnbr=None, out
     fx = _mask(fixed, V, dev)
     out = _out(out, verts)
     if V:
-        with L.device_guard(dev):
-            L.check(L.lib().recmv_laplacian_step(L.ptr(off), L.ptr(idx), V, idx.numel(), L.ptr(verts), L.ptr(weights), L.ptr(fx),
-                                                 L.ptr(bnbr), float(lam), L.ptr(out), L.stream_ptr(dev)), "laplacian_step")
+        L.launch("laplacian_step", dev, L.ptr(off), L.ptr(idx), V, idx.numel(), L.ptr(verts), L.ptr(weights), L.ptr(fx),
+                 L.ptr(bnbr), float(lam), L.ptr(out))
     return out
 
 
@@ -263,15 +236,13 @@ def filter_face_normals(normals, areas, centroids, ff_csr, sigma_c, sigma_s, out
     for name, s in (("sigma_c", sigma_c), ("sigma_s", sigma_s)):
         if not (float(s) > 0. and math.isfinite(float(s))):
             raise ValueError("filter_face_normals: %s must be finite and > 0" % name)
-    off, idx = _check_csr(ff_csr, F, torch.int32, "ff_csr")
+    off, idx = check_csr(ff_csr, F, torch.int32, "ff_csr")
     L.require_cuda(off, "ff_csr")
     normals, areas, centroids = normals.contiguous(), areas.contiguous(), centroids.contiguous()
     out = _out(out, normals)
     if F:
-        with L.device_guard(dev):
-            L.check(L.lib().recmv_face_normal_filter(L.ptr(off), L.ptr(idx), F, idx.numel(), L.ptr(normals), L.ptr(areas),
-                                                     L.ptr(centroids), float(sigma_c), float(sigma_s), L.ptr(out),
-                                                     L.stream_ptr(dev)), "face_normal_filter")
+        L.launch("face_normal_filter", dev, L.ptr(off), L.ptr(idx), F, idx.numel(), L.ptr(normals), L.ptr(areas), L.ptr(centroids),
+                 float(sigma_c), float(sigma_s), L.ptr(out))
     return out
 
 
@@ -302,21 +273,18 @@ def filter_face_normals_torch(normals, areas, centroids, ff_csr, sigma_c, sigma_
 def update_vertices(verts, faces, normals, slots_csr=None, fixed=None, out=None):
     """recmv_vertex_from_normals: one iteration of x_i + 1/|F_i| sum_f n_f (n_f . (c_f - x_i)) on verts [V,3] f32 / faces [F,3]
     int64 with normals [F,3] f32 (CUDA); slots_csr = connectivity.vertex_slots_csr, built when absent (valid faces then)."""
-    _check_mesh(verts, faces, True)
-    L.require_cuda(faces, "faces")
+    verts, faces = check_mesh(verts, faces)
     L.require_cuda(normals, "normals")
     V, F, dev = verts.shape[0], faces.shape[0], verts.device
     if normals.dtype != torch.float32 or normals.shape != (F, 3):
         raise ValueError("normals must be float32 of shape [F,3]")
-    verts, faces, normals = verts.contiguous(), faces.contiguous(), normals.contiguous()
-    soff, sidx = _check_csr(vertex_slots_csr(faces, V) if slots_csr is None else slots_csr, V, torch.int64, "slots_csr")
+    normals = normals.contiguous()
+    soff, sidx = check_csr(vertex_slots_csr(faces, V) if slots_csr is None else slots_csr, V, torch.int64, "slots_csr")
     fx = _mask(fixed, V, dev)
     out = _out(out, verts)
     if V:
-        with L.device_guard(dev):
-            L.check(L.lib().recmv_vertex_from_normals(L.ptr(verts), V, L.ptr(faces), F, L.ptr(soff), L.ptr(sidx), sidx.numel(),
-                                                      L.ptr(normals), L.ptr(fx), L.ptr(out), L.stream_ptr(dev)),
-                    "vertex_from_normals")
+        L.launch("vertex_from_normals", dev, L.ptr(verts), V, L.ptr(faces), F, L.ptr(soff), L.ptr(sidx), sidx.numel(),
+                 L.ptr(normals), L.ptr(fx), L.ptr(out))
     return out
 
 
@@ -410,9 +378,7 @@ def smooth(verts, faces, method='taubin', iterations=10, lam=0.5, mu=None, weigh
         raise ValueError("smooth: sigma_s must be finite and > 0")
     if sigma_c is not None and not (float(sigma_c) > 0. and math.isfinite(float(sigma_c))):
         raise ValueError("smooth: sigma_c must be finite and > 0")
-    _check_mesh(verts, faces, False)
-    if use_kernels:
-        L.require_cuda(verts, "verts")
+    check_mesh(verts, faces, cuda=use_kernels, float_verts=True)
     V, dev = verts.shape[0], verts.device
     if fixed is not None and (not isinstance(fixed, torch.Tensor) or fixed.dim() != 1 or fixed.shape[0] != V):
         raise ValueError("smooth: the fixed mask must have %d entries" % V)

@@ -34,7 +34,7 @@ import torch
 
 from . import _lib as L
 from .connectivity import EdgeTable, compact, edges_packed
-from .metrics import _check_mesh
+from .mesh_args import check_mesh
 
 # Rounds of hook + compress launched between two read-backs of the device's "last round that hooked" counter.  A read-back
 # costs a host synchronisation, a round past the fixpoint two launches that change nothing.  Measured on an MI355X
@@ -82,9 +82,7 @@ def graph_components(n, links, return_info=False, rounds_per_readback=None):
     done = 0
     while True:
         rounds = min(per, cap - done)
-        with L.device_guard(dev):
-            L.check(L.lib().recmv_graph_components(n, L.ptr(links), M, K, done, rounds, L.ptr(label), L.ptr(parent),
-                                                   L.ptr(state), L.stream_ptr(dev)), "graph_components")
+        L.launch("graph_components", dev, n, L.ptr(links), M, K, done, rounds, L.ptr(label), L.ptr(parent), L.ptr(state))
         done += rounds
         last_hooking, invalid = state[:2].cpu().tolist()                          # the read-back
         if last_hooking < done:
@@ -108,9 +106,8 @@ def face_stats(verts, faces):
     area, angle, ratio = (L.scratch((F,), torch.float64, dev) for _ in range(3))
     counts = torch.zeros(2, dtype=torch.int32, device=dev)
     if F:
-        with L.device_guard(dev):
-            L.check(L.lib().recmv_mesh_face_stats(L.ptr(verts), verts.shape[0], L.ptr(faces), F, L.ptr(area), L.ptr(angle),
-                                                  L.ptr(ratio), L.ptr(counts), L.stream_ptr(dev)), "mesh_face_stats")
+        L.launch("mesh_face_stats", dev, L.ptr(verts), verts.shape[0], L.ptr(faces), F, L.ptr(area), L.ptr(angle), L.ptr(ratio),
+                 L.ptr(counts))
     return area, angle, ratio, counts
 
 
@@ -132,11 +129,10 @@ def segment_sums(values, offsets):
     chunk = int(lib.recmv_segment_sums_chunk())
     chunks = torch.zeros(S + 1, dtype=torch.int64, device=dev)
     chunks[1:] = torch.cumsum((offsets[1:] - offsets[:-1] + (chunk - 1)) // chunk, 0)
-    nbytes = int(lib.recmv_segment_sums_workspace_bytes(N, S, Cn))
-    ws = L.scratch((max(nbytes // 8, 1),), torch.float64, dev)
-    with L.device_guard(dev):
-        L.check(lib.recmv_segment_sums(L.ptr(values), N, Cn, L.ptr(offsets), S, L.ptr(chunks), L.ptr(out[0]), L.ptr(out[1]),
-                                       L.ptr(out[2]), L.ptr(ws), nbytes, L.stream_ptr(dev)), "segment_sums")
+    ws = L.workspace(nbytes := int(lib.recmv_segment_sums_workspace_bytes(N, S, Cn)), dev, "segment_sums_workspace_bytes",
+                     dtype=torch.float64)
+    L.launch("segment_sums", dev, L.ptr(values), N, Cn, L.ptr(offsets), S, L.ptr(chunks), L.ptr(out[0]), L.ptr(out[1]),
+             L.ptr(out[2]), L.ptr(ws), nbytes)
     return tuple(out)
 
 
@@ -155,12 +151,9 @@ def components(verts, faces, connectivity='vertex'):
       count C, faces_per_component [C] int64, area [C] float64, bbox_min / bbox_max [C,3] float32
       by_area [C] int64            component ids by decreasing area, ties to the lower id
       rounds, invalid_faces        the rounds recmv_graph_components needed; the faces that are not valid"""
-    _check_mesh(verts, faces, allow_empty=True)
+    verts, faces = check_mesh(verts, faces)
     if connectivity not in ('vertex', 'edge'):
         raise ValueError("connectivity must be 'vertex' or 'edge' (got %r)" % (connectivity,))
-    if verts.device != faces.device:
-        raise ValueError("verts and faces must be on one device")
-    verts, faces = verts.contiguous(), faces.contiguous()
     V, F, dev = verts.shape[0], faces.shape[0], faces.device
     if V >= 1 << 31 or F >= 1 << 31:
         raise ValueError("components: at most 2^31 - 1 vertices and faces")

@@ -52,6 +52,7 @@ import torch
 from . import _lib as L
 from . import metrics
 from . import winding
+from .mesh_args import check_mesh
 
 MAX_NODES = 1 << 28            # recmv_mc_*'s limit
 DEFAULT_BAND_STEPS = 3.        # a choice, not a measurement: marching cubes needs one step, the rest keeps its interpolation
@@ -78,7 +79,7 @@ def _winding_inside(verts, faces, lattice, winding_method):
     N, dev = lattice.n_nodes, verts.device
     method = DEFAULT_WINDING_METHOD if winding_method is None else winding_method
     tree = winding.WindingTree(verts, faces) if method == 'tree' else None
-    out = torch.empty(N, dtype=torch.uint8, device=dev)
+    out = L.scratch((N,), torch.uint8, dev)
     for a in range(0, N, WINDING_SLICE):
         pts = lattice.points(torch.arange(a, min(a + WINDING_SLICE, N), device=dev))
         w = tree.query(pts) if tree is not None else winding.winding_number(pts, verts, faces)
@@ -220,25 +221,19 @@ def distance_field(verts, faces, lattice, band=None, signed=True, method='auto',
     _check_sign(sign, winding_method)
     band = _band_of(lattice, band)
     metrics.use_grid_for_segments(method, 0, 0)
-    metrics._check_mesh(verts, faces)
-    if verts.device != faces.device:
-        raise ValueError("verts and faces must be on one device")
-    verts, faces = verts.contiguous(), faces.contiguous()
+    verts, faces = check_mesh(verts, faces, allow_empty=False)
     dev, N, dims = verts.device, lattice.n_nodes, lattice.dims
     dist2 = L.scratch((N,), torch.float32, dev)
     face = L.scratch((N,), torch.int64, dev)
     sdf = L.scratch((N,), torch.float32, dev)
     inside = L.scratch((N,), torch.uint8, dev)
     open_columns = torch.zeros(1, dtype=torch.int64, device=dev)
-    lib, desc = L.lib(), lattice.desc()
+    desc = lattice.desc()
     band_nodes = 0
     if N:
-        nbytes = int(lib.recmv_voxel_band_workspace_bytes(C.byref(desc)))
-        ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
-        with L.device_guard(dev):
-            L.check(lib.recmv_voxel_band_distance(L.ptr(verts), verts.shape[0], L.ptr(faces), faces.shape[0], C.byref(desc), band,
-                                                  L.ptr(dist2), L.ptr(face), L.ptr(ws), nbytes, L.stream_ptr(dev)),
-                    "voxel_band_distance")
+        ws = L.workspace(nbytes := int(L.lib().recmv_voxel_band_workspace_bytes(C.byref(desc))), dev, "voxel_band_workspace_bytes")
+        L.launch("voxel_band_distance", dev, L.ptr(verts), verts.shape[0], L.ptr(faces), faces.shape[0], C.byref(desc), band,
+                 L.ptr(dist2), L.ptr(face), L.ptr(ws), nbytes)
         del ws
         b = torch.tensor(band, dtype=torch.float32, device=dev)
         in_band = dist2 <= b * b
@@ -257,9 +252,8 @@ def distance_field(verts, faces, lattice, band=None, signed=True, method='auto',
             inside_band = torch.zeros(N, dtype=torch.uint8, device=dev)
             if band_nodes:
                 inside_band[index] = metrics.points_inside(lattice.points(index), verts, faces, method=method).to(torch.uint8)
-        with L.device_guard(dev):
-            L.check(lib.recmv_voxel_sign_fill(L.ptr(dist2), L.ptr(inside_band), C.byref(desc), band, int(bool(signed)), L.ptr(sdf),
-                                              L.ptr(inside), L.ptr(open_columns), L.stream_ptr(dev)), "voxel_sign_fill")
+        L.launch("voxel_sign_fill", dev, L.ptr(dist2), L.ptr(inside_band), C.byref(desc), band, int(bool(signed)), L.ptr(sdf),
+                 L.ptr(inside), L.ptr(open_columns))
         counts = [open_columns[0], _sign_conflicts(inside.view(dims), in_band.view(dims))]
         if not signed:
             counts.append(in_band.sum())
@@ -327,7 +321,7 @@ def remesh(verts, faces, step=None, resolution=None, band=None, method='auto', s
     `faces_out`, `sign`.  sign='winding' takes a mesh with holes (each capped coarsely where w = 1/2) or of overlapping pieces
     (their union); the two diagnostics then are information only."""
     _check_sign(sign, winding_method)
-    metrics._check_mesh(verts, faces)
+    check_mesh(verts, faces, allow_empty=False)
     lo, hi = _box(verts)
     length = (lambda s: DEFAULT_BAND_STEPS * s) if band is None else (lambda s: float(band))
     lattice = lattice_from_box(lo, hi, step, resolution, _steps_beyond(length))
@@ -349,7 +343,7 @@ def solidify(verts, faces, thickness, step=None, resolution=None):
         raise ValueError("thickness must be positive and finite (got %r)" % (thickness,))
     if step is not None and thickness < 3. * _f32(step):
         raise ValueError("thickness %g is below 3 steps of %g: the slab would hold no interior node" % (thickness, _f32(step)))
-    metrics._check_mesh(verts, faces)
+    check_mesh(verts, faces, allow_empty=False)
     lo, hi = _box(verts)
     length = lambda s: 0.5 * thickness + 2. * s  # noqa: E731
     lattice = lattice_from_box(lo, hi, step, resolution, _steps_beyond(length))
@@ -385,8 +379,8 @@ def volume_iou(a_v, a_f, b_v, b_f, step=None, resolution=None, method='auto', si
     `open_columns_a`, `open_columns_b`, `sign_conflicts_a`, `sign_conflicts_b`: not 0 when that mesh is not closed, and the
     figures then mean nothing — under sign='parity'; under sign='winding' (`sign` in the result) they are information only."""
     _check_sign(sign, winding_method)
-    metrics._check_mesh(a_v, a_f)
-    metrics._check_mesh(b_v, b_f)
+    check_mesh(a_v, a_f, allow_empty=False)
+    check_mesh(b_v, b_f, allow_empty=False)
     if a_v.device != b_v.device:
         raise ValueError("the two meshes must be on one device")
     if step is None and resolution is None:

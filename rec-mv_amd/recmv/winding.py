@@ -23,6 +23,7 @@ import math
 import torch
 
 from . import _lib as L
+from .mesh_args import check_mesh, check_points
 
 DEFAULT_BETA = 3.
 MAX_LEVELS = 7
@@ -33,25 +34,10 @@ METHODS = ('exact', 'tree')
 
 
 def _check(points, verts, faces):
-    L.require_cuda(points, "points")
-    L.require_cuda(verts, "verts")
-    L.require_cuda(faces, "faces")
-    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError("points must be float32 of shape [P,3]")
-    _check_mesh(verts, faces)
+    points, (verts, faces) = check_points(points, "points", shape="[P,3]"), check_mesh(verts, faces)
     if points.device != verts.device:
         raise ValueError("the points and the mesh must be on one device")
-
-
-def _check_mesh(verts, faces):
-    L.require_cuda(verts, "verts")
-    L.require_cuda(faces, "faces")
-    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError("verts must be float32 of shape [V,3]")
-    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("faces must be int64 of shape [F,3]")
-    if verts.device != faces.device:
-        raise ValueError("verts and faces must be on one device")
+    return points, verts, faces
 
 
 def chunk_faces():
@@ -62,18 +48,12 @@ def chunk_faces():
 def exact_partials(points, verts, faces):
     """One call of recmv_winding_exact on all the points: (w [P] f64, partials [chunks, P] f64) — the workspace the header
     defines, for tests and tools.  winding_number slices large query sets; this does not."""
-    _check(points, verts, faces)
-    points, verts, faces = points.contiguous(), verts.contiguous(), faces.contiguous()
+    points, verts, faces = _check(points, verts, faces)
     P, F, dev = points.shape[0], faces.shape[0], points.device
-    lib = L.lib()
-    nbytes = int(lib.recmv_winding_exact_workspace_bytes(P, F))
-    if nbytes < 0:
-        L.check(-1, "winding_exact_workspace_bytes")
+    ws = L.workspace(nbytes := int(L.lib().recmv_winding_exact_workspace_bytes(P, F)), dev, "winding_exact_workspace_bytes",
+                     dtype=torch.float64)
     w = L.scratch((P,), torch.float64, dev)
-    ws = L.scratch((max(nbytes // 8, 1),), torch.float64, dev)
-    with L.device_guard(dev):
-        L.check(lib.recmv_winding_exact(L.ptr(points), P, L.ptr(verts), verts.shape[0], L.ptr(faces), F, L.ptr(w), L.ptr(ws),
-                                        nbytes, L.stream_ptr(dev)), "winding_exact")
+    L.launch("winding_exact", dev, L.ptr(points), P, L.ptr(verts), verts.shape[0], L.ptr(faces), F, L.ptr(w), L.ptr(ws), nbytes)
     chunks = -(-F // chunk_faces())
     return w, ws[:chunks * P].view(chunks, P)
 
@@ -114,10 +94,9 @@ class WindingTree:
     [0, V) is left out; a face with a corner that is not finite makes every answer NaN."""
 
     def __init__(self, verts, faces, levels=None):
-        _check_mesh(verts, faces)
+        self.verts, self.faces = check_mesh(verts, faces)
         if levels is not None and not (1 <= int(levels) <= MAX_LEVELS):
             raise ValueError("levels must be 1 .. %d (got %r)" % (MAX_LEVELS, levels))
-        self.verts, self.faces = verts.contiguous(), faces.contiguous()
         dev = self.device = verts.device
         V, F = verts.shape[0], faces.shape[0]
         lib = L.lib()
@@ -142,9 +121,7 @@ class WindingTree:
             d.levels = lv
             cells = L.scratch((F,), torch.int64, dev)
             if F:
-                with L.device_guard(dev):
-                    L.check(lib.recmv_winding_tree_cells(L.ptr(self.verts), V, L.ptr(self.faces), F, C.byref(d), L.ptr(cells),
-                                                         L.stream_ptr(dev)), "winding_tree_cells")
+                L.launch("winding_tree_cells", dev, L.ptr(self.verts), V, L.ptr(self.faces), F, C.byref(d), L.ptr(cells))
             return cells
         if levels is None:
             cells = cells_at(MAX_LEVELS)
@@ -167,9 +144,7 @@ class WindingTree:
         self.nodes = L.scratch((int(lib.recmv_winding_tree_nodes(levels)), 16), torch.float32, dev)
         self.tris = L.scratch((max(self.n_faces, 1), 9), torch.float32, dev)
         d.nodes, d.cell_start, d.tris = self.nodes.data_ptr(), self.cell_start.data_ptr(), self.tris.data_ptr()
-        with L.device_guard(dev):
-            L.check(lib.recmv_winding_tree_build(L.ptr(self.verts), V, L.ptr(self.faces), F, L.ptr(self.order), C.byref(d),
-                                                 L.stream_ptr(dev)), "winding_tree_build")
+        L.launch("winding_tree_build", dev, L.ptr(self.verts), V, L.ptr(self.faces), F, L.ptr(self.order), C.byref(d))
         self._token = L.publish(dev)
 
     def query_order(self, points):
@@ -186,9 +161,7 @@ class WindingTree:
         beta = DEFAULT_BETA if beta is None else float(beta)
         if not (math.isfinite(beta) and beta >= 1.):
             raise ValueError("beta must be finite and at least 1 (got %r)" % (beta,))
-        L.require_cuda(points, "points")
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError("points must be float32 of shape [P,3]")
+        points = check_points(points, "points", shape="[P,3]")
         if points.device != self.device:
             raise ValueError("the points and the tree must be on one device")
         P = points.shape[0]
@@ -196,14 +169,11 @@ class WindingTree:
             return torch.full((P,), float("nan"), dtype=torch.float64, device=self.device)
         if P > TREE_SLICE:
             return torch.cat([self.query(points[a:a + TREE_SLICE], beta, sort) for a in range(0, P, TREE_SLICE)])
-        points = points.contiguous()
         w = L.scratch((P,), torch.float64, self.device)
         if P:
             L.acquire(self._token)
             order = self.query_order(points) if sort else None
-            with L.device_guard(self.device):
-                L.check(L.lib().recmv_winding_tree_query(L.ptr(points), P, L.ptr(order), C.byref(self.desc), beta, L.ptr(w),
-                                                         L.stream_ptr(self.device)), "winding_tree_query")
+            L.launch("winding_tree_query", self.device, L.ptr(points), P, L.ptr(order), C.byref(self.desc), beta, L.ptr(w))
         return w
 
 
@@ -213,12 +183,12 @@ def winding_number(points, verts, faces, method='exact', beta=None, levels=None)
     method='exact' evaluates every face; method='tree' builds a WindingTree (`levels`) and queries it with `beta`."""
     if method not in METHODS:
         raise ValueError("method must be 'exact' or 'tree' (got %r)" % (method,))
-    _check(points, verts, faces)
+    points, verts, faces = _check(points, verts, faces)
     if method == 'tree':
         return WindingTree(verts, faces, levels=levels).query(points, beta)
     if beta is not None or levels is not None:
         raise ValueError("beta and levels belong to method='tree'")
-    return _exact(points.contiguous(), verts.contiguous(), faces.contiguous())
+    return _exact(points, verts, faces)
 
 
 def inside_from_winding(w, threshold=0.5):

@@ -216,3 +216,27 @@ def test_the_query_is_reproducible_whatever_the_entry_order(level3):
     key1 = torch.sort(cell * f.shape[0] + g1.entries[:g1.n_entries].long())[0]
     key2 = torch.sort(cell * f.shape[0] + g2.entries[:g2.n_entries].long())[0]
     assert torch.equal(key1, key2) and bool((key1[1:] > key1[:-1]).all())
+
+
+def test_poisoned_workspaces_are_written_before_they_are_read(monkeypatch):
+    """RECMV_POISON=1 reaches L.workspace (0xff bytes, NaN for float64), and a grid build and query on the smallest mesh that has
+    a grid give the same tensors with it as without: every buffer they allocate is written before it is read."""
+    import mesh_topology_cases as TC
+    from recmv import _lib as L
+    from recmv import metrics
+    v, f = (torch.from_numpy(x).to(DEV) for x in TC.tetrahedron())
+    p = torch.tensor([[0.1, 0.2, 0.3], [2., -1., 0.5], [0.25, 0.25, 0.25], [-3., -3., -3.]], device=DEV)
+
+    def run():
+        g = metrics.MeshGrid(v, f)
+        return (g.offsets, g.tris, g.counts) + tuple(g.closest_point(p))
+    monkeypatch.delenv("RECMV_POISON", raising=False)
+    plain = run()
+    monkeypatch.setenv("RECMV_POISON", "1")
+    dev = torch.device(DEV)
+    assert bool((L.workspace(64, dev, "t") == 0xff).all()) and L.workspace(64, dev, "t").shape == (64,)
+    ws = L.workspace(64, dev, "t", dtype=torch.float64)
+    assert ws.shape == (8,) and bool(torch.isnan(ws).all())
+    poisoned = run()
+    assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(plain, poisoned))
+    assert not bool(torch.isnan(poisoned[4]).any()) and not bool(torch.isnan(poisoned[5]).any())
